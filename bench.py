@@ -2,12 +2,17 @@
 """Benchmark of the SRGAN-ST training hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload srgan|srresnet|srgan_vgg] [--hr 96|192] [--batch B]
+                    [--full] [--dump-outputs DIR]
 
 Default workload = BASELINE.json's metric: the "G+D+ST-loss step" (reference train.py:116-164 with D_UPDATE_INTERVAL = 1):
 SRGAN x4, 96 px HR crops, B = 16 per GPU, generator step (adversarial 1e-3 + pixel MSE + structure tensor / 3, D frozen but in
 train mode) followed by the discriminator step on gt and sr.detach(), both with Adam.  `value`, `ms_per_step`, `roofline` and
-`cpu_baseline` all describe THAT step.  The SRResNet step of BASELINE configs[1] (warmup.py:74-96, G only) is measured in the same
-run under the same protocol and reported as the secondary key `srresnet_step`.
+`cpu_baseline` all describe THAT step.
+A plain run sets up, warms up, times exactly K steps and prints the line.  `--full` adds everything else, measured after the
+headline: the SRResNet step of BASELINE configs[1] (warmup.py:74-96, G only) under the same protocol as the secondary key
+`srresnet_step`, the shared-D(sr) schedule as `srgan_shared_d_sr_step`, the per-kernel `roofline` and the `cpu_baseline`
+(`--no-secondary`, `--no-roofline`, `--no-cpu-baseline` leave single parts of it out).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32; see dump_outputs).
 `--workload srgan_vgg` = configs[2] with the VGG19 content term (seeded-random VGG19: the ImageNet weights are a network fetch).
 Prints ONE JSON line (rank 0).  Inputs are synthetic DIV2K-shaped tensors already resident in HBM.
 Exit status: 0 only when every measured leg finished; a stalled or failed leg still prints the line (with an "error" key)
@@ -281,6 +286,43 @@ def timed_steps(eng, gt, lr, steps, warmup, world, device):
     return el
 
 
+DUMP_MAX_ELEMS = 1 << 22          # per array (16 MB of float32); a larger output is written as a fixed, seeded sample
+
+
+def _dump_array(t, seed):
+    """float32 numpy copy of `t`, flattened to a seeded sample of DUMP_MAX_ELEMS entries when larger (same sample every run)."""
+    t = t.detach().float()
+    if t.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.cpu().numpy()
+
+
+def dump_outputs(eng, out_dir):
+    """What the timed path's last step hands its caller, as out_dir/<name>.npy (float32):
+        sr                 the generator's output for the batch          [B, 3, hr, hr]
+        g_loss_<name>      each weighted generator criterion (Adversarial, Pixel, ST, ...)  [1]
+        d_loss             the discriminator step's loss (G + D workloads)  [1]
+        g_params           the generator's parameters after the step, concatenated in named_parameters() order
+        d_params           the same for the discriminator (a seeded sample: its classifier alone holds 18.9 M weights)
+    Arrays above DUMP_MAX_ELEMS entries are a fixed seeded sample of their flattened values.  Written after the timed region."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrs = {"sr": eng.sr}
+    for k, v in eng.loss_values.items():
+        if v is not None:
+            arrs[f"g_loss_{k}"] = torch.as_tensor(v).reshape(1)
+    if getattr(eng, "d_loss", None) is not None:
+        arrs["d_loss"] = eng.d_loss.reshape(1)
+    arrs["g_params"] = torch.cat([p.detach().reshape(-1) for p in eng.G.parameters()])
+    if hasattr(eng, "D"):
+        arrs["d_params"] = torch.cat([p.detach().reshape(-1) for p in eng.D.parameters()])
+    for i, (name, t) in enumerate(arrs.items()):
+        np.save(os.path.join(out_dir, name + ".npy"), _dump_array(t, seed=i))
+
+
 STALL_EXIT = 3
 
 
@@ -393,10 +435,15 @@ def main():
                     help="headline on the engine's default schedule (the discriminator step re-uses the generator step's D(sr) pass); "
                          "without it the headline runs all three discriminator forwards of the reference's step and the shared "
                          "schedule is reported as the secondary key srgan_shared_d_sr_step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the secondary legs (SRResNet configs[1], shared-D(sr) schedule), the "
+                         "per-kernel roofline and the CPU baseline (a plain run only times the headline step)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32, seeded sample of large arrays)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel roofline")
     ap.add_argument("--no-secondary", "--no-full-step", dest="no_secondary", action="store_true",
-                    help="skip the secondary SRResNet (configs[1]) measurement")
+                    help="with --full: skip the secondary SRResNet (configs[1]) and shared-D(sr) measurements")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for N > 1 (nccl = RCCL; gloo only to rehearse the N > 1 code path with several "
                          "ranks sharing one GPU: ranks then map onto the visible devices modulo their count)")
@@ -427,6 +474,8 @@ def main():
     gt, lr = synth_batch(B, args.hr, device, seed=100 + rank)      # distinct shard per rank, resident in HBM
 
     el = timed_steps(eng, gt, lr, args.steps, args.warmup, world, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
     losses = {k: float(v) for k, v in eng.loss_values.items()}
     graph_active = bool(eng.graph_active)         # what actually happened, not the flag: a failed capture falls back to eager
     d_sr_reused = bool(getattr(eng, "d_sr_reused", False))
@@ -450,7 +499,7 @@ def main():
                                            if d_sr_reused else ("run: all three discriminator forwards of train.py:136,155,158"
                                                                 if args.workload != "srresnet" else None)),
                           "step_tflops": flop_per_image(args.workload, args.hr, d_sr_reused) * imgs / 1e12, "losses_last_step": losses}}
-    if args.workload == "srgan" and not args.no_secondary:
+    if args.full and args.workload == "srgan" and not args.no_secondary:
         # BASELINE configs[1] (SRResNet, G only) in the same run, same protocol, fewer steps; at every N, so the driver's
         # scaling runs also exercise the generator-only gradient all-reduce.
         extra = secondary_leg(out, "srresnet", rank, world, device, args, B)
@@ -463,9 +512,9 @@ def main():
             failed = failed or (extra2 is not None and "error" in extra2)
             if rank == 0:
                 out["srgan_shared_d_sr_step"] = extra2
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline:
         out["roofline"] = kernel_roofline(args.workload, device, args.hr, B)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.workload, B, args.hr)
     if rank == 0:
         print(json.dumps(out), flush=True)

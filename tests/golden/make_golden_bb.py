@@ -71,7 +71,8 @@ def main():
         arrs[f"{name}/pst/ind"] = stop.indices[..., 0].numpy().astype(np.int32)
         arrs[f"{name}/pst/margin"] = (stop.values[..., 1] - stop.values[..., 0]).numpy()
         arrs[f"{name}/pst/p1"] = s1.numpy()
-    save("bestbuddy", **arrs)
+    for name in ("lf48", "lf96"):                                  # one file per case: each stays below 1 MiB
+        save(f"bestbuddy_{name}", **{k: v for k, v in arrs.items() if k.startswith(name + "/")})
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
-"""BestBuddyLoss: the CPU oracle against the reference's own outputs (tests/golden/bestbuddy.npz, generated by
-make_golden_bb.py from loss.py:78-142), and the HIP path against both."""
+"""BestBuddyLoss: the CPU oracle against the reference's own outputs (tests/golden/bestbuddy_<case>.npz, generated
+by make_golden_bb.py from loss.py:78-142), and the HIP path against both."""
 import os
 
 import numpy as np
@@ -8,14 +8,14 @@ import torch
 
 from conftest import rel_err
 
-G = os.path.join(os.path.dirname(__file__), "golden", "bestbuddy.npz")
+G = {name: os.path.join(os.path.dirname(__file__), "golden", f"bestbuddy_{name}.npz") for name in ("lf48", "lf96")}   # one file per case
 
 
 @pytest.mark.parametrize("name", ["lf48", "lf96"])
 @pytest.mark.parametrize("crit", ["l1", "l2"])
 def test_oracle_matches_reference_golden(name, crit):
     from oracle import bb
-    g = np.load(G)
+    g = np.load(G[name])
     x = torch.from_numpy(g[f"{name}/x"]).requires_grad_(True)
     gt = torch.from_numpy(g[f"{name}/gt"])
     loss, ind, _ = bb.best_buddy_loss(x, gt, criterion=crit)
@@ -32,7 +32,7 @@ def test_oracle_matches_reference_golden(name, crit):
 @pytest.mark.parametrize("crit", ["l1", "l2"])
 def test_hip_best_buddy_matches_reference_golden(name, crit):
     from srganst.loss import BestBuddyLoss
-    g = np.load(G)
+    g = np.load(G[name])
     x = torch.from_numpy(g[f"{name}/x"]).cuda().requires_grad_(True)
     gt = torch.from_numpy(g[f"{name}/gt"]).cuda()
     mod = BestBuddyLoss(criterion=crit)
@@ -74,7 +74,7 @@ def test_hip_best_buddy_vs_oracle_hard_matching():
 @pytest.mark.parametrize("crit", ["l1", "l2"])
 def test_gram_oracle_matches_reference_golden(name, crit):
     from oracle import bb
-    g = np.load(G)
+    g = np.load(G[name])
     x = torch.from_numpy(g[f"{name}/x"]).requires_grad_(True)
     gt = torch.from_numpy(g[f"{name}/gt"])
     assert torch.equal(bb.gram_patches(x.detach()), torch.from_numpy(g[f"{name}/gram/p1"]))
@@ -92,7 +92,7 @@ def test_hip_gram_loss_matches_reference_golden(name, crit):
     """Gram features are 4th-order in the pixels and many candidates are near-ties: buddies are compared where the reference's
     margin is clear of fp32 noise, the loss with the tolerance that the remaining flips allow."""
     from srganst.loss import GramLoss
-    g = np.load(G)
+    g = np.load(G[name])
     x = torch.from_numpy(g[f"{name}/x"]).cuda().requires_grad_(True)
     gt = torch.from_numpy(g[f"{name}/gt"]).cuda()
     mod = GramLoss(criterion=crit)
@@ -110,7 +110,7 @@ def test_hip_gram_loss_matches_reference_golden(name, crit):
 @pytest.mark.parametrize("crit", ["l1", "l2"])
 def test_patchwise_st_oracle_matches_reference_golden(name, crit):
     from oracle import bb
-    g = np.load(G)
+    g = np.load(G[name])
     x = torch.from_numpy(g[f"{name}/x"]).requires_grad_(True)
     gt = torch.from_numpy(g[f"{name}/gt"])
     assert torch.equal(bb.st_patches(x.detach()), torch.from_numpy(g[f"{name}/pst/p1"]))
@@ -126,7 +126,7 @@ def test_patchwise_st_oracle_matches_reference_golden(name, crit):
 @pytest.mark.parametrize("crit", ["l1", "l2"])
 def test_hip_patchwise_st_matches_reference_golden(name, crit):
     from srganst.loss import PatchwiseStructureTensorLoss
-    g = np.load(G)
+    g = np.load(G[name])
     x = torch.from_numpy(g[f"{name}/x"]).cuda().requires_grad_(True)
     gt = torch.from_numpy(g[f"{name}/gt"]).cuda()
     mod = PatchwiseStructureTensorLoss(criterion=crit)

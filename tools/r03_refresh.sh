@@ -5,11 +5,11 @@ TAG=${1:-r03f}
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd $R
-python3 bench.py > $O/${TAG}_bench_srgan.json 2> $O/${TAG}_bench_srgan.err; echo "srgan rc=$?"
+python3 bench.py --full > $O/${TAG}_bench_srgan.json 2> $O/${TAG}_bench_srgan.err; echo "srgan rc=$?"
 if [ "$2" != "quick" ]; then
-python3 bench.py --workload srresnet > $O/${TAG}_bench_srresnet.json 2>/dev/null; echo "srresnet rc=$?"
-python3 bench.py --workload srgan_vgg --steps 50 --no-secondary > $O/${TAG}_bench_srgan_vgg.json 2>/dev/null; echo "vgg rc=$?"
-python3 bench.py --hr 192 --batch 8 --steps 50 --no-secondary > $O/${TAG}_bench_srgan_hr192.json 2>/dev/null; echo "hr192 rc=$?"
+python3 bench.py --full --workload srresnet > $O/${TAG}_bench_srresnet.json 2>/dev/null; echo "srresnet rc=$?"
+python3 bench.py --full --workload srgan_vgg --steps 50 --no-secondary > $O/${TAG}_bench_srgan_vgg.json 2>/dev/null; echo "vgg rc=$?"
+python3 bench.py --full --hr 192 --batch 8 --steps 50 --no-secondary > $O/${TAG}_bench_srgan_hr192.json 2>/dev/null; echo "hr192 rc=$?"
 fi
 cd /tmp && export TMPDIR=/tmp
 for wl in srgan; do
