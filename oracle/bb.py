@@ -33,14 +33,16 @@ def candidates(gt, ksize=3, pad=0, stride=3):
     return torch.cat([patches(gt, ksize, pad, stride), patches(gt2, ksize, pad, stride), patches(gt4, ksize, pad, stride)], 1), gt2, gt4
 
 
-def best_buddy_loss(x, gt, alpha=1.0, beta=1.0, ksize=3, pad=0, stride=3, dist_norm="l2", criterion="l1"):
-    """-> (loss, ind [B, n_patches], score [B, n_patches, n_candidates])."""
+def best_buddy_loss(x, gt, alpha=1.0, beta=1.0, ksize=3, pad=0, stride=3, dist_norm="l2", criterion="l1", ind=None):
+    """-> (loss, ind [B, n_patches], score [B, n_patches, n_candidates]).  ind: the buddies to take instead of torch.min's (a
+    fixed selection, e.g. another implementation's matches; the score is still computed and returned).  Same for gram_loss and
+    patchwise_st_loss."""
     p1 = patches(x, ksize, pad, stride)
     p2 = patches(gt, ksize, pad, stride)
     cat, _, _ = candidates(gt, ksize, pad, stride)
     dist = pairwise_sq_l2 if dist_norm == "l2" else pairwise_l1
     score = alpha * dist(p1, cat) + beta * dist(p2, cat)
-    ind = torch.min(score, dim=2)[1]
+    ind = torch.min(score, dim=2)[1] if ind is None else ind.to(device=score.device, dtype=torch.int64)
     sel = torch.gather(cat, 1, ind.unsqueeze(-1).expand(-1, -1, p1.shape[2]))
     loss = F.l1_loss(p1, sel) if criterion == "l1" else F.mse_loss(p1, sel)
     return loss, ind, score
@@ -57,14 +59,14 @@ def gram_patches(img, ksize=3):
     return G.reshape(B, -1, 9)
 
 
-def gram_loss(x, gt, alpha=1.0, beta=1.0, ksize=3, dist_norm="l2", criterion="l1"):
+def gram_loss(x, gt, alpha=1.0, beta=1.0, ksize=3, dist_norm="l2", criterion="l1", ind=None):
     p1, p2 = gram_patches(x, ksize), gram_patches(gt, ksize)
     gt2 = F.interpolate(gt, scale_factor=0.5, mode="bicubic", align_corners=False)
     gt4 = F.interpolate(gt, scale_factor=0.25, mode="bicubic", align_corners=False)
     cat = torch.cat([p2, gram_patches(gt2, ksize), gram_patches(gt4, ksize)], 1)
     dist = pairwise_sq_l2 if dist_norm == "l2" else pairwise_l1
     score = alpha * dist(p1, cat) + beta * dist(p2, cat)
-    ind = torch.min(score, dim=2)[1]
+    ind = torch.min(score, dim=2)[1] if ind is None else ind.to(device=score.device, dtype=torch.int64)
     sel = torch.gather(cat, 1, ind.unsqueeze(-1).expand(-1, -1, p1.shape[2]))
     loss = F.l1_loss(p1, sel) if criterion == "l1" else F.mse_loss(p1, sel)
     return loss, ind, score
@@ -80,14 +82,14 @@ def st_patches(img, sigma=0.5, rho=2.0, ksize=3):
     return ost.normalize(S).reshape(B, -1, 3 * ksize * ksize)
 
 
-def patchwise_st_loss(x, gt, sigma=0.5, rho=2.0, alpha=1.0, beta=1.0, ksize=3, dist_norm="l2", criterion="l1"):
+def patchwise_st_loss(x, gt, sigma=0.5, rho=2.0, alpha=1.0, beta=1.0, ksize=3, dist_norm="l2", criterion="l1", ind=None):
     p1, p2 = st_patches(x, sigma, rho, ksize), st_patches(gt, sigma, rho, ksize)
     gt2 = F.interpolate(gt, scale_factor=0.5, mode="bicubic", align_corners=False)
     gt4 = F.interpolate(gt, scale_factor=0.25, mode="bicubic", align_corners=False)
     cat = torch.cat([p2, st_patches(gt2, sigma, rho, ksize), st_patches(gt4, sigma, rho, ksize)], 1)
     dist = pairwise_sq_l2 if dist_norm == "l2" else pairwise_l1
     score = alpha * dist(p1, cat) + beta * dist(p2, cat)
-    ind = torch.min(score, dim=2)[1]
+    ind = torch.min(score, dim=2)[1] if ind is None else ind.to(device=score.device, dtype=torch.int64)
     sel = torch.gather(cat, 1, ind.unsqueeze(-1).expand(-1, -1, p1.shape[2]))
     loss = F.l1_loss(p1, sel) if criterion == "l1" else F.mse_loss(p1, sel)
     return loss, ind, score

@@ -7,12 +7,13 @@
 // utils.py:212-239 on a 3x3 image = three fixed 9x9 linear maps: Ix = Ax g, Iy = Ay g, J = K (Ix^2, Iy^2, Ix Iy), then
 // S / sqrt(det S + 1e-12); 27-vector (Jxx, Jyy, Jxy) x 9 pixels).  The candidate set is the GT features at scales 1, 1/2, 1/4; SR patch i is paired with the candidate j
 // minimising   alpha * max(|f_sr_i|^2 + |c_j|^2 - 2 f_sr_i.c_j, 0) + beta * max(|f_gt_i|^2 + |c_j|^2 - 2 f_gt_i.c_j, 0)
-// (the reference's expanded squared distance, clamped; first minimum wins like torch.min) and the loss is the mean L1 (or L2)
-// between the SR features and their buddies.  Only that last criterion is differentiated (through the gram map for GramLoss).
+// (the reference's expanded squared distance, clamped; torch.min's order: a NaN score is the minimum, the first NaN / first minimum
+// wins) and the loss is the mean L1 (or L2) between the SR features and their buddies.  Only that last criterion is differentiated
+// (through the gram / structure-tensor map).
 //   bb_patches_kernel<GRAM> : image [B,3,H,W] -> features [B, nP, D] + squared norms, written into the candidate table
-//   bb_match_kernel<D,GRAM> : 32 query patches x 8 candidate splits per workgroup (all lanes of a wave read the SAME candidate
+//   bb_match_kernel<GRAM>   : 32 query patches x 8 candidate splits per workgroup (all lanes of a wave read the SAME candidate
 //                             row from LDS: broadcast), argmin combined, then criterion term + gradient of the patch's 27
-//                             pixels; per-workgroup loss partials
+//                             pixels (structure tensor: staged through LDS over the whole workgroup); per-workgroup loss partials
 #include "common.h"
 
 namespace {
@@ -24,12 +25,23 @@ constexpr int BB_CH = 128;                                     // candidates per
 
 constexpr float BB_GW0 = 0.2989f, BB_GW1 = 0.587f, BB_GW2 = 0.114f;   // torchvision Grayscale (ITU-R 601), loss.py:341
 
+// pins a value as a materialised fp32 register: no contraction or other combine reaches across it
+#define BB_PIN(x) asm("" : "+v"(x))
+
 // normalised structure tensor of a 3x3 patch; mats = [Ax 81][Ay 81][K 81] (row-major [out pixel][in pixel]).
-// Also returns what the backward pass needs when `keep` is given: Ix, Iy, Jxx, Jyy, Jxy, r (9 each).
+// Also returns what the backward pass (bb_match_kernel's tail) needs when `keep` is given: Ix, Iy, Jxx, Jyy, Jxy, r (9 each).
+// Every rounding step is spelled out (fmaf) and pinned (BB_PIN): under -ffp-contract=fast the compiler otherwise picks
+// contractions per call site (and fused the final products into the match kernel's f - c), so an SR patch equal to a GT patch did
+// not reproduce the table's features (bb_patches_kernel) bit for bit, and sign(0) = 0 of the L1 criterion came out as +-1.
 __device__ __forceinline__ void bb_st_forward(const float (&p)[BB_P], const float* mats, float* f, float* keep) {
   float g[9], ix[9], iy[9];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) g[k] = BB_GW0 * p[k] + BB_GW1 * p[9 + k] + BB_GW2 * p[18 + k];
+  for (int k = 0; k < 9; ++k) {
+    float t = BB_GW0 * p[k];
+    BB_PIN(t);
+    g[k] = fmaf(BB_GW2, p[18 + k], fmaf(BB_GW1, p[9 + k], t));
+    BB_PIN(g[k]);
+  }
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
     float a = 0.f, b = 0.f;
@@ -38,6 +50,8 @@ __device__ __forceinline__ void bb_st_forward(const float (&p)[BB_P], const floa
       a = fmaf(mats[i * 9 + k], g[k], a);
       b = fmaf(mats[81 + i * 9 + k], g[k], b);
     }
+    BB_PIN(a);
+    BB_PIN(b);
     ix[i] = a;
     iy[i] = b;
   }
@@ -47,56 +61,45 @@ __device__ __forceinline__ void bb_st_forward(const float (&p)[BB_P], const floa
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
       const float kk = mats[162 + i * 9 + k];
-      jxx = fmaf(kk, ix[k] * ix[k], jxx);
-      jyy = fmaf(kk, iy[k] * iy[k], jyy);
-      jxy = fmaf(kk, ix[k] * iy[k], jxy);
+      float xx = ix[k] * ix[k], yy = iy[k] * iy[k], xy = ix[k] * iy[k];
+      BB_PIN(xx);
+      BB_PIN(yy);
+      BB_PIN(xy);
+      jxx = fmaf(kk, xx, jxx);
+      jyy = fmaf(kk, yy, jyy);
+      jxy = fmaf(kk, xy, jxy);
     }
-    const float r = 1.f / sqrtf(jxx * jyy - jxy * jxy + 1e-12f);
-    f[i] = jxx * r;
-    f[9 + i] = jyy * r;
-    f[18 + i] = jxy * r;
+    BB_PIN(jxx);
+    BB_PIN(jyy);
+    BB_PIN(jxy);
+    float q = jxy * jxy;
+    BB_PIN(q);
+    float det = fmaf(jxx, jyy, -q);
+    BB_PIN(det);
+    det = det + 1e-12f;
+    BB_PIN(det);
+    float r = 1.f / sqrtf(det);
+    BB_PIN(r);
+    float fx = jxx * r, fy = jyy * r, fz = jxy * r;
+    BB_PIN(fx);
+    BB_PIN(fy);
+    BB_PIN(fz);
+    f[i] = fx;
+    f[9 + i] = fy;
+    f[18 + i] = fz;
     if (keep) {
       keep[i] = ix[i]; keep[9 + i] = iy[i]; keep[18 + i] = jxx; keep[27 + i] = jyy; keep[36 + i] = jxy; keep[45 + i] = r;
     }
   }
 }
 
-// gp = (d feature / d patch)^T gf for the structure-tensor features (keep from bb_st_forward)
-__device__ __forceinline__ void bb_st_backward(const float* keep, const float* mats, const float* gf, float* gp) {
-  float dxx[9], dyy[9], dxy[9];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    const float jxx = keep[18 + i], jyy = keep[27 + i], jxy = keep[36 + i], r = keep[45 + i];
-    const float a = gf[i], b = gf[9 + i], c = gf[18 + i];
-    const float t = -0.5f * (a * jxx + b * jyy + c * jxy) * r * r * r;        // through r = (det + eps)^(-1/2)
-    dxx[i] = a * r + t * jyy;
-    dyy[i] = b * r + t * jxx;
-    dxy[i] = c * r - 2.f * t * jxy;
-  }
-  float dix[9], diy[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    float pxx = 0.f, pyy = 0.f, pxy = 0.f;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-      const float kk = mats[162 + i * 9 + k];                               // K^T
-      pxx = fmaf(kk, dxx[i], pxx);
-      pyy = fmaf(kk, dyy[i], pyy);
-      pxy = fmaf(kk, dxy[i], pxy);
-    }
-    const float ix = keep[k], iy = keep[9 + k];
-    dix[k] = 2.f * ix * pxx + iy * pxy;
-    diy[k] = 2.f * iy * pyy + ix * pxy;
-  }
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    float dg = 0.f;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) dg = fmaf(mats[i * 9 + k], dix[i], fmaf(mats[81 + i * 9 + k], diy[i], dg));   // Ax^T, Ay^T
-    gp[k] = BB_GW0 * dg;
-    gp[9 + k] = BB_GW1 * dg;
-    gp[18 + k] = BB_GW2 * dg;
-  }
+// torch.clamp(x, 0): NaN stays NaN (fmaxf would turn it into 0)
+__device__ __forceinline__ float bb_clamp0(float x) { return x < 0.f ? 0.f : x; }
+
+// torch.min's order on (score, index) pairs: NaN is below everything, then the smaller score, then the smaller index
+__device__ __forceinline__ bool bb_before(float s, int i, float best, int bi) {
+  if (s != s) return best == best || i < bi;
+  return best == best && (s < best || (s == best && i < bi));
 }
 
 template <int GRAM>
@@ -193,8 +196,10 @@ __global__ __launch_bounds__(BB_NT) void bb_match_kernel(const float* __restrict
     n1 = fmaf(f1[d], f1[d], n1);
     n2 = fmaf(f2[d], f2[d], n2);
   }
-  float best = 3.4e38f;
-  int bi = 0x7fffffff;
+  // each split starts at its first candidate (index `part`): an index outside [0, ncand) can never be selected - a split without
+  // candidates (ncand < BB_SPLIT) keeps index part >= ncand, which the combine below skips
+  float best = __builtin_inff();
+  int bi = part;
   for (int j0 = 0; j0 < ncand; j0 += BB_CH) {
     __syncthreads();
     for (int i = threadIdx.x; i < BB_CH * DP; i += BB_NT) {
@@ -229,21 +234,27 @@ __global__ __launch_bounds__(BB_NT) void bb_match_kernel(const float* __restrict
           }
         }
         const float cn = sn[j];
-        s = alpha * fmaxf(n1 + cn - 2.f * d1, 0.f) + beta * fmaxf(n2 + cn - 2.f * d2, 0.f);
+        s = alpha * bb_clamp0(n1 + cn - 2.f * d1) + beta * bb_clamp0(n2 + cn - 2.f * d2);
       }
-      if (s < best) { best = s; bi = j0 + j; }          // ascending j within a split: first minimum of the split
+      if (s < best || (s != s && best == best)) { best = s; bi = j0 + j; }   // ascending j: the split's first NaN / first minimum
     }
   }
   sbest[part][ql] = best;
   sbi[part][ql] = bi;
   __syncthreads();
+  // structure-tensor tail (GRAM 2): the query's d(loss)/d(feature) and forward intermediates go to LDS (the candidate chunk `sc`,
+  // free from here on) and the backward runs after a barrier in three stages spread over the workgroup - one thread running the
+  // whole backward per query spilled registers to scratch memory (224 B per lane), which no kernel of the library may use
+  float* sgf = &sc[0][0];                                 // [BB_Q][BB_P]  gf, then (dxx, dyy, dxy)
+  float* skeep = sgf + BB_Q * BB_P;                       // [BB_Q][54]    bb_st_forward's keep, then (dix, diy) in 18..35
+  static_assert(GRAM != 2 || BB_Q * (BB_P + 54) <= BB_CH * DP, "structure-tensor tail does not fit the candidate chunk");
   float lsum = 0.f;
   if (part == 0 && live) {
 #pragma unroll
     for (int k = 1; k < BB_SPLIT; ++k) {
       const float s = sbest[k][ql];
       const int i2 = sbi[k][ql];
-      if (s < best || (s == best && i2 < bi)) { best = s; bi = i2; }
+      if (i2 < ncand && bb_before(s, i2, best, bi)) { best = s; bi = i2; }
     }
     ind_out[(size_t)b * np + q] = bi;
     const float* sel = cand + ((size_t)b * ncand + bi) * D;
@@ -256,9 +267,10 @@ __global__ __launch_bounds__(BB_NT) void bb_match_kernel(const float* __restrict
     }
     float gp[BB_P];                                       // d(loss)/d(patch pixels)
     if (GRAM == 2) {
-      float keep[54], ftmp[BB_P];
-      bb_st_forward(p, mats, ftmp, keep);                 // recomputed here: only one thread in 8 needs the intermediates
-      bb_st_backward(keep, mats, gf, gp);
+      float ftmp[BB_P];
+#pragma unroll
+      for (int d = 0; d < D; ++d) sgf[ql * BB_P + d] = gf[d];
+      bb_st_forward(p, mats, ftmp, skeep + ql * 54);      // recomputed here: only one thread in 8 needs the intermediates
     } else if (GRAM == 1) {                               // G = F F^T / 27  ->  dF = (dG + dG^T) F / 27
 #pragma unroll
       for (int a = 0; a < 3; ++a)
@@ -273,13 +285,59 @@ __global__ __launch_bounds__(BB_NT) void bb_match_kernel(const float* __restrict
 #pragma unroll
       for (int d = 0; d < BB_P; ++d) gp[d] = gf[d < D ? d : 0];
     }
+    if (GRAM != 2) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c)
+      for (int c = 0; c < 3; ++c)
 #pragma unroll
-      for (int ky = 0; ky < 3; ++ky)
+        for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx)
-          dsr[(((size_t)b * 3 + c) * H + py * 3 + ky) * W + px * 3 + kx] = gp[c * 9 + ky * 3 + kx];
+          for (int kx = 0; kx < 3; ++kx)
+            dsr[(((size_t)b * 3 + c) * H + py * 3 + ky) * W + px * 3 + kx] = gp[c * 9 + ky * 3 + kx];
+    }
+  }
+  if (GRAM == 2) {                    // d(sr) = (d feature / d patch)^T gf: one (query, pixel) pair per thread and stage
+    const int q0 = q - ql, nq = min(BB_Q, np - q0);
+    __syncthreads();
+    for (int it = threadIdx.x; it < nq * 9; it += BB_NT) {          // through r = (det + eps)^(-1/2): d(Jxx, Jyy, Jxy)
+      const int r = it / 9, i = it - r * 9;
+      float* g = sgf + r * BB_P;
+      const float* kp = skeep + r * 54;
+      const float jxx = kp[18 + i], jyy = kp[27 + i], jxy = kp[36 + i], rr = kp[45 + i];
+      const float a = g[i], bb = g[9 + i], c = g[18 + i];
+      const float t = -0.5f * (a * jxx + bb * jyy + c * jxy) * rr * rr * rr;
+      g[i] = a * rr + t * jyy;
+      g[9 + i] = bb * rr + t * jxx;
+      g[18 + i] = c * rr - 2.f * t * jxy;
+    }
+    __syncthreads();
+    for (int it = threadIdx.x; it < nq * 9; it += BB_NT) {          // K^T, then the products: d(Ix), d(Iy)
+      const int r = it / 9, k = it - r * 9;
+      const float* g = sgf + r * BB_P;
+      float* kp = skeep + r * 54;
+      float pxx = 0.f, pyy = 0.f, pxy = 0.f;
+#pragma unroll
+      for (int i = 0; i < 9; ++i) {
+        const float kk = mats[162 + i * 9 + k];
+        pxx = fmaf(kk, g[i], pxx);
+        pyy = fmaf(kk, g[9 + i], pyy);
+        pxy = fmaf(kk, g[18 + i], pxy);
+      }
+      const float ix = kp[k], iy = kp[9 + k];
+      kp[18 + k] = 2.f * ix * pxx + iy * pxy;                       // jxx / jyy slots: read by the first stage only
+      kp[27 + k] = 2.f * iy * pyy + ix * pxy;
+    }
+    __syncthreads();
+    for (int it = threadIdx.x; it < nq * 9; it += BB_NT) {          // Ax^T, Ay^T, then the grayscale weights
+      const int r = it / 9, k = it - r * 9;
+      const float* kp = skeep + r * 54;
+      float dg = 0.f;
+#pragma unroll
+      for (int i = 0; i < 9; ++i) dg = fmaf(mats[i * 9 + k], kp[18 + i], fmaf(mats[81 + i * 9 + k], kp[27 + i], dg));
+      const int qq = q0 + r, yy = qq / pw * 3 + k / 3, xx = (qq % pw) * 3 + k % 3;
+      dsr[(((size_t)b * 3 + 0) * H + yy) * W + xx] = BB_GW0 * dg;
+      dsr[(((size_t)b * 3 + 1) * H + yy) * W + xx] = BB_GW1 * dg;
+      dsr[(((size_t)b * 3 + 2) * H + yy) * W + xx] = BB_GW2 * dg;
+    }
   }
   const float tot = block_sum<BB_NT>(lsum, red);
   if (threadIdx.x == 0) partials[blockIdx.x] = tot * inv_n;
@@ -342,8 +400,8 @@ __global__ __launch_bounds__(BB_NT) void bbg_match_kernel(const float* __restric
     n1 = fmaf(fq1[ql * DS + d], fq1[ql * DS + d], n1);
     n2 = fmaf(fq2[ql * DS + d], fq2[ql * DS + d], n2);
   }
-  float best = 3.4e38f;
-  int bi = 0x7fffffff;
+  float best = __builtin_inff();                          // see bb_match_kernel: torch.min's order, indices stay in [0, ncand)
+  int bi = part;
   for (int j0 = 0; j0 < ncand; j0 += BBG_CH) {
     __syncthreads();
     for (int i = threadIdx.x; i < BBG_CH * D; i += BB_NT) {
@@ -368,11 +426,11 @@ __global__ __launch_bounds__(BB_NT) void bbg_match_kernel(const float* __restric
           d2 = fmaf(fq2[ql * DS + d], cv, d2);
         }
         const float cn = sn[j];
-        d1 = fmaxf(n1 + cn - 2.f * d1, 0.f);
-        d2 = fmaxf(n2 + cn - 2.f * d2, 0.f);
+        d1 = bb_clamp0(n1 + cn - 2.f * d1);
+        d2 = bb_clamp0(n2 + cn - 2.f * d2);
       }
       const float s = alpha * d1 + beta * d2;
-      if (s < best) { best = s; bi = j0 + j; }
+      if (s < best || (s != s && best == best)) { best = s; bi = j0 + j; }
     }
   }
   sbest[part][ql] = best;
@@ -383,7 +441,7 @@ __global__ __launch_bounds__(BB_NT) void bbg_match_kernel(const float* __restric
     for (int kk = 1; kk < BB_SPLIT; ++kk) {
       const float s = sbest[kk][ql];
       const int i2 = sbi[kk][ql];
-      if (s < best || (s == best && i2 < bi)) { best = s; bi = i2; }
+      if (i2 < ncand && bb_before(s, i2, best, bi)) { best = s; bi = i2; }
     }
     ind_out[(size_t)b * np + q] = bi;
     const float* sel = cand + ((size_t)b * ncand + bi) * D;

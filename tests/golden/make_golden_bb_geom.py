@@ -2,7 +2,10 @@
 """Golden fixture for the patch losses OFF the reference's default configuration, FROM THE REFERENCE: BestBuddyLoss with other patch
 geometries (loss.py:86: ksize / pad / stride) and both matching distances (utils.py:157-191 dist_norm 'l1' / 'l2'), GramLoss and
 PatchwiseStructureTensorLoss with dist_norm 'l1'.  Inputs, loss, d(loss)/d(sr), the selected candidate per patch and the margin to the
-runner-up.  Build container only (needs /root/reference).  Re-run:  python tests/golden/make_golden_bb_geom.py"""
+runner-up.  Build container only (needs /root/reference).  Re-run:  python tests/golden/make_golden_bb_geom.py [geom|odd]
+(default: both files).  bestbuddy_odd.npz: BestBuddyLoss on images whose size is no multiple of 4 (F.interpolate(scale_factor)
+then maps coordinates with 1 / factor, not in / out size) and on a 4 x 4 image with fewer candidates (6) than the matcher's 8
+candidate splits."""
 import os
 import sys
 
@@ -68,5 +71,46 @@ def main():
     save("bestbuddy_geom", **arrs)
 
 
+# name -> (B, H, W, ksize, pad, stride, dist_norm, criterion)
+ODD_CASES = {
+    "h45w42": (2, 45, 42, 3, 0, 3, "l2", "l1"),      # the default geometry on an odd, non-square image: the general path
+    "h4w4": (2, 4, 4, 3, 1, 3, "l2", "l2"),          # 4 + 1 + 1 = 6 candidates (unpadded, unfold refuses the 1 x 1 quarter image)
+}
+
+
+def main_odd():
+    _, _, _, rutils, rloss = import_reference()
+    import torch.nn.functional as F
+    gen = torch.Generator().manual_seed(4521)
+    arrs = {}
+    for name, (B, H, W, k, pad, stride, dn, crit) in ODD_CASES.items():
+        base = torch.rand(B, 3, 12, 12, generator=gen)
+        gt = F.interpolate(base, size=(H, W), mode="bicubic", align_corners=False) + 0.05 * torch.randn(B, 3, H, W, generator=gen)
+        gt = torch.round(gt.clamp(0, 1) * 255) / 255
+        x = (gt + 0.08 * torch.randn(gt.shape, generator=gen)).clamp(0, 1).requires_grad_(True)
+        mod = rloss.BestBuddyLoss(ksize=k, pad=pad, stride=stride, dist_norm=dn, criterion=crit)
+        loss = mod(x, gt)
+        (gx,) = torch.autograd.grad(loss, x)
+        with torch.no_grad():
+            unf = lambda t: F.unfold(t, kernel_size=k, padding=pad, stride=stride).permute(0, 2, 1).contiguous()
+            p1, p2 = unf(x), unf(gt)
+            gt2 = F.interpolate(gt, scale_factor=0.5, mode="bicubic", align_corners=False)
+            gt4 = F.interpolate(gt, scale_factor=0.25, mode="bicubic", align_corners=False)
+            cat = torch.cat([p2, unf(gt2), unf(gt4)], 1)
+            score = rutils.batch_pairwise_distance(p1, cat, dn) + rutils.batch_pairwise_distance(p2, cat, dn)
+            top2 = torch.topk(score, 2, dim=2, largest=False)
+        arrs[f"{name}/x"], arrs[f"{name}/gt"] = x.detach().numpy(), gt.numpy()
+        arrs[f"{name}/gt2"], arrs[f"{name}/gt4"] = gt2.numpy(), gt4.numpy()
+        arrs[f"{name}/loss"], arrs[f"{name}/grad"] = loss.detach().numpy(), gx.numpy()
+        arrs[f"{name}/ind"] = torch.min(score, dim=2)[1].numpy().astype(np.int32)
+        arrs[f"{name}/ncand"] = np.array(cat.shape[1], dtype=np.int32)
+        arrs[f"{name}/margin"] = (top2.values[..., 1] - top2.values[..., 0]).numpy()
+    save("bestbuddy_odd", **arrs)
+
+
 if __name__ == "__main__":
-    main()
+    which = sys.argv[1] if len(sys.argv) > 1 else "all"
+    if which in ("all", "geom"):
+        main()
+    if which in ("all", "odd"):
+        main_odd()

@@ -247,3 +247,53 @@ def test_hip_best_buddy_general_path_equals_default_path():
     m2 = BestBuddyLoss()
     l2 = m2(x2.detach().cuda(), gt2.cuda())
     assert np.array_equal(m2.last_index.cpu().numpy()[clear], io.numpy()[clear]) and abs(l2.item() - lo.item()) < 1e-3 * abs(lo.item())
+
+
+# ---- odd, non-square images (F.interpolate(scale_factor) maps coordinates with 1 / factor) and a 4 x 4 image with fewer candidates
+# than the matcher's 8 candidate splits (tests/golden/bestbuddy_odd.npz, make_golden_bb_geom.py odd, from the reference itself)
+GO = os.path.join(os.path.dirname(__file__), "golden", "bestbuddy_odd.npz")
+ODD_CASES = {"h45w42": (3, 0, 3, "l2", "l1"), "h4w4": (3, 1, 3, "l2", "l2")}
+
+
+@pytest.mark.parametrize("name", list(ODD_CASES))
+def test_oracle_odd_size_matches_reference_golden(name):
+    from oracle import bb
+    k, pad, stride, dn, crit = ODD_CASES[name]
+    g = np.load(GO)
+    x = torch.from_numpy(g[f"{name}/x"]).requires_grad_(True)
+    gt = torch.from_numpy(g[f"{name}/gt"])
+    loss, ind, score = bb.best_buddy_loss(x, gt, ksize=k, pad=pad, stride=stride, dist_norm=dn, criterion=crit)
+    (gx,) = torch.autograd.grad(loss, x)
+    assert score.shape[2] == int(g[f"{name}/ncand"])
+    assert torch.equal(loss.detach(), torch.from_numpy(g[f"{name}/loss"]))
+    assert torch.equal(gx, torch.from_numpy(g[f"{name}/grad"]))
+    assert np.array_equal(ind.numpy(), g[f"{name}/ind"])
+    _, gt2, gt4 = bb.candidates(gt, k, pad, stride)
+    assert torch.equal(gt2, torch.from_numpy(g[f"{name}/gt2"])) and torch.equal(gt4, torch.from_numpy(g[f"{name}/gt4"]))
+
+
+def test_odd_size_fixture_covers_the_edges():
+    g = np.load(GO)
+    assert g["h45w42/x"].shape == (2, 3, 45, 42) and int(g["h45w42/ncand"]) == 210 + 49 + 9       # 15x14, 7x7 (22x21), 3x3 (11x10)
+    assert not np.array_equal(g["h45w42/x"][0], g["h45w42/x"][1])
+    assert int(g["h4w4/ncand"]) == 6 < 8                                                       # fewer candidates than the 8 splits
+
+
+@pytest.mark.parametrize("fn", ["best_buddy_loss", "gram_loss", "patchwise_st_loss"])
+@pytest.mark.parametrize("crit", ["l1", "l2"])
+def test_oracle_fixed_selection(fn, crit):
+    """ind= evaluates the loss at given buddies: at torch.min's own picks it is the unfixed loss bit for bit; at other picks it is
+    the criterion against exactly those candidate rows."""
+    from oracle import bb
+    g = np.load(G["lf48"])
+    x = torch.from_numpy(g["lf48/x"]).requires_grad_(True)
+    gt = torch.from_numpy(g["lf48/gt"])
+    f = getattr(bb, fn)
+    loss, ind, score = f(x, gt, criterion=crit)
+    (gx,) = torch.autograd.grad(loss, x)
+    loss2, ind2, score2 = f(x, gt, criterion=crit, ind=ind.to(torch.int32))
+    (gx2,) = torch.autograd.grad(loss2, x)
+    assert torch.equal(loss, loss2) and torch.equal(gx, gx2) and torch.equal(ind, ind2) and torch.equal(score, score2)
+    other = (ind + 1) % score.shape[2]
+    loss3, ind3, _ = f(x, gt, criterion=crit, ind=other)
+    assert torch.equal(ind3, other) and loss3.item() != loss.item()
