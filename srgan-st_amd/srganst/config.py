@@ -110,50 +110,19 @@ class Config:
         # the generator's backward starts when the discriminator branch has ended) - 5.80 ms against 5.20 ms for the cut graphs and
         # 4.97 ms single-process (tools/time_dp.py, three discriminator forwards)
         self.DIST.ONE_GRAPH = os.environ.get("SST_DP_ONE_GRAPH", "0") != "0"
-        # overlapped schedule, N > 1, RCCL: the generator's all-reduce on its own communicator (does not queue behind the discriminator's
-        # buckets).  OFF by default: it cannot be exercised here (RCCL needs one GPU per rank, a call has one) and an untested
-        # communicator must not be the first thing a multi-GPU run meets; SST_DP_G_OWN_GROUP=1 to try it on a node
-        self.DIST.G_OWN_GROUP = os.environ.get("SST_DP_G_OWN_GROUP", "0") != "0"
         self.KERNEL = dotdict()
         self.KERNEL.USE_GRAPH = True        # capture the train step into a hipGraph
         self.KERNEL.SYNC_LOSS_EVERY_STEP = False  # reference does .item() per criterion per step (train.py:141)
-        # discriminator step: D(gt) and D(sr) passes as two parallel branches of the graph (engine.TrainEngine._d_two_stream)
-        self.KERNEL.D_TWO_STREAMS = os.environ.get("SST_D_TWO_STREAMS", "0") != "0"
         # the discriminator step beside the generator's backward, whole iteration = one graph (engine.TrainEngine._iter_gd)
         self.KERNEL.OVERLAP_GD = os.environ.get("SST_OVERLAP_GD", "1") != "0"
-        # the discriminator step's D(sr.detach()) forward (train.py:158) is not run again: it repeats the generator step's D(sr)
-        # (same input, same weights, deterministic kernels); its running-statistics side effects are replayed (disc_graph.replay_running_stats)
-        # D(gt)'s forward starts with the iteration, beside the generator's forward (running statistics replayed in the reference's order).
-        # Off: measured 5.44 vs 5.36 ms - two conv-bound passes side by side just take turns (G forward + D(sr): 1.30 -> 1.84 ms)
-        self.KERNEL.EARLY_D_GT = os.environ.get("SST_EARLY_D_GT", "0") != "0"
         # merged iteration: the conv weight gradients of the discriminator's last backward pass run on the generator's stream after its
         # backward (the discriminator branch is the longer one)
         # (= how many layers, counted from the first: the ones the backward chain reaches last; 0 = none, 8 = all)
         self.KERNEL.DEFER_D_WGRAD = int(os.environ.get("SST_DEFER_D_WGRAD", "8"))
         # merged iteration: D's weight packing on the side stream beside the generator's forward
-        # ... with the two passes batched (BATCH_D_STEP) the side branch is the shorter one: nothing is moved (measured: 5.03 ms with
-        # 0 layers deferred, 5.05 / 5.08 / 5.09 / 5.11 with 1 / 2 / 3 / 4, 5.17 with all 8)
-        self.KERNEL.DEFER_D_WGRAD_BATCHED = int(os.environ.get("SST_DEFER_D_WGRAD_B", "0"))
-        # merged iteration: the discriminator's Adam in two launches - the classifier (18.9 of 23.6 M parameters) on the side stream as
-        # soon as its gradient is complete and the generator's backward has read the weights, the feature stack after the join
-        # OFF: measured slower (5.015 vs 4.960 ms, same box): the 75.5 MB classifier's update streams 528 MB through the Infinity Cache
-        # while both branches are running and evicts what their conv kernels were re-reading; at the join nothing else runs
-        self.KERNEL.SPLIT_D_ADAM = os.environ.get("SST_SPLIT_D_ADAM", "0") != "0"
-        # merged iteration, the other direction: with the discriminator step batched the GENERATOR's branch is the longer one - its
-        # weight gradients (leaves of its backward) run on the discriminator's stream after that branch's work.  Mask: 1 conv3 (9x9),
-        # 2 the up-sampling convs, 4 the grouped trunk launch, 8 conv1 (9x9); 0 = none
-        # OFF: measured slower (5.00 ms with none, 5.26 with the trunk launch moved, 5.76-5.88 with more): the generator's backward does not
-        # get shorter without them (device stamps: it ends at 4.9-5.0 ms either way - its chain of short launches only gets the chip when
-        # the discriminator branch's persistent conv kernels leave it), the moved launches just run after everything else.  Stream
-        # priorities change nothing either (main high: 5.00 ms; side high: 8.55 ms)
-        self.KERNEL.DEFER_G_WGRAD = int(os.environ.get("SST_DEFER_G_WGRAD", "0"))
-        # merged iteration: where the discriminator step's branch forks off the generator's stream - 0: after the generator step's forward
-        # and losses (round 2), 1: after the generator's backward has passed the discriminator's classifier, 2: after it has left the
-        # discriminator altogether.  The generator's backward is a chain of short launches that only advances when the other branch's
-        # persistent conv kernels let it (its first launches - a 1-workgroup BCE backward, the classifier's data-gradient - took 75 /
-        # 123 us beside the discriminator step's forward, 5 / 37 us alone): what runs before the fork runs at full speed
-        self.KERNEL.FORK_D_STEP_AT = int(os.environ.get("SST_FORK_D_STEP_AT", "0"))
         self.KERNEL.EARLY_D_PACK = os.environ.get("SST_EARLY_D_PACK", "1") != "0"
+        # the discriminator step's D(sr.detach()) forward (train.py:158) is not run again: it repeats the generator step's D(sr)
+        # (same input, same weights, deterministic kernels); its running-statistics side effects are replayed (disc_graph.replay_running_stats)
         self.KERNEL.REUSE_D_SR = os.environ.get("SST_REUSE_D_SR", "1") != "0"
         # the discriminator step's two passes, D(gt) and D(sr.detach()) (train.py:155-158), as ONE batch of 2B images with per-pass
         # train-mode BatchNorm statistics (disc_graph.forward on a list of inputs): one launch per layer instead of two, the classifier

@@ -111,19 +111,11 @@ def batched_saved(arena, sv_any):
     return sv
 
 
-def forward(module, x, p, training, need_grad=False, bump_counters=True, bn_hook=None, update_running=True, arena=None):
+def forward(module, x, p, training, need_grad=False, arena=None):
     """x: one NCHW batch, or a LIST of `groups` equally-shaped NCHW batches = that many passes of the discriminator run as ONE
     batch (each pass keeps its own train-mode BatchNorm statistics: per-pass scale / shift rows, running statistics updated pass by
     pass in list order, batch counters + groups) - the discriminator step's D(gt) and D(sr.detach()) (train.py:155-158) as one tall
-    image; returns logits [groups * B, 1] and saved tensors with sv["groups"], sv["gB"].
-    bump_counters=False: the caller has already added this pass to num_batches_tracked (two passes on two streams must
-    not race on the counters).  bn_hook(li, when) is called right before ("pre") / after ("post") each train-mode
-    bn_finalize - the only kernels of a forward that write shared state (running statistics): a caller that runs two passes
-    concurrently orders them there.  update_running=False: the pass leaves the running statistics and the batch counter alone;
-    the caller applies them later, in the reference's order, with replay_running_stats (a pass that runs EARLIER than its place
-    in the reference's sequence)."""
-    if not update_running:
-        bump_counters = False
+    image; returns logits [groups * B, 1] and saved tensors with sv["groups"], sv["gB"]."""
     groups, gB = 1, 0
     ar, slot = arena if arena is not None else (None, 0)      # (PassArena, slot): this pass writes its slice of the shared tensors
     if ar is not None:
@@ -143,7 +135,7 @@ def forward(module, x, p, training, need_grad=False, bump_counters=True, bn_hook
             raise NotImplementedError("batched passes are a train-mode schedule (eval mode has no per-pass statistics to keep apart)")
     sv = {"layers": [], "groups": groups, "gB": gB}
     wp, sv["wd"], sv["ws2"] = _packs(module, p, need_grad)
-    if training and bump_counters and not module.__dict__.get("_counters_external"):
+    if training and not module.__dict__.get("_counters_external"):
         ops.flatten_bn_counters(module).add_(groups)
     if groups > 1:
         _, c3, hh, ww = x[0].shape
@@ -168,16 +160,11 @@ def forward(module, x, p, training, need_grad=False, bump_counters=True, bn_hook
             bn = module.features[bi]
             g, b = p[f"features.{bi}.weight"], p[f"features.{bi}.bias"]
             if training:
-                if bn_hook is not None:
-                    bn_hook(len(sv["layers"]), "pre")
                 rows = None
                 if ar is not None:      # this pass's row of the [passes, C] coefficient tables
                     li_ = len(sv["layers"])
                     rows = tuple(ar.get((k, li_), (1, cout), h, slot, 0) for k in ("mean", "rstd", "scale", "shift"))
-                mean, rstd, scale, shift = ops.bn_finalize(st, cnt, g, b, bn.running_mean if update_running else None,
-                                                           bn.running_var if update_running else None, groups=groups, out=rows)
-                if bn_hook is not None:
-                    bn_hook(len(sv["layers"]), "post")
+                mean, rstd, scale, shift = ops.bn_finalize(st, cnt, g, b, bn.running_mean, bn.running_var, groups=groups, out=rows)
                 rec["mean"], rec["rstd"] = mean, rstd
                 rec["st"], rec["cnt"] = st, cnt             # replay_running_stats
             else:
@@ -348,14 +335,7 @@ def backward_features(module, p, sv, st, need_param_grads, need_dx, defer_wgrad=
 
 def backward(module, p, sv, dout, need_param_grads, need_dx):
     st = backward_classifier(module, p, sv, dout, need_param_grads)
-    hook = module.__dict__.get("_after_cls_bwd")
-    if hook is not None:             # engine.TrainEngine: the classifier's weights have been read for the last time on this stream
-        hook()
-    out = backward_features(module, p, sv, st, need_param_grads, need_dx)
-    hook = module.__dict__.get("_after_bwd")
-    if hook is not None:             # engine.TrainEngine: the generator's backward has left the discriminator
-        hook()
-    return out
+    return backward_features(module, p, sv, st, need_param_grads, need_dx)
 
 
 class DiscriminatorFn(torch.autograd.Function):

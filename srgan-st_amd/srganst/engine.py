@@ -303,17 +303,10 @@ class TrainEngine:
                              and bool(getattr(config.KERNEL, "OVERLAP_GD", False)))
         if self.one_graph_dp:
             self.overlap = False
-        # The generator's gradient travels on a communicator of its own in the overlapped schedule: on the default one its 6.2 MB
-        # message would queue behind the discriminator's buckets (collectives of one process group run in issue order on one stream)
-        # and hold the generator's Adam until the feature bucket - i.e. the whole discriminator backward - is through.
-        self.pg_g = process_group
-        if self.overlap and self.world > 1 and sdist.is_rccl(process_group) and bool(config.DIST.G_OWN_GROUP):
-            import torch.distributed as td
-            self.pg_g = td.new_group(ranks=list(range(td.get_world_size())) if process_group is None else td.get_process_group_ranks(process_group))
         self._d_a = self._d_b = self._g_f = self._g_b = None
         self.d_batched = False           # set once the discriminator step has run its two passes as one batch (KERNEL.BATCH_D_STEP)
         self.d_sr_reused = False         # set once the discriminator step has run on the generator step's D(sr) pass (KERNEL.REUSE_D_SR)
-        self._side = self._side_d = None
+        self._side_d = None
         self._it = None
         if self.one_graph_dp:
             self._g_fb, self._g_op = _GraphedStep(self._g_full, enabled=g, on_fail=f), None
@@ -329,9 +322,8 @@ class TrainEngine:
                 self._d_a = _GraphedStep(self._d_fwd_cls, enabled=g, on_fail=f)
                 self._d_b = _GraphedStep(self._d_features, enabled=g, on_fail=f)
         else:
-            two = bool(getattr(config.KERNEL, "D_TWO_STREAMS", False))
             self._g_fb, self._g_op = _GraphedStep(self._g_full, enabled=g, on_fail=f), None
-            self._d_fb, self._d_op = _GraphedStep(self._d_two_stream_full if two else self._d_full, enabled=g, on_fail=f), None
+            self._d_fb, self._d_op = _GraphedStep(self._d_full, enabled=g, on_fail=f), None
             # whole iteration as ONE graph: the discriminator step runs beside the generator's backward (see _iter_gd)
             if bool(getattr(config.KERNEL, "OVERLAP_GD", False)):
                 self._it = _GraphedStep(self._iter_gd, enabled=g, on_fail=f)
@@ -464,87 +456,41 @@ class TrainEngine:
     # -- discriminator half without autograd, in two parts (data-parallel overlap).  Same kernels with the same arguments as
     # the autograd path above, in an order that keeps every parameter's accumulation order (autograd runs the D(sr) pass
     # before the D(gt) pass: loss_fake was recorded last), so the gradients are bit-identical.
-    def _d_gt_fwd(self):
-        """D(gt)'s forward ahead of its place in the reference's sequence (it needs nothing of the generator): running statistics
-        and batch counter untouched - _d_fwd_cls replays them where the reference has the pass (after the generator step's D(sr))."""
-        from . import disc_graph
-        D = self.D
-        names = [n for n, _ in D.named_parameters()]
-        pd = dict(zip(names, [t.detach() for t in D.parameters()]))
-        pred_gt, sv_gt = disc_graph.forward(D, self.gt, pd, True, True, update_running=False)
-        return pd, pred_gt, sv_gt
-
-    def _d_fwd_cls(self, early_gt=None):
+    def _d_fwd_cls(self):
         from . import disc_graph, ops
         D = self.D
         for p in D.parameters():
             p.requires_grad = True
         self.d_opt.zero_grad(set_to_none=True)
         names = [n for n, _ in D.named_parameters()]
+        pd = dict(zip(names, [t.detach() for t in D.parameters()]))
+        B = self.gt.shape[0]
         kept = D.__dict__.get("_last_pass") if self.config.KERNEL.REUSE_D_SR else None
-        if early_gt is None and kept is None and self.config.KERNEL.BATCH_D_STEP:
-            pd = dict(zip(names, [t.detach() for t in D.parameters()]))
-            B = self.gt.shape[0]
-            if self.sr.shape == self.gt.shape and disc_graph.groups_supported(D, pd, B, 2, self.gt.shape[2], self.gt.shape[3]):
+        if self.config.KERNEL.BATCH_D_STEP:
+            if kept is None and self.sr.shape == self.gt.shape and disc_graph.groups_supported(D, pd, B, 2, self.gt.shape[2], self.gt.shape[3]):
                 # Both passes of the step as ONE batch [gt ; sr] with per-pass BatchNorm statistics (running statistics move in the
                 # reference's order: gt, then sr), one backward over 2B images.
                 D.__dict__.pop("_last_pass", None)
                 pred, sv = disc_graph.forward(D, [self.gt, self.sr], pd, True, True)
-                pred_gt, pred_sr = pred[:B], pred[B:]
-                dl = torch.empty_like(pred)
-                loss_real, _ = ops.bce_logits(pred_gt, self.real, want_loss=True, want_grad=True, grad_out=dl[:B])
-                loss_fake, _ = ops.bce_logits(pred_sr, self.fake, want_loss=True, want_grad=True, grad_out=dl[B:])
-                self.d_loss, self.pred_gt, self.pred_sr = loss_real + loss_fake, pred_gt, pred_sr
-                st = disc_graph.backward_classifier(D, pd, sv, dl, True)
-                self._d_state = (pd, None, None, sv, st)
-                self.d_batched = True
-                flat = D.__dict__["_flat_grads"][-1]
-                plist = [pd[n] for n in names]
-                offs, total = ops.flat_layout(plist)
-                cut = offs[names.index("classifier.0.weight")]
-                self._d_flat, self._d_buckets = flat, (flat[cut:total], flat[:cut])
-                return self.d_loss
-        if early_gt is None and kept is not None and kept.get("arena") is not None and self.config.KERNEL.BATCH_D_STEP:
-            pd = dict(zip(names, [t.detach() for t in D.parameters()]))
-            if (kept["x_ptr"] == self.sr.data_ptr() and kept["x_shape"] == tuple(self.sr.shape) and tuple(self.gt.shape) == tuple(self.sr.shape)
-                    and all(kept["p"][n].data_ptr() == pd[n].data_ptr() and kept["p"][n]._version == pd[n]._version for n in names)):
+                return self._d_cls_batched(pd, names, pred[:B], pred[B:], sv)
+            if (kept is not None and kept.get("arena") is not None and tuple(self.gt.shape) == tuple(self.sr.shape)
+                    and self._is_sr_pass(kept, pd, names)):
                 # The kept D(sr) pass sits in slot 1 of a two-pass arena: D(gt) fills slot 0, the running statistics take D(sr.detach())'s
                 # step (replayed, as below), and ONE backward runs over the 2B images with per-pass BatchNorm rows.
                 D.__dict__.pop("_last_pass", None)
-                B = self.gt.shape[0]
                 arena = kept["arena"]
                 pred_gt, sv_gt = disc_graph.forward(D, self.gt, pd, True, True, arena=(arena, 0))
                 disc_graph.replay_running_stats(D, pd, kept["sv"])
-                pred_sr = kept["out"].detach()
                 self.d_sr_reused = True
-                dl = torch.empty(2 * B, 1, device=pred_gt.device, dtype=torch.float32)
-                loss_real, _ = ops.bce_logits(pred_gt, self.real, want_loss=True, want_grad=True, grad_out=dl[:B])
-                loss_fake, _ = ops.bce_logits(pred_sr, self.fake, want_loss=True, want_grad=True, grad_out=dl[B:])
-                self.d_loss, self.pred_gt, self.pred_sr = loss_real + loss_fake, pred_gt, pred_sr
-                sv = disc_graph.batched_saved(arena, sv_gt)
-                st = disc_graph.backward_classifier(D, pd, sv, dl, True)
-                self._d_state = (pd, None, None, sv, st)
-                self.d_batched = True
-                flat = D.__dict__["_flat_grads"][-1]
-                plist = [pd[n] for n in names]
-                offs, total = ops.flat_layout(plist)
-                cut = offs[names.index("classifier.0.weight")]
-                self._d_flat, self._d_buckets = flat, (flat[cut:total], flat[:cut])
-                return self.d_loss
-        if early_gt is not None:
-            pd, pred_gt, sv_gt = early_gt
-            disc_graph.replay_running_stats(D, pd, sv_gt)
-        else:
-            pd = dict(zip(names, [t.detach() for t in D.parameters()]))
-            pred_gt, sv_gt = disc_graph.forward(D, self.gt, pd, True, True)
+                return self._d_cls_batched(pd, names, pred_gt, kept["out"].detach(), disc_graph.batched_saved(arena, sv_gt))
+        pred_gt, sv_gt = disc_graph.forward(D, self.gt, pd, True, True)
         loss_real, dl_gt = ops.bce_logits(pred_gt, self.real, want_loss=True, want_grad=True)
         # D(sr.detach()) (train.py:158) repeats the generator step's D(sr) (train.py:136): same input, same weights (D's Adam comes
         # after both), train-mode BatchNorm both times - every kernel is deterministic, so the pass would reproduce the saved
         # activations and logits bit for bit.  It is not run again: its side effects (running statistics, batch counter) are
         # replayed in the reference's order (after D(gt)'s) and the backward works on the generator step's saved pass.
         kept = D.__dict__.pop("_last_pass", None) if self.config.KERNEL.REUSE_D_SR else None
-        if (kept is not None and kept["x_ptr"] == self.sr.data_ptr() and kept["x_shape"] == tuple(self.sr.shape)
-                and all(kept["p"][n].data_ptr() == pd[n].data_ptr() and kept["p"][n]._version == pd[n]._version for n in names)):
+        if kept is not None and self._is_sr_pass(kept, pd, names):
             disc_graph.replay_running_stats(D, pd, kept["sv"])
             pred_sr, sv_sr = kept["out"].detach(), kept["sv"]
             self.d_sr_reused = True
@@ -559,81 +505,50 @@ class TrainEngine:
         finally:
             D.__dict__.pop("_grad_accum", None)
         self._d_state = (pd, sv_sr, st_sr, sv_gt, st_gt)
-        flat = D.__dict__["_flat_grads"][-1]
-        plist = [pd[n] for n in names]
-        offs, total = ops.flat_layout(plist)
-        cut = offs[names.index("classifier.0.weight")]          # features.* come first in the reference's parameter order
-        self._d_flat, self._d_buckets = flat, (flat[cut:total], flat[:cut])
+        self._cut_d_buckets(pd, names)
         return self.d_loss
 
+    def _is_sr_pass(self, kept, pd, names):
+        """Is the generator step's kept D(sr) pass (disc_graph.DiscriminatorFn) a pass over self.sr with D's current weights?"""
+        return (kept["x_ptr"] == self.sr.data_ptr() and kept["x_shape"] == tuple(self.sr.shape)
+                and all(kept["p"][n].data_ptr() == pd[n].data_ptr() and kept["p"][n]._version == pd[n]._version for n in names))
+
+    def _d_cls_batched(self, pd, names, pred_gt, pred_sr, sv):
+        """_d_fwd_cls on both passes as one batch of 2B images (logits of D(gt) first): the losses, their logit gradients in one
+        buffer and ONE classifier backward."""
+        from . import disc_graph, ops
+        B = pred_gt.shape[0]
+        dl = torch.empty(2 * B, 1, device=pred_gt.device, dtype=torch.float32)
+        loss_real, _ = ops.bce_logits(pred_gt, self.real, want_loss=True, want_grad=True, grad_out=dl[:B])
+        loss_fake, _ = ops.bce_logits(pred_sr, self.fake, want_loss=True, want_grad=True, grad_out=dl[B:])
+        self.d_loss, self.pred_gt, self.pred_sr = loss_real + loss_fake, pred_gt, pred_sr
+        st = disc_graph.backward_classifier(self.D, pd, sv, dl, True)
+        self._d_state = (pd, None, None, sv, st)
+        self.d_batched = True
+        self._cut_d_buckets(pd, names)
+        return self.d_loss
+
+    def _cut_d_buckets(self, pd, names):
+        """The two all-reduce buckets of the discriminator's flat gradient buffer: (classifier, feature stack)."""
+        from . import ops
+        flat = self.D.__dict__["_flat_grads"][-1]
+        offs, total = ops.flat_layout([pd[n] for n in names])
+        cut = offs[names.index("classifier.0.weight")]          # features.* come first in the reference's parameter order
+        self._d_buckets = (flat[cut:total], flat[:cut])
+
     def _d_features(self, defer_gt_wgrad=None):
-        """defer_gt_wgrad (a list): the conv weight gradients of the D(gt) pass are handed back instead of launched
-        (disc_graph.backward_features); they ADD into what the D(sr) pass wrote, which is complete by then on this stream."""
+        """defer_gt_wgrad (a list; passes run one by one only): the conv weight gradients of the D(gt) pass are handed back instead of
+        launched (disc_graph.backward_features); they ADD into what the D(sr) pass wrote, which is complete by then on this stream."""
         from . import disc_graph
         pd, sv_sr, st_sr, sv_gt, st_gt = self._d_state
-        if sv_sr is None:               # both passes as one batch (_d_fwd_cls): one backward, its weight gradients are the leaves
-            grads, _ = disc_graph.backward_features(self.D, pd, sv_gt, st_gt, True, False, defer_wgrad=defer_gt_wgrad,
-                                                    defer_below=int(self.config.KERNEL.DEFER_D_WGRAD_BATCHED))
+        if sv_sr is None:               # both passes as one batch (_d_fwd_cls): one backward
+            grads, _ = disc_graph.backward_features(self.D, pd, sv_gt, st_gt, True, False)
         else:
             grads, _ = disc_graph.backward_features(self.D, pd, sv_sr, st_sr, True, False)
             disc_graph.backward_features(self.D, pd, sv_gt, st_gt, True, False, defer_wgrad=defer_gt_wgrad,
                                          defer_below=int(self.config.KERNEL.DEFER_D_WGRAD))
         for n, p in self.D.named_parameters():
             p.grad = grads[n]
-
-    # -- discriminator half with its two passes on two streams (under capture: two parallel branches of the hipGraph).  D(gt) and
-    # D(sr.detach()) share nothing but the weights (read-only here), the BatchNorm running statistics (ordered pass by pass at
-    # every bn_finalize, so the buffers move exactly as in the sequential order gt -> sr) and the gradient buffer (each pass
-    # writes its own flat buffer; they are added afterwards: fl(a + b), bit for bit what the accumulate flag does).  The many
-    # latency-bound launches of one pass (BatchNorm finalize / backward reduce / apply, 1-4 workgroups each) then run beside
-    # the other pass's kernels instead of in front of them.  Measured: 6.49 -> 6.18 ms per iteration; superseded by _iter_gd
-    # (5.92 ms), kept as KERNEL.D_TWO_STREAMS for engines that do not merge the iteration.
-    def _d_two_stream(self):
-        from . import disc_graph, ops
-        D = self.D
-        for p in D.parameters():
-            p.requires_grad = True
-        self.d_opt.zero_grad(set_to_none=True)
-        names = [n for n, _ in D.named_parameters()]
-        pd = dict(zip(names, [t.detach() for t in D.parameters()]))
-        ops.flatten_bn_counters(D).add_(2)
-        main = torch.cuda.current_stream()
-        if self._side is None:
-            self._side = torch.cuda.Stream()
-        side = self._side
-        ev = {}
-
-        def hook_a(li, when):
-            if when == "post":
-                e = torch.cuda.Event()
-                e.record(main)
-                ev[li] = e
-
-        def hook_b(li, when):
-            if when == "pre":
-                side.wait_event(ev[li])
-
-        pred_gt, sv_gt = disc_graph.forward(D, self.gt, pd, True, True, bump_counters=False, bn_hook=hook_a)   # packs weights if needed
-        loss_real, dl_gt = ops.bce_logits(pred_gt, self.real, want_loss=True, want_grad=True)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            pred_sr, sv_sr = disc_graph.forward(D, self.sr, pd, True, True, bump_counters=False, bn_hook=hook_b)
-            loss_fake, dl_sr = ops.bce_logits(pred_sr, self.fake, want_loss=True, want_grad=True)
-            st_sr = disc_graph.backward_classifier(D, pd, sv_sr, dl_sr, True)
-            g_sr, _ = disc_graph.backward_features(D, pd, sv_sr, st_sr, True, False)
-            flat_sr = D.__dict__["_flat_grads"][-1]
-        st_gt = disc_graph.backward_classifier(D, pd, sv_gt, dl_gt, True)
-        g_gt, _ = disc_graph.backward_features(D, pd, sv_gt, st_gt, True, False)
-        flat_gt = D.__dict__["_flat_grads"][-1]
-        ops.check_capture_join(main)          # inside the side branch of a merged capture this join is the one the runtime faults on
-        main.wait_stream(side)
-        flat_sr.add_(flat_gt)                 # autograd order of the sequential path: the D(sr) pass writes, the D(gt) pass accumulates
-        self.d_loss, self.pred_gt, self.pred_sr = loss_real + loss_fake, pred_gt, pred_sr
-        lst = D.__dict__["_flat_grads"]
-        lst[:] = [t for t in lst if t is not flat_sr] + [flat_sr]      # the buffer that holds p.grad is the newest one (FlatAdam / dist look there first)
-        for n, p in D.named_parameters():
-            p.grad = g_sr[n]
-        return self.d_loss
 
     # -- the whole iteration (train.py:125-164) as one launch DAG: the discriminator step needs nothing of the generator's
     # backward (only sr, D's weights and - for the order of the running statistics - the generator step's D(sr) FORWARD), so it
@@ -656,32 +571,28 @@ class TrainEngine:
         self.D.__dict__["_keep_pass"], self.D.__dict__["_last_pass"] = True, None
         self._request_arena()
         from . import disc_graph, ops
-        adv_d = "Adversarial" in cfg.MODEL.G_LOSS.CRITERIONS
+        adv = "Adversarial" in cfg.MODEL.G_LOSS.CRITERIONS
         # the batch counters of D's BatchNorms move by one per pass (run or replayed): ONE add per iteration instead of three
         self.D.__dict__["_counters_external"] = True
-        n_pass = 3 if adv_d else 2
-        adv = adv_d
-        ride = bool(adv and cfg.KERNEL.EARLY_D_PACK)       # ... and that add rides in the early pack launch below when there is one
-        if not ride:
+        n_pass = 3 if adv else 2
+        early_pack = bool(adv and cfg.KERNEL.EARLY_D_PACK)      # ... and that add rides in the early pack launch below when there is one
+        if not early_pack:
             ops.flatten_bn_counters(self.D).add_(n_pass)
         ops.debug_stamp(0)
         main = torch.cuda.current_stream()
         if self._side_d is None:
             self._side_d = torch.cuda.Stream()
-        early_gt = None
-        if adv and (cfg.KERNEL.EARLY_D_PACK or cfg.KERNEL.EARLY_D_GT):
+        side = self._side_d
+        if early_pack:
             # D's weights are packed (one multi-tensor launch + one per stride-2 layer, 67 us) for all passes of the iteration on the
             # side stream, beside the generator's forward, instead of in front of D(sr) on the critical path
             names = [n for n, _ in self.D.named_parameters()]
-            self._side_d.wait_stream(main)
-            with torch.cuda.stream(self._side_d):
-                disc_graph._packs(self.D, dict(zip(names, [t.detach() for t in self.D.parameters()])), True,
-                                  counter_add=n_pass if ride else 0)
-                if cfg.KERNEL.EARLY_D_GT:            # D(gt)'s forward beside the generator's forward as well (measured slower, off)
-                    early_gt = self._d_gt_fwd()
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                disc_graph._packs(self.D, dict(zip(names, [t.detach() for t in self.D.parameters()])), True, counter_add=n_pass)
         sr = self.G(self.lr)
-        if adv and (cfg.KERNEL.EARLY_D_PACK or cfg.KERNEL.EARLY_D_GT):
-            main.wait_stream(self._side_d)           # D(sr) below reads the packed weights
+        if early_pack:
+            main.wait_stream(side)               # D(sr) below reads the packed weights
         ops.debug_stamp(1)
         total, vals = _criterion_total(sr, self.gt, cfg.MODEL.G_LOSS.CRITERIONS, cfg.MODEL.G_LOSS.CRITERION_WEIGHTS,
                                        adversarial=lambda crit: crit(self.D(sr), self.real),
@@ -690,77 +601,31 @@ class TrainEngine:
         self.D.__dict__.pop("_arena_request", None)
         self.sr = sr.detach()
         ops.debug_stamp(2)
-        side = self._side_d
-        dp_ar = {}
-
-        def start_side():                       # the discriminator step's branch forks HERE off the stream the caller runs on (main)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):       # both passes on ONE side stream (a helper stream forked from it could only be joined into
-                ops.debug_stamp(3)              # `main`: ops.check_capture_join)
-                self._d_fwd_cls(early_gt)
-                ops.debug_stamp(4)
-                # data parallel, one graph: the classifier bucket (75.5 MB) goes out now, under the feature stack's backward.  The
-                # collective runs on the process group's own stream - forked from this side stream, i.e. a second-level fork: its
-                # wait() below is issued on `main`, the capture's origin stream (a second-level stream joined into a first-level one
-                # is what crashes hipStreamEndCapture).
-                dp_ar["c"] = sdist.AsyncAllReduce(self._d_buckets[0], self.pg, force=True) if self.one_graph_dp else None
-        fork_at = int(cfg.KERNEL.FORK_D_STEP_AT) if adv_d else 0
-        if fork_at == 0:
-            start_side()
-        else:
-            self.D.__dict__["_after_cls_bwd" if fork_at == 1 else "_after_bwd"] = start_side
-        # D's Adam in two parts (KERNEL.SPLIT_D_ADAM): the classifier's gradient is complete here; its weights are read once more,
-        # by the head of the generator's backward (through D), which hands over with an event - then the classifier's update runs on
-        # the side stream beside the rest of both branches and only the feature stack's (4.7 M parameters) is left for the join.
-        names = [n for n, _ in self.D.named_parameters()]
-        cls0 = names.index("classifier.0.weight")
-        split = (bool(cfg.KERNEL.SPLIT_D_ADAM) and not self.dp and fork_at == 0 and self._d_flat is not None
-                 and hasattr(self.d_opt, "step_params"))
-
-        def cls_adam():
-            ev = torch.cuda.Event()
-            ev.record()                          # on the stream the backward runs on
-            with torch.cuda.stream(side):
-                side.wait_event(ev)
-                self.d_opt.step_params(cls0, len(names), flat_grad=self._d_flat)
-        if split:
-            if adv_d:
-                self.D.__dict__["_after_cls_bwd"] = cls_adam
-            else:
-                cls_adam()
+        side.wait_stream(main)                  # the discriminator step's branch forks HERE
+        with torch.cuda.stream(side):           # both passes on ONE side stream (a helper stream forked from it could only be joined into
+            ops.debug_stamp(3)                  # `main`: ops.check_capture_join)
+            self._d_fwd_cls()
+            ops.debug_stamp(4)
+            # data parallel, one graph: the classifier bucket (75.5 MB) goes out now, under the feature stack's backward.  The
+            # collective runs on the process group's own stream - forked from this side stream, i.e. a second-level fork: its
+            # wait() below is issued on `main`, the capture's origin stream (a second-level stream joined into a first-level one
+            # is what crashes hipStreamEndCapture).
+            ar_c = sdist.AsyncAllReduce(self._d_buckets[0], self.pg, force=True) if self.one_graph_dp else None
         ops.debug_stamp(6)
-        # The generator's weight gradients selected by KERNEL.DEFER_G_WGRAD leave its backward chain and run on the side stream behind
-        # the discriminator step's work (gen_graph.backward hands them over): its Adam then waits for the join.
-        g_def = [] if (int(cfg.KERNEL.DEFER_G_WGRAD) and not self.dp) else None
-        if g_def is not None:
-            self.G.__dict__["_defer_wgrad"] = (g_def, int(cfg.KERNEL.DEFER_G_WGRAD))
-        try:
-            with torch.autograd.set_multithreading_enabled(False):      # backward on this thread: one thread feeds the open capture
-                total.backward(_one(total))
-        finally:
-            self.D.__dict__.pop("_after_cls_bwd", None)
-            self.D.__dict__.pop("_after_bwd", None)
-            self.G.__dict__.pop("_defer_wgrad", None)
+        with torch.autograd.set_multithreading_enabled(False):      # backward on this thread: one thread feeds the open capture
+            total.backward(_one(total))
         ops.debug_stamp(7)
         self.loss_values = vals
         if self.one_graph_dp:
             self._g_allreduce()                 # 6.2 MB, behind the classifier bucket on the process group's stream
-        if not g_def:
-            self.g_opt.step()
+        self.g_opt.step()
         ops.debug_stamp(8)
-        with torch.cuda.stream(side):           # (issued after the generator's backward: the classifier's Adam sits in front of it)
+        with torch.cuda.stream(side):
             # (data parallel: nothing is deferred - the feature bucket goes out right behind this call and must be complete)
             deferred = [] if (cfg.KERNEL.DEFER_D_WGRAD and not self.dp) else None
             self._d_features(deferred)
             ar_f = sdist.AsyncAllReduce(self._d_buckets[1], self.pg, force=True) if self.one_graph_dp else None
             ops.debug_stamp(5)
-            for ev, launch, tensors in (g_def or ()):
-                side.wait_event(ev)
-                if not torch.cuda.is_current_stream_capturing():     # eager: main's allocator must not re-use these blocks before `side` is done
-                    for t in tensors:
-                        if t is not None:
-                            t.record_stream(side)
-                launch()
         # The side branch is the longer one (D(gt) forward + two backward passes against one generator backward).  The conv weight
         # gradients of its last pass are leaves of that chain: they run HERE, on the generator's stream, which would otherwise idle
         # until the join - each behind the event of its dy.  Same kernels, same arguments, same accumulation order per parameter
@@ -773,25 +638,14 @@ class TrainEngine:
                     if t is not None:    # tensors until every launch of the iteration is issued) - and recording the CAPTURE stream, which
                         t.record_stream(main)   # is destroyed after the capture, left the allocator with a dangling stream (segfaults in later replays)
             launch()
-        main.wait_stream(self._side_d)
-        if g_def:
-            self.g_opt.step()                    # its last weight gradients came from the side stream
+        main.wait_stream(side)
         if self.one_graph_dp:
-            dp_ar["c"].wait()                    # on the origin stream
+            ar_c.wait()                          # on the origin stream
             ar_f.wait()
-        if split:
-            self.d_opt.step_params(0, cls0, flat_grad=self._d_flat)
-            self.D.__dict__["_packs_fresh"] = False      # weights changed
-        else:
-            self._d_step()
+        self._d_step()
         self.D.__dict__["_counters_external"] = False
         ops.debug_stamp(9)
         return vals
-
-    def _d_two_stream_full(self):
-        v = self._d_two_stream()
-        self._d_step()
-        return v
 
     def _d_step(self):
         self.d_opt.step()
@@ -806,7 +660,7 @@ class TrainEngine:
         """See WarmupEngine.close."""
         self._g_fb = self._g_op = self._d_fb = self._d_op = self._d_a = self._d_b = self._it = self._g_f = self._g_b = None
         self._g_total = None
-        self._d_state = self._d_flat = self._d_buckets = None
+        self._d_state = self._d_buckets = None
         self.D.__dict__.pop("_last_pass", None)
         self.gt = self.lr = self.sr = None
 
@@ -829,9 +683,9 @@ class TrainEngine:
                 self._d_b()
                 ar_f = sdist.AsyncAllReduce(self._d_buckets[1], self.pg, force=True)
         self._g_b()
-        ar_g = sdist.AsyncAllReduce(sdist.module_flat_grad(self.G), self.pg_g, force=True)
+        ar_g = sdist.AsyncAllReduce(sdist.module_flat_grad(self.G), self.pg, force=True)
         if ar_g.flat is None:                                    # gradients not in one flat buffer: the generic path
-            sdist.allreduce_module_grads(self.G, self.pg_g, force=True)
+            sdist.allreduce_module_grads(self.G, self.pg, force=True)
         ar_g.wait()
         self._g_op()
         if did_d:

@@ -332,18 +332,18 @@ def test_train_engine_capture_failure_drops_every_graph(fail):
 
 @pytest.mark.parametrize("interval", [1, 2])
 def test_train_engine_schedules_are_bit_identical(interval):
-    """The iteration's launch schedules (engine.TrainEngine): sequential [G step][D step] (round 1), the discriminator step's two
-    passes on two streams (KERNEL.D_TWO_STREAMS), and the default - whole iteration as ONE graph with the discriminator step beside
-    the generator's backward (KERNEL.OVERLAP_GD, _iter_gd).  Same kernels, same arguments, same order per tensor: parameters,
-    BatchNorm buffers (running statistics move in the order D(sr) of the G step, D(gt), D(sr)) and losses must be bit-identical,
-    eager and under hipGraph replay, with D updated every step and every second step."""
+    """The iteration's launch schedules (engine.TrainEngine): sequential [G step][D step] (round 1) and the default - whole
+    iteration as ONE graph with the discriminator step beside the generator's backward (KERNEL.OVERLAP_GD, _iter_gd).  Same
+    kernels, same arguments, same order per tensor: parameters, BatchNorm buffers (running statistics move in the order D(sr) of the
+    G step, D(gt), D(sr)) and losses must be bit-identical, eager and under hipGraph replay, with D updated every step and every
+    second step."""
     from srganst.engine import TrainEngine
     from srganst.loss import MSELoss, StructureTensorLoss
     from srganst.model import Discriminator, Generator
 
-    def run(gd, two, use_graph, reuse=True, early=True, defer=True, pack_early=True):
+    def run(gd, use_graph, reuse=True, defer=True, pack_early=True):
         cfg = make_cfg(16, 2, 8)
-        cfg.KERNEL.OVERLAP_GD, cfg.KERNEL.D_TWO_STREAMS, cfg.KERNEL.REUSE_D_SR, cfg.KERNEL.EARLY_D_GT = gd, two, reuse, early
+        cfg.KERNEL.OVERLAP_GD, cfg.KERNEL.REUSE_D_SR = gd, reuse
         cfg.KERNEL.EARLY_D_PACK = pack_early
         cfg.KERNEL.DEFER_D_WGRAD = {True: 8, False: 0}.get(defer, defer)      # layers whose last-pass weight gradients move to the other stream
         torch.manual_seed(1)
@@ -363,25 +363,21 @@ def test_train_engine_schedules_are_bit_identical(interval):
         sd["d_loss"] = eng.d_loss.clone()
         return sd
 
-    ref = run(False, False, False)                      # sequential, eager
+    ref = run(False, False)                             # sequential, eager
     assert int(ref["D.features.3.num_batches_tracked"]) == 8 + 2 * (8 // interval)
     # the merged schedule does not run D(sr.detach()) again (KERNEL.REUSE_D_SR: the generator step's D(sr) pass is re-used and the
     # running statistics replayed) - with and without that, against the sequential schedule that runs all three passes
-    # ... and starts D(gt)'s forward with the iteration (KERNEL.EARLY_D_GT, statistics replayed in the reference's order)
-    for gd, two, use_graph, reuse, early in ((False, False, True, True, True), (False, True, False, True, True), (False, True, True, True, True),
-                                             (True, False, False, True, True), (True, False, True, True, True),
-                                             (True, False, False, False, False), (True, False, True, False, False),
-                                             (True, False, True, True, False), (True, False, True, False, True)):
-        out = run(gd, two, use_graph, reuse, early)
+    for gd, use_graph, reuse in ((False, True, True), (True, False, True), (True, True, True), (True, False, False), (True, True, False)):
+        out = run(gd, use_graph, reuse)
         for k in ref:
-            assert torch.equal(ref[k], out[k]), (gd, two, use_graph, reuse, early, k)
+            assert torch.equal(ref[k], out[k]), (gd, use_graph, reuse, k)
     # ... and without moving the last pass's weight gradients to the generator's stream (KERNEL.DEFER_D_WGRAD)
     for use_graph, defer in ((False, False), (True, False), (True, 3)):
-        out = run(True, False, use_graph, defer=defer)
+        out = run(True, use_graph, defer=defer)
         for k in ref:
             assert torch.equal(ref[k], out[k]), ("defer", defer, use_graph, k)
     # ... and with D's weights packed in front of D(sr) on the main stream instead of beside the generator's forward (KERNEL.EARLY_D_PACK)
-    out = run(True, False, True, pack_early=False)
+    out = run(True, True, pack_early=False)
     for k in ref:
         assert torch.equal(ref[k], out[k]), ("late pack", k)
 

@@ -37,6 +37,16 @@ def test_config_surface_matches_reference_defaults():
     assert "ST" not in Config().MODEL.G_LOSS.CRITERIONS        # instances do not share dicts
 
 
+def test_config_switch_sets():
+    """The engine's switches, exactly: a schedule variant that was measured and removed does not come back
+    unnoticed, and a test that still sets one fails here."""
+    from srganst.config import Config
+    c = Config()
+    assert set(c.KERNEL) == {"USE_GRAPH", "SYNC_LOSS_EVERY_STEP", "OVERLAP_GD", "DEFER_D_WGRAD", "EARLY_D_PACK", "REUSE_D_SR",
+                             "BATCH_D_STEP", "LR_ON_DEVICE"}
+    assert set(c.DIST) == {"BACKEND", "BUCKET_D", "OVERLAP_COMM", "ONE_GRAPH"}
+
+
 def test_parameter_trees_and_init_order_match_oracle():
     from oracle import model as om
     from srganst.config import Config
