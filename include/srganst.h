@@ -345,6 +345,13 @@ int sst_bce_logits(const float* logits, float target, float* loss, float* dlogit
  * tables: x [planes,H,W] -> y [planes,oh,ow]; wy/iy [oh,Ty], wx/ix [ow,Tx]; round_grid: round to the 1/255 grid (no clamp) */
 int sst_bicubic(const float* x, float* y, const float* wy, const int* iy, const float* wx, const int* ix,
                 int64_t planes, int H, int W, int oh, int ow, int Ty, int Tx, int round_grid, void* stream);
+/* Training-batch gather from a device-resident uint8 crop store (device_data.py): src [N,H,W,3] HWC/RGB uint8, idx [B] int32
+ * crop indices (device; repeats allowed; an index outside [0, N) yields NaN); lut [256] = float(u) / 255 (host-made);
+ * gt [B,3,H,W] = lut[src[idx[b],y,x,c]] (may be null); lr [B,3,oh,ow] = the sst_bicubic of gt with round_grid, same tap tables
+ * wy/iy [oh,Ty], wx/ix [ow,Tx] and same arithmetic (may be null).  One launch; no allocation, no sync (capturable). */
+int sst_gather_batch(const uint8_t* src, int64_t N, const int* idx, int B, int H, int W, const float* lut, float* gt, float* lr,
+                     const float* wy, const int* iy, const float* wx, const int* ix, int oh, int ow, int Ty, int Tx,
+                     void* stream);
 /* ---- best-buddy losses (loss.py:78-142 BestBuddyLoss, loss.py:145-228 GramLoss, loss.py:292-375
  * PatchwiseStructureTensorLoss; ksize 3, stride 3, pad 0, squared-L2 matching):
  * sst_bb_patches cuts an image [B,3,H,W] into 27-vectors (unfold order) + squared norms inside the candidate table

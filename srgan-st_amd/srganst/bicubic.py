@@ -52,21 +52,34 @@ class Bicubic(nn.Module):
         self.device = device
         self._cache = {}
 
+    def tables(self, h: int, w: int, scale: float, device):
+        """Tap tables of an [h, w] -> [int(h*scale), int(w*scale)] resampling on `device`, built once and cached:
+        (wy [oh,Ty] fp32, iy [oh,Ty] int64, wx [ow,Tx] fp32, ix [ow,Tx] int64)."""
+        device = torch.device(device)
+        key = (h, w, scale, device)
+        if key not in self._cache:
+            w0, i0 = _contribute(h, int(h * scale), scale)
+            w1, i1 = _contribute(w, int(w * scale), scale)
+            self._cache[key] = tuple(t.to(device) for t in (w0, i0, w1, i1))
+        return self._cache[key]
+
+    def tables_i32(self, h: int, w: int, scale: float, device):
+        """tables() with int32 indices, the form the HIP kernels read (sst_bicubic, sst_gather_batch)."""
+        device = torch.device(device)
+        w0, i0, w1, i1 = self.tables(h, w, scale, device)
+        k2 = (h, w, scale, device, "i32")
+        if k2 not in self._cache:
+            self._cache[k2] = (i0.to(torch.int32).contiguous(), i1.to(torch.int32).contiguous())
+        j0, j1 = self._cache[k2]
+        return w0, j0, w1, j1
+
     def forward(self, input: torch.Tensor, scale: float = 4):
         b, c, h, w = input.shape
         oh, ow = int(h * scale), int(w * scale)
-        key = (h, w, scale, input.device)
-        if key not in self._cache:
-            w0, i0 = _contribute(h, oh, scale)
-            w1, i1 = _contribute(w, ow, scale)
-            self._cache[key] = tuple(t.to(input.device) for t in (w0, i0, w1, i1))
-        w0, i0, w1, i1 = self._cache[key]
+        w0, i0, w1, i1 = self.tables(h, w, scale, input.device)
         if input.is_cuda:
             from . import _abi
-            k2 = key + ("i32",)
-            if k2 not in self._cache:
-                self._cache[k2] = (i0.to(torch.int32).contiguous(), i1.to(torch.int32).contiguous())
-            j0, j1 = self._cache[k2]
+            w0, j0, w1, j1 = self.tables_i32(h, w, scale, input.device)
             x = input.contiguous().to(torch.float32)
             out = torch.empty(b, c, oh, ow, device=input.device, dtype=torch.float32)
             _abi.check(_abi.lib().sst_bicubic(_abi.ptr(x), _abi.ptr(out), _abi.ptr(w0), _abi.ptr(j0), _abi.ptr(w1), _abi.ptr(j1), b * c,

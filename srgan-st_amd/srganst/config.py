@@ -53,6 +53,10 @@ class Config:
         self.DATA.UPSCALE_FACTOR = 4
         self.DATA.BATCH_SIZE = 16
         self.DATA.GT_IMAGE_SIZE = 96
+        # True: the train()/warmup() drivers decode the training set ONCE into device memory (uint8) and build every batch with one
+        # HIP launch (device_data.py: gather + LR synthesis, sst_gather_batch) instead of the host DataLoader; needs the whole HR
+        # set in device memory on every rank and crops of one size on the 1/255 grid.  KERNEL.LR_ON_DEVICE does not apply to it
+        self.DATA.ON_DEVICE = False
 
         self.MODEL = dotdict()
         self.MODEL.G_CONTINUE_FROM_WARMUP = False

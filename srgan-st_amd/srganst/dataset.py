@@ -13,12 +13,16 @@ from torch.utils.data import Dataset
 from .bicubic import Bicubic
 
 
-def read_image(path: str) -> Tensor:
-    """uint8 [3,H,W] RGB, like torchvision.io.read_image."""
+def read_image_hwc(path: str) -> np.ndarray:
+    """uint8 [H,W,3] RGB as PIL decodes it (read_image before its permute)."""
     from PIL import Image
     with Image.open(path) as im:
-        arr = np.asarray(im.convert("RGB"))
-    return torch.from_numpy(arr.copy()).permute(2, 0, 1).contiguous()
+        return np.asarray(im.convert("RGB"))
+
+
+def read_image(path: str) -> Tensor:
+    """uint8 [3,H,W] RGB, like torchvision.io.read_image."""
+    return torch.from_numpy(read_image_hwc(path).copy()).permute(2, 0, 1).contiguous()
 
 
 def absoluteFilePaths(directory):

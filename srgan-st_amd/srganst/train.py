@@ -9,6 +9,7 @@ import torch
 from torch.optim import lr_scheduler
 from torch.utils.data import DataLoader
 
+from . import device_data
 from . import dist as sdist
 from .bicubic import Bicubic
 from .config import Config
@@ -26,9 +27,13 @@ def train(config: Config, train_dataset=None, test_dataset=None, max_steps_per_e
     best_psnr = best_ssim = 0.0
     train_ds = train_dataset or TrainImageDataset(config.DATA.TRAIN_GT_IMAGES_DIR, config.DATA.UPSCALE_FACTOR)
     test_ds = test_dataset or TestImageDataset(config.DATA.TEST_GT_IMAGES_DIR, config.DATA.TEST_LR_IMAGES_DIR)
-    sampler = torch.utils.data.distributed.DistributedSampler(train_ds, world, rank, shuffle=True) if world > 1 else None
-    train_loader = DataLoader(train_ds, batch_size=config.DATA.BATCH_SIZE, shuffle=sampler is None, sampler=sampler,
-                              num_workers=1, pin_memory=True, drop_last=True, persistent_workers=True)
+    on_device = config.DATA.ON_DEVICE
+    if on_device:                                # HBM-resident set, one gather launch per batch (device_data.py)
+        train_loader, sampler = device_data.train_loader(config, train_dataset, world, rank)
+    else:
+        sampler = torch.utils.data.distributed.DistributedSampler(train_ds, world, rank, shuffle=True) if world > 1 else None
+        train_loader = DataLoader(train_ds, batch_size=config.DATA.BATCH_SIZE, shuffle=sampler is None, sampler=sampler,
+                                  num_workers=1, pin_memory=True, drop_last=True, persistent_workers=True)
     test_loader = DataLoader(test_ds, batch_size=1, shuffle=False, num_workers=0, drop_last=False)
     device_bicubic = Bicubic(config.DEVICE)
     start_workers(train_loader)                  # fork the loader workers with the collector frozen (see utils.start_workers)
@@ -57,16 +62,19 @@ def train(config: Config, train_dataset=None, test_dataset=None, max_steps_per_e
         for batch_num, (gt, lr) in enumerate(train_loader):
             if max_steps_per_epoch is not None and batch_num >= max_steps_per_epoch:
                 break
-            # host batch straight into the engine's static input buffers when they exist and fit (copy_ returns the buffer)
-            fits = engine.gt is not None and engine.gt.shape == gt.shape
-            gt = engine.gt.copy_(gt, non_blocking=True) if fits else gt.to(device=config.DEVICE, non_blocking=True)
-            if config.KERNEL.LR_ON_DEVICE:
-                lr = device_bicubic(gt, scale=1.0 / config.DATA.UPSCALE_FACTOR)
-            elif fits and engine.lr.shape == lr.shape:
-                lr = engine.lr.copy_(lr, non_blocking=True)
-            else:
-                lr = lr.to(device=config.DEVICE, non_blocking=True)
+            if not on_device:                        # (on device: the batch is made in the engine's input buffers once bound)
+                # host batch straight into the engine's static input buffers when they exist and fit (copy_ returns the buffer)
+                fits = engine.gt is not None and engine.gt.shape == gt.shape
+                gt = engine.gt.copy_(gt, non_blocking=True) if fits else gt.to(device=config.DEVICE, non_blocking=True)
+                if config.KERNEL.LR_ON_DEVICE:
+                    lr = device_bicubic(gt, scale=1.0 / config.DATA.UPSCALE_FACTOR)
+                elif fits and engine.lr.shape == lr.shape:
+                    lr = engine.lr.copy_(lr, non_blocking=True)
+                else:
+                    lr = lr.to(device=config.DEVICE, non_blocking=True)
             loss_values, d_now = engine.step(gt, lr)
+            if on_device:
+                train_loader.bind(engine.gt, engine.lr)
             d_loss = d_now if d_now is not None else d_loss
             if batch_num % config.LOG_TRAIN_PERIOD != 0 or rank != 0:
                 continue
