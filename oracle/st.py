@@ -7,7 +7,7 @@ Restates, batched and without ``vmap``:
   * compute_invS1xS2         reference utils.py:242-254
   * compute_eigenvalues      reference utils.py:257-266
   * compute_distance         reference utils.py:269-280
-  * StructureTensorLoss      reference loss.py:380-413 (sigma=.5, rho=2, normalize=True)
+  * StructureTensorLoss      reference loss.py:380-413 (any sigma, rho, normalize)
   * torchvision Grayscale    ITU-R 601 weights (0.2989, 0.587, 0.114) - torchvision is
                              absent from the image, restated from its documentation.
 All functions are dtype-generic (fp32 to mirror the reference, fp64 as "truth").
@@ -93,6 +93,22 @@ def distance(L: torch.Tensor, eps: float = 1e-12) -> torch.Tensor:
     L = torch.clamp(L, min=1)
     L = torch.log(L) ** 2
     return torch.sqrt(L.sum(dim=1) + eps)
+
+
+def pixel_distance(S1: torch.Tensor, S2: torch.Tensor, normalize_: bool = True) -> torch.Tensor:
+    """Per-pixel distance d [B,H,W] of two structure tensors [B,3,H,W]: the pointwise half of the loss."""
+    return distance(eigenvalues(inv_s1_x_s2(S1, S2, normalize_)))
+
+
+def st_intermediates(x: torch.Tensor, gt: torch.Tensor, sigma: float = 0.5, rho: float = 2.0,
+                     normalize_: bool = True) -> dict:
+    """The loss's intermediates, same arithmetic as st_loss: S1 / S2 [B,3,H,W] (Jxx, Jyy, Jxy of x / gt), M [B,4,H,W],
+    the eigenvalues L [B,2,H,W] (before the clamp at 1) and the per-pixel distance d [B,H,W]."""
+    S1 = structure_tensor(grayscale(x), sigma, rho)
+    S2 = structure_tensor(grayscale(gt), sigma, rho)
+    M = inv_s1_x_s2(S1, S2, normalize_)
+    L = eigenvalues(M)
+    return {"S1": S1, "S2": S2, "M": M, "L": L, "d": distance(L)}
 
 
 def st_loss(x: torch.Tensor, gt: torch.Tensor, sigma: float = 0.5, rho: float = 2.0,

@@ -180,11 +180,11 @@ __global__ __launch_bounds__(NT) void st_loss_fwd_kernel(const float* __restrict
     // eigenvalues                                                           utils.py:260-265
     const float ApB = A + Bm;
     const float disc = ApB * ApB - 4.f * (A * Bm - C * D);
-    const float discc = fmaxf(disc, eps);
+    const float discc = disc < eps ? eps : disc;           // torch.clamp: NaN stays NaN (a max would return eps)
     const float r = sqrtf(discc);
     const float l1 = 0.5f * (ApB - r), l2 = 0.5f * (ApB + r);
     // distance                                                              utils.py:275-280
-    const float L1 = fmaxf(l1, 1.f), L2 = fmaxf(l2, 1.f);
+    const float L1 = l1 < 1.f ? 1.f : l1, L2 = l2 < 1.f ? 1.f : l2;   // likewise: a NaN eigenvalue keeps d NaN
     const float g1 = logf(L1), g2 = logf(L2);
     const float d = sqrtf(g1 * g1 + g2 * g2 + eps);
     lsum += d;

@@ -58,6 +58,65 @@ def test_st_loss_and_grad(golden, case):
     assert rel_err(g64, g[case + "_grad64"]) < 1e-5
 
 
+ST_PARAM_CASES = ["s10r25", "s04r19", "s05r20_raw", "s10r25_raw", "s05r20_eq", "s10r25_eq", "s05r20_nan"]
+
+
+def _st_params_case(g, case):
+    p = f"st/{case}/"
+    sigma, rho, norm, scale = (float(v) for v in g[p + "params"])
+    gt = T(g[p + "gt_u8"]).float() * scale
+    x = T(g[p + "x_u8"]).float() * scale if p + "x_u8" in g.files else gt.clone()
+    if p + "nan_at" in g.files:
+        x[tuple(int(i) for i in g[p + "nan_at"])] = float("nan")
+    return x, gt, sigma, rho, bool(norm)
+
+
+@pytest.mark.parametrize("case", ST_PARAM_CASES)
+def test_st_loss_and_grad_params(golden, case):
+    """StructureTensorLoss(sigma, rho, normalize) off the defaults (tests/golden/make_golden_st_params.py): the (4, 10) radius pair,
+    other taps in the (2, 8) pair, normalize=False, x == gt and a NaN in x - same checks as test_st_loss_and_grad."""
+    g = golden("st_params")
+    p = f"st/{case}/"
+    x, gt, sigma, rho, norm = _st_params_case(g, case)
+    loss, gx = ost.st_loss_and_grad(x, gt, sigma, rho, norm)
+    l64, g64 = ost.st_loss_and_grad(x.double(), gt.double(), sigma, rho, norm)
+    ref, ref64 = g[p + "loss"].item(), g[p + "loss64"].item()
+    fin = np.unpackbits(g[p + "grad_finite"])[:gx.numel()].reshape(gx.shape).astype(bool)
+    assert torch.equal(torch.isfinite(gx), T(fin)), "non-finite gradient pattern differs from the reference's"
+    if case.endswith("_nan"):
+        assert np.isnan(ref) and np.isnan(ref64) and torch.isnan(loss) and torch.isnan(l64)
+        assert torch.equal(torch.isfinite(g64), T(np.isfinite(g[p + "grad64"])))
+        assert 0 < int(fin.sum()) < fin.size
+        # the other image is untouched by the NaN
+        assert rel_err(gx[0], g[p + "grad64"][0]) <= max(3 * rel_err(gx[0], g64[0]), 1e-5)
+        assert rel_err(g64[0], g[p + "grad64"][0]) < 1e-5
+        return
+    assert abs(loss.item() - ref) <= 2e-5 * abs(ref)
+    assert rel_err(gx, g[p + "grad64"]) <= max(3 * g[p + "grad_ref_err"].item(), 1e-5)
+    assert abs(l64.item() - ref64) < 1e-6 * abs(ref64)
+    assert rel_err(g64, g[p + "grad64"]) < 1e-5
+
+
+@pytest.mark.parametrize("sigma, rho, norm", [(0.5, 2.0, True), (1.0, 2.5, False)])
+def test_st_intermediates_match_loss(sigma, rho, norm):
+    """oracle.st.st_intermediates (used by the GPU tests to prove their cases non-vacuous) is the loss's own arithmetic."""
+    gen = torch.Generator().manual_seed(31)
+    gt = torch.rand(2, 3, 24, 20, generator=gen, dtype=torch.float64) * (1 if norm else 255)
+    x = gt + 0.1 * torch.randn(gt.shape, generator=gen, dtype=torch.float64) * (1 if norm else 255)
+    it = ost.st_intermediates(x, gt, sigma, rho, norm)
+    assert it["S1"].shape == (2, 3, 24, 20) and it["M"].shape == (2, 4, 24, 20) and it["L"].shape == (2, 2, 24, 20)
+    assert torch.equal(it["d"].mean(dim=(1, 2)).mean(), ost.st_loss(x, gt, sigma, rho, norm))
+    assert torch.equal(it["d"], ost.pixel_distance(it["S1"], it["S2"], norm))
+    assert torch.equal(it["L"], ost.eigenvalues(it["M"]))
+    # L are the eigenvalues of the 2x2 matrix [[A, C], [D, B]] wherever the discriminant is above its clamp
+    A, Bm, C, D = it["M"].unbind(1)
+    disc = (A + Bm) ** 2 - 4 * (A * Bm - C * D)
+    ok = disc > 1e-6 * (A + Bm) ** 2
+    assert bool(ok.any())
+    lam = torch.linalg.eigvals(torch.stack((A, C, D, Bm), -1).reshape(*A.shape, 2, 2)).real.sort(-1).values
+    assert torch.allclose(it["L"].permute(0, 2, 3, 1)[ok], lam[ok], rtol=1e-9, atol=1e-9 * float(lam.abs().max()))
+
+
 def _state(g, prefix):
     return {k[len(prefix):]: T(g[k]).clone() for k in g.files if k.startswith(prefix) and "#" not in k}
 
