@@ -75,8 +75,10 @@ __global__ __launch_bounds__(NT) void bn_finalize_kernel(const float* __restrict
   }
   for (int t = threadIdx.x + KT * NT; t < ntiles; t += NT) {
     const float nt = cnt[t];
-    const float d = stats[(size_t)t * 2 * C + c] / nt - mean;
-    m2 += stats[(size_t)t * 2 * C + C + c] + nt * d * d;
+    if (nt > 0.f) {                                                 // an empty tile adds nothing (0 / 0 otherwise), as above
+      const float d = stats[(size_t)t * 2 * C + c] / nt - mean;
+      m2 += stats[(size_t)t * 2 * C + C + c] + nt * d * d;
+    }
   }
   m2 = block_sum<NT>(m2, red[0]);
   if (threadIdx.x == 0) {

@@ -46,18 +46,19 @@ __global__ __launch_bounds__(NT) void maxpool_relu_fwd_kernel(const float* __res
     const int oy = (int)(p % Ho);
     const int64_t b = p / Ho;
     const f32x4* src = reinterpret_cast<const f32x4*>(y) + (((b * H + 2 * oy) * W + 2 * ox) * (int64_t)c4n + c4);
-    f32x4 m = {0.f, 0.f, 0.f, 0.f};   // relu: max with 0
+    // relu = max with 0; explicit compares (fmaxf drops NaN): a NaN in the window comes through, as in F.max_pool2d(F.relu(x), 2)
+    f32x4 m = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const f32x4 v = src[((k >> 1) * W + (k & 1)) * (int64_t)c4n];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) m[j] = fmaxf(m[j], v[j]);
+      for (int j = 0; j < 4; ++j) m[j] = (v[j] > m[j] || v[j] != v[j]) ? v[j] : m[j];
     }
     reinterpret_cast<f32x4*>(out)[i] = m;
   }
 }
 
-// dy[b,y,x,c] = g[b,y/2,x/2,c] if (y,x) is the first arg-max of relu(y) in its window and y > 0, else 0
+// dy[b,y,x,c] = g[b,y/2,x/2,c] if (y,x) is the first arg-max of relu(y) in its window and y > 0 (or y is the window's NaN), else 0
 __global__ __launch_bounds__(NT) void maxpool_relu_bwd_kernel(const float* __restrict__ g, const float* __restrict__ y,
                                                               float* __restrict__ dy, int B, int H, int W, int C) {
   const int Ho = H >> 1, Wo = W >> 1, c4n = C >> 2;
@@ -77,15 +78,17 @@ __global__ __launch_bounds__(NT) void maxpool_relu_bwd_kernel(const float* __res
     f32x4 o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
+      // torch's rule for the same input: the first maximum wins a tie, a NaN takes the window (the last one if several) and
+      // ReLU's backward lets the gradient through to it (NaN <= 0 is false)
       int arg = 0;
-      float m = fmaxf(v[0][j], 0.f);
+      float m = v[0][j] < 0.f ? 0.f : v[0][j];
 #pragma unroll
       for (int k = 1; k < 4; ++k) {
-        const float r = fmaxf(v[k][j], 0.f);
-        if (r > m) { m = r; arg = k; }
+        const float r = v[k][j] < 0.f ? 0.f : v[k][j];
+        if (r > m || r != r) { m = r; arg = k; }
       }
 #pragma unroll
-      for (int k = 0; k < 4; ++k) o[k][j] = (k == arg && v[k][j] > 0.f) ? gv[j] : 0.f;
+      for (int k = 0; k < 4; ++k) o[k][j] = (k == arg && !(v[k][j] <= 0.f)) ? gv[j] : 0.f;
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) reinterpret_cast<f32x4*>(dy)[base + ((k >> 1) * W + (k & 1)) * (int64_t)c4n] = o[k];
