@@ -352,6 +352,14 @@ int sst_bicubic(const float* x, float* y, const float* wy, const int* iy, const 
 int sst_gather_batch(const uint8_t* src, int64_t N, const int* idx, int B, int H, int W, const float* lut, float* gt, float* lr,
                      const float* wy, const int* iy, const float* wx, const int* ix, int oh, int ow, int Ty, int Tx,
                      void* stream);
+/* Validation metrics of validate.image_metrics on the device (metrics.py), rounding for rounding: sr, hr fp32 NCHW [B,3,H,W] RGB;
+ * out fp64 [B,2] = (MSE of the Y channel on the 0..255 scale over all H*W pixels, mean of the SSIM map over its (H-10) x (W-10)
+ * valid region); sr_u8 / hr_u8: uint8 [B,H,W,3] BGR = tensor2img of each image (either may be null).  workspace:
+ * sst_image_metrics_workspace() doubles.  H, W >= 11.  A NaN anywhere in sr or hr makes that image's two outputs NaN; its uint8
+ * pixel is 0.  Two launches, partials summed in index order (bit-identical from run to run); no allocation, no sync. */
+int sst_image_metrics_workspace(int B, int H, int W, int64_t* partial_doubles);
+int sst_image_metrics(const float* sr, const float* hr, int B, int H, int W, double* out, uint8_t* sr_u8, uint8_t* hr_u8,
+                      double* workspace, void* stream);
 /* ---- best-buddy losses (loss.py:78-142 BestBuddyLoss, loss.py:145-228 GramLoss, loss.py:292-375
  * PatchwiseStructureTensorLoss; ksize 3, stride 3, pad 0, squared-L2 matching):
  * sst_bb_patches cuts an image [B,3,H,W] into 27-vectors (unfold order) + squared norms inside the candidate table

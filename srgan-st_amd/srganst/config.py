@@ -57,6 +57,11 @@ class Config:
         # HIP launch (device_data.py: gather + LR synthesis, sst_gather_batch) instead of the host DataLoader; needs the whole HR
         # set in device memory on every rank and crops of one size on the 1/255 grid.  KERNEL.LR_ON_DEVICE does not apply to it
         self.DATA.ON_DEVICE = False
+        # True: validation stays on the device - the test pairs are copied to it once (device_data.DeviceTestSet), PSNR / SSIM come
+        # from one HIP kernel per image (metrics.py: sst_image_metrics, the host path's numbers up to fp64 summation order) and all
+        # results cross to the host in one copy after the loop.  Images must be at least 11 px on each side.  (Beside
+        # DATA.ON_DEVICE, not under KERNEL: KERNEL holds the training engine's schedule switches, a set the tests pin exactly)
+        self.DATA.VALIDATE_ON_DEVICE = False
 
         self.MODEL = dotdict()
         self.MODEL.G_CONTINUE_FROM_WARMUP = False

@@ -17,7 +17,7 @@ from torch import Tensor
 
 from . import _abi
 from .bicubic import Bicubic
-from .dataset import TrainImageDataset, read_image_hwc
+from .dataset import TestImageDataset, TrainImageDataset, read_image_hwc
 
 _CHUNK_BYTES = 64 << 20          # host staging: decoded crops go to the device in pinned chunks of at most this size
 _MARGIN_BYTES = 2 << 30          # device memory left to the training step when the set is sized against mem_get_info
@@ -149,6 +149,57 @@ class DeviceImageSet:
 def _expect(t: Tensor, shape, name: str) -> None:
     if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise ValueError(f"DeviceImageSet.batch: {name} must be contiguous fp32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+
+class DeviceTestSet:
+    """The validation pairs on one device (config.DATA.VALIDATE_ON_DEVICE): decoded and copied ONCE, then iterated every epoch
+    like DataLoader(ds, batch_size=1, shuffle=False) - (hr [1,3,H,W], lr [1,3,h,w]) fp32, bit-identical to what that loader
+    yields.  Test images differ in size, so the store is a plain list of per-image tensors: no uniform-size store, no kernel."""
+
+    def __init__(self, pairs):
+        self.pairs = list(pairs)
+        if not self.pairs:
+            raise ValueError("DeviceTestSet: empty set")
+        self.device = self.pairs[0][0].device
+
+    def __len__(self) -> int:
+        return len(self.pairs)
+
+    def __iter__(self):
+        # A DataLoader draws its base seed from the default CPU generator every time it is iterated, also with num_workers=0.
+        # The same draw here: the training sampler's next shuffle, hence the training run, is then the same whichever way the
+        # validation ran (tests/test_metrics_gpu.py compares the checkpoints of both).
+        torch.empty((), dtype=torch.int64).random_()
+        return iter(self.pairs)
+
+    def __getitem__(self, i):
+        return self.pairs[i]
+
+    @classmethod
+    def from_dataset(cls, ds, device) -> "DeviceTestSet":
+        """From a dataset whose items are (hr [3,H,W], lr [3,h,w]) tensors, in the dataset's order.  Each image is sized against
+        the free device memory before it is copied (MemoryError, as for the training set)."""
+        device = torch.device(device)
+        pairs = []
+        for i in range(len(ds)):
+            hr, lr = ds[i]
+            for name, t in (("hr", hr), ("lr", lr)):
+                if not (isinstance(t, Tensor) and t.dim() == 3):
+                    raise ValueError(f"DeviceTestSet: item {i}: {name} must be a [C, H, W] tensor")
+            # the default collate of a batch of one: stack = unsqueeze(0), values untouched
+            hr, lr = hr.detach().unsqueeze(0).contiguous(), lr.detach().unsqueeze(0).contiguous()
+            try:
+                _check_fits(hr.numel() * hr.element_size() + lr.numel() * lr.element_size(), device)
+            except MemoryError as e:
+                raise MemoryError(f"DeviceTestSet: item {i} of {len(ds)} does not fit beside the training step ({e}); validate "
+                                  "through the host loader (DATA.VALIDATE_ON_DEVICE = False)") from e
+            pairs.append((hr.to(device), lr.to(device)))
+        return cls(pairs)
+
+    @classmethod
+    def from_dir(cls, gt_dir: str, lr_dir: str, device) -> "DeviceTestSet":
+        """TestImageDataset's file list and order."""
+        return cls.from_dataset(TestImageDataset(gt_dir, lr_dir), device)
 
 
 class DeviceLoader:

@@ -35,6 +35,8 @@ def train(config: Config, train_dataset=None, test_dataset=None, max_steps_per_e
         train_loader = DataLoader(train_ds, batch_size=config.DATA.BATCH_SIZE, shuffle=sampler is None, sampler=sampler,
                                   num_workers=1, pin_memory=True, drop_last=True, persistent_workers=True)
     test_loader = DataLoader(test_ds, batch_size=1, shuffle=False, num_workers=0, drop_last=False)
+    if config.DATA.VALIDATE_ON_DEVICE and rank == 0:       # the validation pairs on the device, once (only rank 0 validates)
+        test_loader = device_data.DeviceTestSet.from_dataset(test_ds, config.DEVICE)
     device_bicubic = Bicubic(config.DEVICE)
     start_workers(train_loader)                  # fork the loader workers with the collector frozen (see utils.start_workers)
     discriminator = Discriminator(config).to(config.DEVICE)     # train.py:52-53: D is constructed before G

@@ -1,6 +1,7 @@
 """Validation / test path.  Mirrors reference validate.py:18-137: batch-1 full-image generator forward
 under no_grad -> tensor2img -> /255 -> Y channel -> PSNR / SSIM (no border shave), mean +- CI.
-The generator forward is the HIP path in eval mode (BatchNorm folded to scale/shift from running stats)."""
+The generator forward is the HIP path in eval mode (BatchNorm folded to scale/shift from running stats).
+With config.DATA.VALIDATE_ON_DEVICE (or on_device=True) the metrics are taken on the device too (metrics.py)."""
 from __future__ import annotations
 
 import argparse
@@ -40,28 +41,62 @@ def _save_png(path, bgr_u8):
     Image.fromarray(np.ascontiguousarray(bgr_u8[..., ::-1])).save(path)
 
 
-def _validate(generator, val_loader, config, save_images=False, concat_with_gt=False, save_metrics=False):
+def _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt):
+    """The per-image loop of _validate with everything on the device: generator forward -> sst_image_metrics into row idx of one
+    [N,2] result buffer, ONE device-to-host copy after the loop.  Nothing syncs per image unless save_images is set (the uint8
+    images tensor2img would make then cross per image and are written by _save_png)."""
+    from .metrics import image_metrics_device, psnr_from_mse
+    results = torch.empty(len(val_loader), 2, dtype=torch.float64, device=config.DEVICE)
+    with torch.no_grad():
+        for idx, (hr_img, lr_img) in enumerate(val_loader):
+            lr_img = lr_img.to(config.DEVICE, non_blocking=True)
+            hr_img = hr_img.to(config.DEVICE, non_blocking=True)
+            output = generator(lr_img)
+            row = results[idx:idx + 1]
+            if save_images:
+                path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
+                os.makedirs(path, exist_ok=True)
+                _, o, g = image_metrics_device(output, hr_img, want_u8=True, out=row)
+                o = o[0].cpu().numpy()
+                _save_png(f"{path}/{idx}.png", np.concatenate([o, g[0].cpu().numpy()], axis=1) if concat_with_gt else o)
+            else:
+                image_metrics_device(output, hr_img, out=row)
+    host = results.cpu().tolist()
+    return [psnr_from_mse(mse) for mse, _ in host], [ssim for _, ssim in host]
+
+
+def _validate(generator, val_loader, config, save_images=False, concat_with_gt=False, save_metrics=False, on_device=None):
+    """on_device: None = config.DATA.VALIDATE_ON_DEVICE; True = metrics by the HIP kernel, one host copy per pass
+    (_metrics_on_device); False = the host loop below.  Same averages, same printed line, same _metrics.txt either way."""
+    if on_device is None:
+        on_device = bool(config.DATA.get("VALIDATE_ON_DEVICE", False))
     file = None
     if save_metrics:
         path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
         os.makedirs(path, exist_ok=True)
         file = open(os.path.join(path, "_metrics.txt"), mode="w")
     all_psnr, all_ssim = [], []
-    with torch.no_grad():
-        for idx, (hr_img, lr_img) in enumerate(val_loader):
-            lr_img = lr_img.to(config.DEVICE)
-            hr_img = hr_img.to(config.DEVICE)
-            output = generator(lr_img)
-            if save_images:
-                path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
-                os.makedirs(path, exist_ok=True)
-                o, g = tensor2img(output), tensor2img(hr_img)
-                _save_png(f"{path}/{idx}.png", np.concatenate([o, g], axis=1) if concat_with_gt else o)
-            psnr, ssim = image_metrics(output, hr_img)
-            all_psnr.append(psnr)
-            all_ssim.append(ssim)
-            if file:
+    if on_device:
+        all_psnr, all_ssim = _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt)
+        if file:
+            for idx, (psnr, ssim) in enumerate(zip(all_psnr, all_ssim)):
                 file.write(f"{idx}.png | PSNR: {psnr:.2f} | SSIM: {ssim:.4f}\n")
+    else:
+        with torch.no_grad():
+            for idx, (hr_img, lr_img) in enumerate(val_loader):
+                lr_img = lr_img.to(config.DEVICE)
+                hr_img = hr_img.to(config.DEVICE)
+                output = generator(lr_img)
+                if save_images:
+                    path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
+                    os.makedirs(path, exist_ok=True)
+                    o, g = tensor2img(output), tensor2img(hr_img)
+                    _save_png(f"{path}/{idx}.png", np.concatenate([o, g], axis=1) if concat_with_gt else o)
+                psnr, ssim = image_metrics(output, hr_img)
+                all_psnr.append(psnr)
+                all_ssim.append(ssim)
+                if file:
+                    file.write(f"{idx}.png | PSNR: {psnr:.2f} | SSIM: {ssim:.4f}\n")
     avg_psnr = sum(all_psnr) / len(all_psnr)
     avg_ssim = sum(all_ssim) / len(all_ssim)
     out = (f"[Test] | PSNR: {avg_psnr:.2f} ± {confidence_interval(all_psnr):.2f} | "
@@ -73,7 +108,7 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
     return avg_psnr, avg_ssim
 
 
-def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_gt: bool = False, dataset=None):
+def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_gt: bool = False, dataset=None, on_device=None):
     if not g_path:
         g_path = f"results/{config.EXP.NAME}/g_best.pth"
     ds = dataset if dataset is not None else TestImageDataset(config.DATA.TEST_GT_IMAGES_DIR, config.DATA.TEST_LR_IMAGES_DIR)
@@ -86,7 +121,8 @@ def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_
         generator = Generator(config).to(config.DEVICE)
         generator = load_state_dict(generator, torch.load(g_path, map_location=config.DEVICE, weights_only=True))
         generator.eval()
-    return _validate(generator, loader, config, save_images=save_images, concat_with_gt=concat_w_gt, save_metrics=True)
+    return _validate(generator, loader, config, save_images=save_images, concat_with_gt=concat_w_gt, save_metrics=True,
+                     on_device=on_device)
 
 
 if __name__ == "__main__":
@@ -95,6 +131,7 @@ if __name__ == "__main__":
     parser.add_argument("--g-path", type=str, default=None)
     parser.add_argument("--test-set", type=str, default=None)
     parser.add_argument("--no-images", action="store_true")
+    parser.add_argument("--on-device", action="store_true", help="PSNR / SSIM by the HIP kernel (DATA.VALIDATE_ON_DEVICE)")
     a = parser.parse_args()
     cfg = Config()
     if a.name:
@@ -103,4 +140,4 @@ if __name__ == "__main__":
         cfg.DATA.TEST_SET = a.test_set
         cfg.DATA.TEST_GT_IMAGES_DIR = f"/work3/{cfg.EXP.USER}/data/{a.test_set}/GTmod12"
         cfg.DATA.TEST_LR_IMAGES_DIR = f"/work3/{cfg.EXP.USER}/data/{a.test_set}/LRbicx4"
-    test(cfg, save_images=not a.no_images, g_path=a.g_path)
+    test(cfg, save_images=not a.no_images, g_path=a.g_path, on_device=True if a.on_device else None)
