@@ -352,6 +352,17 @@ int sst_bicubic(const float* x, float* y, const float* wy, const int* iy, const 
 int sst_gather_batch(const uint8_t* src, int64_t N, const int* idx, int B, int H, int W, const float* lut, float* gt, float* lr,
                      const float* wy, const int* iy, const float* wx, const int* ix, int oh, int ow, int Ty, int Tx,
                      void* stream);
+/* Training-batch gather from device-resident WHOLE images (device_data.py: DeviceImageArena): arena = packed HWC/RGB uint8 images
+ * (base and arena_bytes multiples of 16); table [N,3] int64 = (byte offset, H_img, W_img) per image; desc [B,4] int32 (device,
+ * 16-byte aligned) = (image, y0, x0, t) per sample.  With C = img[y0:y0+S, x0:x0+S] and t = 4*transpose + 2*vflip + 1*hflip, applied
+ * in that order: out[y][x] = C[sy][sx], y' = t&2 ? S-1-y : y, x' = t&1 ? S-1-x : x, (sy,sx) = t&4 ? (x',y') : (y',x').
+ * gt [B,3,S,S] = lut[out] (may be null); lr [B,3,oh,ow] = the sst_bicubic of gt with round_grid, tap tables of an S x S input (may be
+ * null).  S % 4 == 0.  span: an upper bound of the number of consecutive crop rows one band needs (its LR row's taps and, with gt,
+ * its own rows; sizes the LDS).  A descriptor out of range (image, window, t) yields NaN for that sample and reads nothing outside
+ * the arena.  One launch; no allocation, no sync (capturable). */
+int sst_gather_crops(const uint8_t* arena, int64_t arena_bytes, const int64_t* table, int64_t N, const int* desc, int B, int S,
+                     const float* lut, float* gt, float* lr, const float* wy, const int* iy, const float* wx, const int* ix,
+                     int oh, int ow, int Ty, int Tx, int span, void* stream);
 /* Validation metrics of validate.image_metrics on the device (metrics.py), rounding for rounding: sr, hr fp32 NCHW [B,3,H,W] RGB;
  * out fp64 [B,2] = (MSE of the Y channel on the 0..255 scale over all H*W pixels, mean of the SSIM map over its (H-10) x (W-10)
  * valid region); sr_u8 / hr_u8: uint8 [B,H,W,3] BGR = tensor2img of each image (either may be null).  workspace:

@@ -103,6 +103,147 @@ __global__ __launch_bounds__(GATHER_NT) void gather_batch_kernel(
   }
 }
 
+
+// ---- Batch gather from WHOLE images (device_data.py: DeviceImageArena / DeviceCropLoader): crop, dihedral transform, conversion
+// and LR synthesis in one launch.  arena: packed HWC/RGB uint8 images; table [N,3] int64 = (byte offset, H_img, W_img) per image;
+// desc [B,4] int32 = (image, y0, x0, t) per sample.  With C = img[y0:y0+S, x0:x0+S] and t = 4*transpose + 2*vflip + 1*hflip
+// (applied in that order):   out[y][x] = C[sy][sx],  y' = t&2 ? S-1-y : y,  x' = t&1 ? S-1-x : x,  (sy,sx) = t&4 ? (x',y') : (y',x').
+// gt = lut[out]; lr = the bicubic of OUT (not the transform of C's bicubic: fp32 sums are not order-symmetric), in the term order
+// of gather_batch_kernel above, so lr equals Bicubic("cuda")(gt) bit for bit.
+//
+// One workgroup per (sample, band of output rows), as above.  Call the source axis that y' walks the MAJOR axis (source rows
+// without transpose, source columns with it) and the one x' walks the MINOR axis.  The band's output rows and its LR row's taps
+// name a run of consecutive major lines [lo, hi] (the taps are consecutive, clamped at the borders; hi - lo < span, the caller's
+// bound, else NaN).  The workgroup stages exactly that run as raw bytes in source order:
+//   no transpose: hi-lo+1 source rows of 3S bytes, LDS pitch W3p;         byte(line, x', c) at (line-lo)*W3p + x'*3 + c
+//   transpose:    from each of the S source rows the 3*(hi-lo+1) bytes of columns lo..hi, coalesced along the source row, LDS
+//                 pitch P (P/4 odd: lanes that walk x' spread over the banks);   byte(line, x', c) at x'*P + (line-lo)*3 + c
+// so the transpose is only the choice of the two strides, and both flips are index maps of the consumers.  A crop row starts at
+// byte 3*x0 of an image row of 3*W_img bytes: no alignment at all.  Every staged dword is therefore funnel-shifted from the one or
+// two ALIGNED dwords that hold its bytes; an aligned dword that holds a byte of an image lies inside the arena (base and size are
+// multiples of 16), so nothing outside the arena is read.  The vertical pass leaves the column sums V indexed by x' (each sum is
+// one column's own, so its place in V changes no bit) and the horizontal pass reads V through the hflip map.
+constexpr int CROPS_NT = 256;
+
+// bytes a .. a+3 of the arena as one little-endian dword; only the first nvalid (1..4) of them have to be bytes of an image
+__device__ __forceinline__ uint32_t load_dword_unaligned(const uint8_t* __restrict__ arena, int64_t a, int nvalid) {
+  const int sh = (int)(a & 3);
+  const uint32_t* p = reinterpret_cast<const uint32_t*>(arena + (a - sh));
+  const uint32_t lo = p[0];
+  if (sh + nvalid <= 4) return lo >> (8 * sh);
+  return (uint32_t)((((uint64_t)p[1] << 32) | lo) >> (8 * sh));
+}
+
+__global__ __launch_bounds__(CROPS_NT) void gather_crops_kernel(
+    const uint8_t* __restrict__ arena, int64_t arena_bytes, const int64_t* __restrict__ table, int64_t N,
+    const int* __restrict__ desc, int S, int nband, const float* __restrict__ lut, float* __restrict__ gt, float* __restrict__ lr,
+    const float* __restrict__ wy, const int* __restrict__ iy, const float* __restrict__ wx, const int* __restrict__ ix, int oh,
+    int ow, int Ty, int Tx, int span, int P) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int b = blockIdx.y, band = blockIdx.x, tid = threadIdx.x;
+  const int S3 = S * 3;
+  const int W3p = (S3 + 15) & ~15;
+  float* s_lut = reinterpret_cast<float*>(smem);                         // [256]
+  float* s_v = s_lut + 256;                                              // [W3p] column sums of the vertical pass, indexed by x'
+  uint8_t* s_src = reinterpret_cast<uint8_t*>(s_v + W3p);                // the staged run of major lines (see above)
+  const int yb0 = (int)((int64_t)band * S / nband), yb1 = (int)((int64_t)(band + 1) * S / nband);
+
+  // ---- the sample: every field checked here again (the host has checked them); anything out of range yields NaN below
+  const int4 d = reinterpret_cast<const int4*>(desc)[b];
+  const int t = d.w;
+  const bool tr = t & 4, vf = t & 2, hf = t & 1;
+  bool ok = d.x >= 0 && d.x < N && t >= 0 && t < 8;
+  int64_t off = 0, Hi = 0, Wi = 0;
+  if (ok) {
+    off = table[(int64_t)d.x * 3], Hi = table[(int64_t)d.x * 3 + 1], Wi = table[(int64_t)d.x * 3 + 2];
+    ok = off >= 0 && off <= arena_bytes && Hi > 0 && Wi > 0 && Wi <= arena_bytes && Hi <= (arena_bytes - off) / (3 * Wi) &&
+         d.y >= 0 && d.z >= 0 && (int64_t)d.y + S <= Hi && (int64_t)d.z + S <= Wi;
+  }
+  // ---- the run [lo, hi] of major lines this band needs
+  int lo = S, hi = -1;
+  if (gt) {
+    const int m0 = vf ? S - 1 - yb0 : yb0, m1 = vf ? S - yb1 : yb1 - 1;
+    lo = min(m0, m1), hi = max(m0, m1);
+  }
+  if (lr)
+    for (int ty = 0; ty < Ty; ++ty) {
+      const int r = iy[band * Ty + ty];
+      ok = ok && r >= 0 && r < S;
+      const int m = vf ? S - 1 - r : r;
+      lo = min(lo, m), hi = max(hi, m);
+    }
+  const int nline = hi - lo + 1;
+  ok = ok && nline >= 1 && nline <= span;
+  if (!ok) {
+    const float q = __builtin_nanf("");
+    if (gt)
+      for (int i = tid; i < 3 * (yb1 - yb0) * S; i += CROPS_NT) {
+        const int x = i % S, r = i / S;
+        gt[(((int64_t)b * 3 + r / (yb1 - yb0)) * S + yb0 + r % (yb1 - yb0)) * S + x] = q;
+      }
+    if (lr)
+      for (int i = tid; i < 3 * ow; i += CROPS_NT) lr[(((int64_t)b * 3 + i / ow) * oh + band) * ow + i % ow] = q;
+    return;
+  }
+  s_lut[tid] = lut[tid];                                                 // CROPS_NT == 256
+
+  // ---- stage: consecutive lanes take consecutive dwords of a source row's segment
+  {
+    const int nrow = tr ? S : nline;                                     // source rows read
+    const int seg = tr ? nline * 3 : S3;                                 // bytes of each
+    const int pitch = tr ? P : W3p;
+    const int ndw = (seg + 3) >> 2;
+    const int64_t base = off + (((int64_t)d.y + (tr ? 0 : lo)) * Wi + d.z + (tr ? lo : 0)) * 3;
+    const int64_t rowb = Wi * 3;
+    uint32_t* dst = reinterpret_cast<uint32_t*>(s_src);
+    for (int i = tid; i < nrow * ndw; i += CROPS_NT) {
+      const int row = i / ndw, k = i - row * ndw;
+      dst[row * (pitch >> 2) + k] = load_dword_unaligned(arena, base + row * rowb + 4 * k, min(4, seg - 4 * k));
+    }
+  }
+  __syncthreads();
+  const int sL = tr ? 3 : W3p, sX = tr ? P : 3;                          // byte(line, x', c) = s_src[(line - lo) * sL + x' * sX + c]
+
+  // ---- gt: the band's output rows -> NCHW planes, 4 pixels of one channel per float4 store  (S % 4 == 0)
+  if (gt) {
+    const int rows = yb1 - yb0, S4 = S >> 2;
+    for (int i = tid; i < 3 * rows * S4; i += CROPS_NT) {
+      const int x4 = i % S4, r = (i / S4) % rows, c = i / (S4 * rows);
+      const int y = yb0 + r, x = x4 * 4;
+      const uint8_t* p = s_src + ((vf ? S - 1 - y : y) - lo) * sL + (hf ? S - 1 - x : x) * sX + c;
+      const int dx = hf ? -sX : sX;
+      const float4 v = make_float4(s_lut[p[0]], s_lut[p[dx]], s_lut[p[2 * dx]], s_lut[p[3 * dx]]);
+      *reinterpret_cast<float4*>(gt + (((int64_t)b * 3 + c) * S + y) * S + x) = v;
+    }
+  }
+  if (!lr) return;
+
+  // ---- lr, vertical pass: V[x'*3 + c] = sum_ty out[iy[ty]][c][x] * wy[ty]   (bicubic_kernel's inner loop, same order)
+  const float* wrow = wy + band * Ty;
+  const int* irow = iy + band * Ty;
+  for (int j = tid; j < S3; j += CROPS_NT) {
+    const int xs = j / 3, c = j - xs * 3;
+    const uint8_t* p = s_src + xs * sX + c;
+    float v = 0.f;
+    for (int ty = 0; ty < Ty; ++ty) {
+      const int r = irow[ty];
+      v += s_lut[p[((vf ? S - 1 - r : r) - lo) * sL]] * wrow[ty];
+    }
+    s_v[j] = v;
+  }
+  __syncthreads();
+  // ---- horizontal pass: acc = sum_tx V[x'(ix[tx])] * wx[tx], rounded to the 1/255 grid
+  for (int i = tid; i < 3 * ow; i += CROPS_NT) {
+    const int ox = i % ow, c = i / ow;
+    float acc = 0.f;
+    for (int tx = 0; tx < Tx; ++tx) {
+      const int x = min(max(ix[ox * Tx + tx], 0), S - 1);
+      acc += s_v[(hf ? S - 1 - x : x) * 3 + c] * wx[ox * Tx + tx];
+    }
+    lr[(((int64_t)b * 3 + c) * oh + band) * ow + ox] = rintf(255.f * acc) / 255.f;
+  }
+}
+
 }  // namespace
 
 SST_API int sst_gather_batch(const uint8_t* src, int64_t N, const int* idx, int B, int H, int W, const float* lut, float* gt,
@@ -122,5 +263,32 @@ SST_API int sst_gather_batch(const uint8_t* src, int64_t N, const int* idx, int 
   gather_batch_kernel<<<dim3(nband, B), GATHER_NT, (size_t)lds, sst_stream(stream)>>>(src, N, idx, H, W, nband, lut, gt, lr, wy, iy,
                                                                                       wx, ix, oh, ow, Ty, Tx, band_max, vec);
   SST_LAUNCH_CHECK("gather_batch_kernel");
+  return SST_OK;
+}
+
+SST_API int sst_gather_crops(const uint8_t* arena, int64_t arena_bytes, const int64_t* table, int64_t N, const int* desc, int B,
+                             int S, const float* lut, float* gt, float* lr, const float* wy, const int* iy, const float* wx,
+                             const int* ix, int oh, int ow, int Ty, int Tx, int span, void* stream) {
+  SST_REQUIRE(arena && table && desc && lut && arena_bytes > 0 && N > 0 && B > 0 && S > 0 && (gt || lr),
+              "sst_gather_crops: bad argument");
+  SST_REQUIRE((reinterpret_cast<uintptr_t>(arena) & 15) == 0 && arena_bytes % 16 == 0,
+              "sst_gather_crops: the arena and its size (%lld B) must be multiples of 16 bytes", (long long)arena_bytes);
+  SST_REQUIRE((reinterpret_cast<uintptr_t>(desc) & 15) == 0, "sst_gather_crops: desc must be 16-byte aligned");
+  SST_REQUIRE(B <= 65535, "sst_gather_crops: batch %d > 65535", B);
+  SST_REQUIRE(S % 4 == 0 && S <= 16384, "sst_gather_crops: crop side %d must be a multiple of 4 (and at most 16384)", S);
+  SST_REQUIRE(span > 0 && span <= S, "sst_gather_crops: span %d outside [1, %d]", span, S);
+  if (lr)
+    SST_REQUIRE(wy && iy && wx && ix && oh > 0 && ow > 0 && oh <= S && ow <= S && Ty > 0 && Tx > 0,
+                "sst_gather_crops: bad LR arguments");
+  const int nband = lr ? oh : (S + 3) / 4;                       // gt only: bands of about four rows
+  const int W3p = (3 * S + 15) & ~15;
+  int P = (3 * span + 3) & ~3;                                   // pitch of a transposed sample's LDS rows: whole dwords, an odd number
+  if (((P >> 2) & 1) == 0) P += 4;
+  const int64_t stage = (int64_t)span * W3p > (int64_t)S * P ? (int64_t)span * W3p : (int64_t)S * P;
+  const int64_t lds = 256 * 4 + (int64_t)W3p * 4 + stage;
+  SST_REQUIRE(lds <= 64 * 1024, "sst_gather_crops: %lld B of LDS needed (S %d, span %d) > 64 KiB", (long long)lds, S, span);
+  gather_crops_kernel<<<dim3(nband, B), CROPS_NT, (size_t)lds, sst_stream(stream)>>>(arena, arena_bytes, table, N, desc, S, nband, lut,
+                                                                                     gt, lr, wy, iy, wx, ix, oh, ow, Ty, Tx, span, P);
+  SST_LAUNCH_CHECK("gather_crops_kernel");
   return SST_OK;
 }

@@ -108,6 +108,7 @@ SIGNATURES = {
     "sst_bce_logits": (c_int, [P, c_float, P, P, P, c_float, c_int, P]),
     "sst_bicubic": (c_int, [P, P, P, P, P, P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_gather_batch": (c_int, [P, c_int64, P, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "sst_gather_crops": (c_int, [P, c_int64, P, c_int64, P, c_int, c_int, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_image_metrics_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
     "sst_image_metrics": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P]),
     "sst_feat_loss_fwd": (c_int, [P, P, P, P, c_float, c_int, P, P, P, c_int64, c_int, P]),

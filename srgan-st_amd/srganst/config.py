@@ -63,6 +63,19 @@ class Config:
         # DATA.ON_DEVICE, not under KERNEL: KERNEL holds the training engine's schedule switches, a set the tests pin exactly)
         self.DATA.VALIDATE_ON_DEVICE = False
 
+        # True: the drivers keep the WHOLE training images of TRAIN_ORIGINAL_IMAGES_DIR (any sizes, e.g. DIV2K as distributed) in
+        # device memory and one HIP launch per batch cuts, transforms, converts and downscales the samples (device_data.py:
+        # DeviceImageArena / DeviceCropLoader, sst_gather_crops).  No crops need to be cut beforehand: an epoch walks the tiles
+        # data-prep/prepare_dataset.py would have written (GT_IMAGE_SIZE squares every CROP_STEP pixels), shuffled.  Takes the place of
+        # ON_DEVICE when both are set
+        self.DATA.ON_DEVICE_WHOLE_IMAGES = False
+        self.DATA.TRAIN_ORIGINAL_IMAGES_DIR = f"/work3/{self.EXP.USER}/data/original"
+        self.DATA.CROP_STEP = 96
+        # with ON_DEVICE_WHOLE_IMAGES only: each sample's window at a uniform position of its image instead of on the tile grid /
+        # one of the eight flips and transpositions per sample; drawn per epoch from a private generator seeded by (SEED, epoch)
+        self.DATA.RANDOM_CROP = False
+        self.DATA.AUGMENT = False
+
         self.MODEL = dotdict()
         self.MODEL.G_CONTINUE_FROM_WARMUP = False
         self.MODEL.G_WARMUP_WEIGHTS = ""

@@ -5,6 +5,10 @@ training batch is then ONE HIP launch (csrc/data.hip: sst_gather_batch) that gat
 fp32 NCHW on the 1/255 grid and synthesises the x1/upscale bicubic LR in the same pass - the values TrainImageDataset + the
 default collate produce (gt bit for bit; lr bit for bit with Bicubic("cuda")(gt), within the host-versus-device bound of the CPU
 Bicubic).  No decode, no host-to-device copy and no sync per step.  The cost: the whole HR set in device memory on every rank.
+With config.DATA.ON_DEVICE_WHOLE_IMAGES the device holds the WHOLE training images instead (DeviceImageArena: no crops cut
+beforehand, images of any sizes) and the one launch per batch (sst_gather_crops) also cuts each sample's S x S window and applies one
+of the eight dihedral transforms to it: DeviceCropLoader walks the tile grid data-prep/prepare_dataset.py would have written, or,
+with DATA.RANDOM_CROP / DATA.AUGMENT, draws the window and the transform anew every epoch.
 """
 from __future__ import annotations
 
@@ -240,13 +244,323 @@ class DeviceLoader:
             yield self.dset.batch(idx[k * B:(k + 1) * B], self._gt, self._lr)
 
 
+def tile_grid(sizes, crop: int, step: int) -> np.ndarray:
+    """The tiles data-prep/prepare_dataset.py:34-47 writes for images of these (H, W), as int32 [M, 3] rows (image, y0, x0): for
+    each image, y0 in range(0, H - crop + 1, step), x0 in range(0, W - crop + 1, step), row-major.  An image smaller than
+    `crop` on either side contributes nothing."""
+    if crop <= 0 or step <= 0:
+        raise ValueError(f"tile_grid: crop {crop} and step {step} must be positive")
+    out = []
+    for n, (h, w) in enumerate(sizes):
+        ys, xs = np.arange(0, h - crop + 1, step), np.arange(0, w - crop + 1, step)     # empty when the image is too small
+        if len(ys) and len(xs):
+            g = np.empty((len(ys), len(xs), 3), np.int32)
+            g[..., 0], g[..., 1], g[..., 2] = n, ys[:, None], xs[None, :]
+            out.append(g.reshape(-1, 3))
+    return np.concatenate(out) if out else np.empty((0, 3), np.int32)
+
+
+def dihedral(c: Tensor, t: int) -> Tensor:
+    """Transform t = 4*transpose + 2*vflip + 1*hflip of c [..., H, W], applied in that order (all eight dihedral elements):
+    out[y][x] = c[sy][sx] with y' = t&2 ? S-1-y : y, x' = t&1 ? S-1-x : x and (sy, sx) = t&4 ? (x', y') : (y', x')."""
+    if t & 4:
+        c = c.transpose(-2, -1)
+    if t & 2:
+        c = c.flip(-2)
+    if t & 1:
+        c = c.flip(-1)
+    return c
+
+
+def crops_reference(images, desc, crop: int, upscale: int):
+    """What one sst_gather_crops launch computes, in plain torch on the host: for each row (image, y0, x0, t) of desc the window
+    images[image][y0:y0+crop, x0:x0+crop] (uint8 [H, W, 3]), transformed by dihedral(t), / 255 -> gt [B,3,crop,crop]; lr = the CPU
+    Bicubic of gt (the data loader's host code).  The restatement the tests compare the kernel against."""
+    desc = torch.as_tensor(np.asarray(desc)).reshape(-1, 4).tolist()
+    gts = []
+    for n, y0, x0, t in desc:
+        im = torch.as_tensor(np.asarray(images[n]))
+        if not (0 <= y0 and y0 + crop <= im.shape[0] and 0 <= x0 and x0 + crop <= im.shape[1] and 0 <= t < 8):
+            raise ValueError(f"crops_reference: descriptor {(n, y0, x0, t)} is outside image {n} ({im.shape[0]}x{im.shape[1]})")
+        c = im[y0:y0 + crop, x0:x0 + crop].permute(2, 0, 1)
+        gts.append(dihedral(c, t).contiguous().float() / 255.0)
+    gt = torch.stack(gts)
+    return gt, Bicubic("cpu")(gt, scale=1.0 / upscale)
+
+
+def _pad16(n: int) -> int:
+    return (n + 15) & ~15
+
+
+class DeviceImageArena:
+    """WHOLE training images of any sizes on one device: one packed uint8 arena (HWC/RGB, every image at a 16-byte aligned
+    offset) and a device table [N, 3] int64 of (byte offset, H, W).  len() is the number of tiles of the virtual tile list
+    (tile_grid: what prepare_dataset.py would have cut), so an epoch has the reference's number of steps and samplers work on
+    tile indices; crops() makes (gt, lr) batches from window descriptors with ONE sst_gather_crops launch."""
+
+    def __init__(self, arena: Tensor, table: np.ndarray, crop: int, step: int, upscale: int):
+        table = np.asarray(table, np.int64).reshape(-1, 3)
+        if arena.dtype != torch.uint8 or arena.dim() != 1 or arena.numel() % 16:
+            raise ValueError("DeviceImageArena: the arena must be a flat uint8 tensor of a multiple of 16 bytes")
+        if crop <= 0 or crop % 4:
+            raise ValueError(f"DeviceImageArena: the crop side must be a positive multiple of 4, got {crop}")
+        for off, h, w in table.tolist():
+            if off % 16 or off < 0 or h <= 0 or w <= 0 or off + h * w * 3 > arena.numel():
+                raise ValueError(f"DeviceImageArena: image (offset {off}, {h}x{w}) is not inside the arena at a 16-byte aligned offset")
+        self.arena = arena.contiguous()
+        self.device = arena.device
+        self.table_host = table
+        self.table = torch.from_numpy(table).to(self.device)
+        self.crop, self.step, self.upscale = int(crop), int(step), int(upscale)
+        self.tiles = tile_grid(table[:, 1:3].tolist(), self.crop, self.step)
+        if len(self.tiles) == 0:
+            raise ValueError(f"DeviceImageArena: none of the {len(table)} images holds a {crop}x{crop} tile")
+        self.lut = lut(self.device)
+        self.out = int(self.crop * (1.0 / self.upscale))
+        self._bicubic = Bicubic(str(self.device))
+        self._span = {}
+
+    def __len__(self) -> int:
+        return len(self.tiles)
+
+    @property
+    def n_images(self) -> int:
+        return len(self.table_host)
+
+    @staticmethod
+    def _layout(sizes):
+        offs, total = [], 0
+        for h, w in sizes:
+            offs.append(total)
+            total += _pad16(h * w * 3)
+        return offs, total
+
+    @classmethod
+    def from_arrays(cls, images, crop: int, step: int, upscale: int, device) -> "DeviceImageArena":
+        """From uint8 [H, W, 3] arrays (numpy or torch), in the given order."""
+        device = torch.device(device)
+        arrs = [np.ascontiguousarray(np.asarray(a)) for a in images]
+        for i, a in enumerate(arrs):
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"DeviceImageArena: image {i} must be uint8 [H, W, 3], got {a.dtype} {a.shape}")
+        sizes = [a.shape[:2] for a in arrs]
+        offs, total = cls._layout(sizes)
+        _check_fits(total, device)
+        host = np.zeros(max(total, 16), np.uint8)
+        for a, o in zip(arrs, offs):
+            host[o:o + a.size] = a.reshape(-1)
+        table = np.array([(o, h, w) for o, (h, w) in zip(offs, sizes)], np.int64).reshape(-1, 3)
+        return cls(torch.from_numpy(host).to(device), table, crop, step, upscale)
+
+    @classmethod
+    def from_dir(cls, image_dir: str, crop: int, step: int, upscale: int, device) -> "DeviceImageArena":
+        """Every image under `image_dir` (TrainImageDataset's file list and order), whole.  The sizes are read from the file
+        headers first, the arena is sized against the free device memory (MemoryError as for DeviceImageSet), then the images are
+        decoded by a thread pool, group by group through one pinned staging buffer, and copied to their places."""
+        from PIL import Image
+        device = torch.device(device)
+        files = TrainImageDataset(image_dir, upscale).image_file_names
+        if not files:
+            raise ValueError(f"DeviceImageArena: no images under {image_dir}")
+
+        def size(f):
+            with Image.open(f) as im:
+                return im.size[1], im.size[0]
+
+        with ThreadPoolExecutor(decode_threads()) as pool:
+            sizes = list(pool.map(size, files))
+            offs, total = cls._layout(sizes)
+            _check_fits(total, device)
+            arena = torch.zeros(total, dtype=torch.uint8, device=device)
+            room = max(_CHUNK_BYTES, max(_pad16(h * w * 3) for h, w in sizes))
+            staging = torch.zeros(room, dtype=torch.uint8, pin_memory=device.type == "cuda")
+            host = staging.numpy()
+
+            def decode(j, o0):
+                a = read_image_hwc(files[j])
+                if a.shape != (*sizes[j], 3):
+                    raise ValueError(f"DeviceImageArena: {files[j]} decodes to {a.shape}, its header said {sizes[j]}")
+                host[offs[j] - o0:offs[j] - o0 + a.size] = a.reshape(-1)
+
+            i0 = 0
+            while i0 < len(files):
+                i1 = i0 + 1
+                while i1 < len(files) and offs[i1] + _pad16(sizes[i1][0] * sizes[i1][1] * 3) - offs[i0] <= room:
+                    i1 += 1
+                list(pool.map(decode, range(i0, i1), [offs[i0]] * (i1 - i0)))       # re-raises the first failure in file order
+                end = offs[i1] if i1 < len(files) else total
+                arena[offs[i0]:end].copy_(staging[: end - offs[i0]])                # synchronous: the staging buffer is reused next
+                i0 = i1
+        table = np.array([(o, h, w) for o, (h, w) in zip(offs, sizes)], np.int64).reshape(-1, 3)
+        return cls(arena, table, crop, step, upscale)
+
+    def check_desc(self, desc) -> None:
+        """The host-side range check of window descriptors [.., 4] = (image, y0, x0, t): IndexError unless every image exists,
+        every window lies inside its image and every t is in 0..7."""
+        d = np.asarray(desc, np.int64).reshape(-1, 4)
+        if not len(d):
+            return
+        if d[:, 0].min() < 0 or d[:, 0].max() >= self.n_images:
+            raise IndexError(f"DeviceImageArena: a descriptor names an image outside [0, {self.n_images})")
+        h, w = self.table_host[d[:, 0], 1], self.table_host[d[:, 0], 2]
+        bad = (d[:, 1] < 0) | (d[:, 1] + self.crop > h) | (d[:, 2] < 0) | (d[:, 2] + self.crop > w)
+        if bad.any():
+            k = int(np.argmax(bad))
+            raise IndexError(f"DeviceImageArena: window (y0 {d[k, 1]}, x0 {d[k, 2]}, side {self.crop}) is outside image {d[k, 0]} "
+                             f"({h[k]}x{w[k]})")
+        if d[:, 3].min() < 0 or d[:, 3].max() > 7:
+            raise IndexError("DeviceImageArena: a descriptor's transform is outside 0..7")
+
+    def span(self, with_gt: bool, with_lr: bool) -> int:
+        """The most consecutive crop rows one workgroup of the kernel stages: over the bands (LR rows; groups of four rows without
+        lr), the extent of the band's tap rows and, with gt, of its own rows."""
+        key = (with_gt, with_lr)
+        if key not in self._span:
+            S = self.crop
+            if with_lr:
+                _, iy, _, _ = self._bicubic.tables(S, S, 1.0 / self.upscale, "cpu")
+                lo, hi = iy.min(1).values.numpy(), iy.max(1).values.numpy()
+                if with_gt:
+                    b = np.arange(self.out, dtype=np.int64)
+                    lo, hi = np.minimum(lo, b * S // self.out), np.maximum(hi, (b + 1) * S // self.out - 1)
+                self._span[key] = int((hi - lo).max()) + 1
+            else:
+                nband = (S + 3) // 4
+                self._span[key] = (S + nband - 1) // nband
+        return self._span[key]
+
+    def crops(self, desc: Tensor, gt_out: Tensor | None = None, lr_out: Tensor | None = None, with_gt: bool = True,
+              with_lr: bool = True):
+        """ONE sst_gather_crops launch on the current stream: gt [B,3,S,S] = the windows desc names, transformed, on the 1/255
+        grid; lr [B,3,S/up,S/up] = their bicubic.  desc: int32 [B,4] on the arena's device (checked on the host by DeviceCropLoader /
+        check_desc).  Writes into gt_out / lr_out when given; with_gt / with_lr = False skips that output (returned as None)."""
+        if desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != 4 or desc.device != self.device:
+            raise ValueError(f"DeviceImageArena.crops: desc must be int32 [B, 4] on {self.device}")
+        B, S, o = desc.shape[0], self.crop, self.out
+        gt = lr = None
+        if with_gt:
+            gt = gt_out if gt_out is not None else torch.empty(B, 3, S, S, device=self.device)
+            _expect(gt, (B, 3, S, S), "gt_out")
+        wy = iy = wx = ix = None
+        Ty = Tx = 0
+        if with_lr:
+            lr = lr_out if lr_out is not None else torch.empty(B, 3, o, o, device=self.device)
+            _expect(lr, (B, 3, o, o), "lr_out")
+            wy, iy, wx, ix = self._bicubic.tables_i32(S, S, 1.0 / self.upscale, self.device)
+            Ty, Tx = wy.shape[1], wx.shape[1]
+        _abi.check(_abi.lib().sst_gather_crops(_abi.ptr(self.arena), self.arena.numel(), _abi.ptr(self.table), self.n_images,
+                                               _abi.ptr(desc), B, S, _abi.ptr(self.lut), _abi.ptr(gt), _abi.ptr(lr), _abi.ptr(wy),
+                                               _abi.ptr(iy), _abi.ptr(wx), _abi.ptr(ix), o, o, Ty, Tx,
+                                               self.span(with_gt, with_lr), _abi.stream_ptr()), "sst_gather_crops")
+        return gt, lr
+
+
+class DeviceCropLoader:
+    """DeviceLoader's semantics (drop_last, bind(), plan() with the range check on the host, one non-blocking upload per epoch) over
+    a DeviceImageArena.  The sampler draws TILE indices; plan() turns its order into window descriptors (image, y0, x0, t):
+      * as they are, t = 0: the tile grid, i.e. the batches DeviceLoader makes from the pre-cut tiles;
+      * random_crop: each tile's (y0, x0) is replaced by a uniform position in the SAME image (images stay drawn in proportion to
+        their tile counts);  augment: t uniform in 0..7.
+    The draws come from a private torch.Generator seeded from (seed, epoch) and are made for ALL tiles of the set, then indexed by
+    the sampler's order: a tile's window and transform in an epoch depend on neither world size nor rank nor batch size, and the
+    default CPU generator (model init, shuffles) is never touched.  With both switches off nothing is drawn.  The epoch advances
+    with every __iter__; set_epoch() sets it."""
+
+    def __init__(self, arena: DeviceImageArena, batch_size: int, sampler=None, random_crop: bool = False, augment: bool = False,
+                 seed: int = 0):
+        if batch_size <= 0:
+            raise ValueError("DeviceCropLoader: batch_size must be positive")
+        self.dset = arena
+        self.batch_size = int(batch_size)
+        self.sampler = sampler if sampler is not None else torch.utils.data.RandomSampler(arena)
+        self.random_crop, self.augment, self.seed = bool(random_crop), bool(augment), int(seed)
+        self.epoch = 0
+        self._gt = self._lr = None
+
+    def __len__(self) -> int:
+        return len(self.sampler) // self.batch_size
+
+    def bind(self, gt: Tensor | None, lr: Tensor | None) -> None:
+        """Later batches land in these buffers (the engine's static inputs: the step then copies nothing)."""
+        self._gt, self._lr = gt, lr
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = int(epoch)
+
+    def draws(self, epoch: int) -> np.ndarray:
+        """The epoch's descriptor of EVERY tile of the set: int32 [len(arena), 4]."""
+        a = self.dset
+        d = np.zeros((len(a), 4), np.int32)
+        d[:, :3] = a.tiles
+        if self.random_crop or self.augment:
+            g = torch.Generator().manual_seed((self.seed * 1000003 + epoch) % (1 << 63))
+            if self.random_crop:
+                room = torch.from_numpy(a.table_host[a.tiles[:, 0], 1:3] - a.crop + 1)        # [M, 2] positions per axis, >= 1
+                d[:, 1:3] = (torch.randint(0, 1 << 62, room.shape, generator=g, dtype=torch.int64) % room).numpy()
+            if self.augment:
+                d[:, 3] = torch.randint(0, 8, (len(a),), generator=g, dtype=torch.int64).numpy()
+        return d
+
+    def plan(self) -> Tensor:
+        """The current epoch's descriptors on the host, in the sampler's order: int32 [len(self) * batch_size, 4]; tile indices and
+        windows checked against the set."""
+        order = np.fromiter(iter(self.sampler), dtype=np.int64)[: len(self) * self.batch_size]
+        n = len(self.dset)
+        if order.size and (int(order.min()) < 0 or int(order.max()) >= n):
+            raise IndexError(f"DeviceCropLoader: the sampler produced an index outside [0, {n})")
+        desc = self.draws(self.epoch)[order]
+        self.dset.check_desc(desc)
+        return torch.from_numpy(np.ascontiguousarray(desc))
+
+    def __iter__(self):
+        B = self.batch_size
+        host = self.plan()
+        self.epoch += 1
+        dev = self.dset.device
+        desc = host.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else host
+        for k in range(len(self)):
+            yield self.dset.crops(desc[k * B:(k + 1) * B], self._gt, self._lr)
+
+
+def check_switches(config) -> None:
+    """DATA.RANDOM_CROP and DATA.AUGMENT are made by the whole-image gather only."""
+    data = config.DATA
+    if (data.get("RANDOM_CROP", False) or data.get("AUGMENT", False)) and not data.get("ON_DEVICE_WHOLE_IMAGES", False):
+        raise ValueError("DATA.RANDOM_CROP / DATA.AUGMENT need DATA.ON_DEVICE_WHOLE_IMAGES = True: the random window and the flips / "
+                         "transposition are made by the whole-image gather (device_data.DeviceCropLoader), no other data path has them")
+
+
+def on_device(config) -> bool:
+    """The drivers' switch: True when the batches come from device memory (DATA.ON_DEVICE or DATA.ON_DEVICE_WHOLE_IMAGES)."""
+    check_switches(config)
+    return bool(config.DATA.ON_DEVICE or config.DATA.get("ON_DEVICE_WHOLE_IMAGES", False))
+
+
 def train_loader(config, train_dataset, world: int, rank: int):
-    """The drivers' ON_DEVICE data path: (DeviceLoader, sampler or None).  The set comes from `train_dataset` when one is given
-    (from_dataset), else from DATA.TRAIN_GT_IMAGES_DIR (from_dir); data-parallel ranks shard it with a DistributedSampler."""
+    """The drivers' device data path: (loader, sampler or None).  DATA.ON_DEVICE: a DeviceLoader over the pre-cut crops, from
+    `train_dataset` when one is given (from_dataset), else from DATA.TRAIN_GT_IMAGES_DIR (from_dir).  DATA.ON_DEVICE_WHOLE_IMAGES:
+    a DeviceCropLoader over the whole images of DATA.TRAIN_ORIGINAL_IMAGES_DIR (or over `train_dataset` when it is a
+    DeviceImageArena).  Data-parallel ranks shard the set with a DistributedSampler."""
+    check_switches(config)
     up = config.DATA.UPSCALE_FACTOR
+    DS = torch.utils.data.distributed.DistributedSampler
+    if config.DATA.get("ON_DEVICE_WHOLE_IMAGES", False):
+        if isinstance(train_dataset, DeviceImageArena):
+            arena = train_dataset
+        elif train_dataset is None:
+            arena = DeviceImageArena.from_dir(config.DATA.TRAIN_ORIGINAL_IMAGES_DIR, config.DATA.GT_IMAGE_SIZE, config.DATA.CROP_STEP,
+                                              up, config.DEVICE)
+        else:
+            raise ValueError("DATA.ON_DEVICE_WHOLE_IMAGES: the whole images come from DATA.TRAIN_ORIGINAL_IMAGES_DIR (or a "
+                             "DeviceImageArena passed as train_dataset), not from a dataset of crops")
+        sampler = DS(arena, world, rank, shuffle=True) if world > 1 else None
+        loader = DeviceCropLoader(arena, config.DATA.BATCH_SIZE, sampler, config.DATA.RANDOM_CROP, config.DATA.AUGMENT,
+                                  config.DATA.SEED)
+        loader.set_epoch(config.EXP.START_EPOCH)
+        return loader, sampler
     if train_dataset is not None:
         dset = DeviceImageSet.from_dataset(train_dataset, up, config.DEVICE)
     else:
         dset = DeviceImageSet.from_dir(config.DATA.TRAIN_GT_IMAGES_DIR, up, config.DEVICE)
-    sampler = torch.utils.data.distributed.DistributedSampler(dset, world, rank, shuffle=True) if world > 1 else None
+    sampler = DS(dset, world, rank, shuffle=True) if world > 1 else None
     return DeviceLoader(dset, config.DATA.BATCH_SIZE, sampler), sampler

@@ -41,7 +41,7 @@ def warmup(config: Config, train_dataset=None, test_dataset=None, max_steps_per_
     engine = WarmupEngine(config, generator)
     train_ds = train_dataset or TrainImageDataset(config.DATA.TRAIN_GT_IMAGES_DIR, config.DATA.UPSCALE_FACTOR)
     test_ds = test_dataset or TestImageDataset(config.DATA.TEST_GT_IMAGES_DIR, config.DATA.TEST_LR_IMAGES_DIR)
-    on_device = config.DATA.ON_DEVICE
+    on_device = device_data.on_device(config)    # DATA.ON_DEVICE or DATA.ON_DEVICE_WHOLE_IMAGES
     if on_device:                                # HBM-resident set, one gather launch per batch (device_data.py)
         train_loader, sampler = device_data.train_loader(config, train_dataset, world, rank)
     else:

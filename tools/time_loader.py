@@ -6,14 +6,23 @@ tensor / 3, D updated every step - bench.py's workload):
     host             train() with the host DataLoader (PIL decode + CPU Bicubic in one worker, pinned H2D copy)
     host+lr_dev      the same with KERNEL.LR_ON_DEVICE (the LR made on the GPU from the copied GT batch)
     on_device        train() with DATA.ON_DEVICE (device-resident uint8 set, one sst_gather_batch launch per batch)
+    whole_images     train() with DATA.ON_DEVICE_WHOLE_IMAGES (whole images of differing sizes in device memory, one
+                     sst_gather_crops launch per batch; the tile grid, no transform)
+    whole_images_aug the same with DATA.RANDOM_CROP and DATA.AUGMENT
 
 M synthetic crops on the 1/255 grid are written as PNGs into a temporary directory first; train() reads them from there
-(DATA.TRAIN_GT_IMAGES_DIR).  A step's time is taken over steps [S0, S0 + S) of one epoch, with a device sync at both ends only.
-The one-time decode + upload of the on_device set is timed separately.  Prints one JSON line.
+(DATA.TRAIN_GT_IMAGES_DIR).  The whole_images legs read a second synthetic set, DIV2K-shaped whole images of four different
+sizes with at least as many 96-px tiles (DATA.TRAIN_ORIGINAL_IMAGES_DIR).  A step's time is taken over steps [S0, S0 + S) of one epoch, with a device sync at both ends only.
+The one-time decode + upload of the on_device set and of the whole-image arena are timed separately.  --repeat R runs the
+chosen legs R times, round robin, and reports every repeat (the spread among the repeats of one leg is the yardstick for a
+difference between two legs).  Prints one JSON line.
 
-    python tools/time_loader.py [--images M] [--steps S] [--skip S0] [--cases device,host,host_lr,on_device]
+    python tools/time_loader.py [--images M] [--steps S] [--skip S0] [--repeat R]
+                                [--cases device,host,host_lr,on_device,whole_images,whole_images_aug]
     python tools/time_loader.py --gather-only [--iters N]     # N gather launches alone, for a kernel trace:
         rocprofv3 --kernel-trace --stats -d OUT -o gather -- python tools/time_loader.py --gather-only
+    python tools/time_loader.py --gather-only --crops grid|odd_x0|transposed [--iters N]
+        # the same trace with N sst_gather_crops launches beside N sst_gather_batch launches on the same tiles, in one process
 """
 import argparse
 import json
@@ -45,6 +54,25 @@ def write_crops(d, m, seed=0):
         u8 = torch.round(x.clamp(0, 1) * 255).to(torch.uint8).permute(0, 2, 3, 1).numpy()
         for j in range(n):
             Image.fromarray(np.ascontiguousarray(u8[j])).save(os.path.join(d, f"crop_{i0 + j:06d}.png"))
+
+
+WHOLE_SIZES = ((1356, 2040), (2040, 1356), (1404, 2039), (1117, 1853))      # H, W: DIV2K-like, two odd widths
+
+
+def write_whole_images(d, tiles, seed=1):
+    """Whole images of WHOLE_SIZES in turn (bicubic-upsampled coarse noise) until they hold at least `tiles` 96-px tiles."""
+    from PIL import Image
+    g = torch.Generator().manual_seed(seed)
+    have = i = 0
+    while have < tiles:
+        h, w = WHOLE_SIZES[i % len(WHOLE_SIZES)]
+        base = torch.rand(1, 3, h // 8, w // 8, generator=g)
+        x = torch.nn.functional.interpolate(base, size=(h, w), mode="bicubic", align_corners=False)
+        u8 = torch.round(x[0].clamp(0, 1) * 255).to(torch.uint8).permute(1, 2, 0).contiguous().numpy()
+        Image.fromarray(u8).save(os.path.join(d, f"whole_{i:04d}.png"), compress_level=1)
+        have += (h // HR) * (w // HR)
+        i += 1
+    return i
 
 
 class _OnePair(Dataset):
@@ -144,6 +172,39 @@ def gather_only(iters):
     print(json.dumps({"gather_launches": n, "batch": B, "hr": HR}))
 
 
+def gather_crops_only(iters, case):
+    """`iters` sst_gather_crops launches of one kind beside `iters` sst_gather_batch launches on the same tiles (cut from the same
+    images on the device), alternating: grid = the tile grid, t = 0; odd_x0 = the same windows moved to an odd x0, t = 0;
+    transposed = the grid with t = 5 (transpose + hflip)."""
+    from srganst.device_data import DeviceCropLoader, DeviceImageArena, DeviceImageSet
+    g = torch.Generator().manual_seed(0)
+    imgs = [torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8) for h, w in WHOLE_SIZES * 4]
+    arena = DeviceImageArena.from_arrays(imgs, HR, HR, UP, "cuda")
+    tiles = torch.from_numpy(arena.tiles)
+    pick = torch.randperm(len(tiles), generator=g)[:4096]
+    store = torch.stack([imgs[n][y:y + HR, x:x + HR] for n, y, x in tiles[pick].tolist()])
+    dset = DeviceImageSet(store.cuda(), UP)
+    desc = torch.zeros(len(pick), 4, dtype=torch.int32)
+    desc[:, :3] = tiles[pick]
+    if case == "odd_x0":
+        room = torch.from_numpy(arena.table_host[desc[:, 0].long().numpy(), 2]) - HR
+        desc[:, 2] = torch.minimum(desc[:, 2] | 1, ((room - 1) | 1).to(torch.int32))
+        assert bool((desc[:, 2] % 2 == 1).all())
+    elif case == "transposed":
+        desc[:, 3] = 5
+    elif case != "grid":
+        raise SystemExit(f"--crops {case}: grid, odd_x0 or transposed")
+    arena.check_desc(desc.numpy())
+    desc, idx = desc.cuda(), torch.arange(len(pick), dtype=torch.int32).cuda()
+    gt, lr = torch.empty(B, 3, HR, HR, device="cuda"), torch.empty(B, 3, HR // UP, HR // UP, device="cuda")
+    for n in range(iters):
+        k = (n * B) % (len(pick) - B)
+        dset.batch(idx[k:k + B], gt, lr)
+        arena.crops(desc[k:k + B], gt, lr)
+    torch.cuda.synchronize()
+    print(json.dumps({"gather_launches_each": iters, "crops_case": case, "batch": B, "hr": HR, "arena_bytes": arena.arena.numel()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=8192)
@@ -152,9 +213,11 @@ def main():
     ap.add_argument("--cases", default="device,host,host_lr,on_device")
     ap.add_argument("--gather-only", action="store_true")
     ap.add_argument("--iters", type=int, default=500)
+    ap.add_argument("--crops", default="", help="with --gather-only: grid, odd_x0 or transposed (sst_gather_crops beside sst_gather_batch)")
+    ap.add_argument("--repeat", type=int, default=1)
     a = ap.parse_args()
     if a.gather_only:
-        return gather_only(a.iters)
+        return gather_crops_only(a.iters, a.crops) if a.crops else gather_only(a.iters)
     if a.images < (a.skip + a.steps + 1) * B:
         raise SystemExit(f"--images {a.images} < {(a.skip + a.steps + 1) * B}: the timed window must fit into one epoch")
     cases = a.cases.split(",")
@@ -178,17 +241,40 @@ def main():
             out["decode_threads"] = decode_threads()
             out["store_bytes"] = s.store.numel()
             del s
+        whole_dir = os.path.join(tmp, "original")
+        if any(c.startswith("whole_images") for c in cases):
+            from srganst.device_data import DeviceImageArena, decode_threads
+            os.makedirs(whole_dir)
+            t0 = time.perf_counter()
+            out["whole_images"] = write_whole_images(whole_dir, a.images)
+            out["whole_png_write_s"] = round(time.perf_counter() - t0, 2)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            s = DeviceImageArena.from_dir(whole_dir, HR, HR, UP, "cuda")
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            out["whole_decode_upload_s"] = round(dt, 3)
+            out["whole_decode_threads"] = decode_threads()
+            out["whole_arena_bytes"] = s.arena.numel()
+            out["whole_tiles"] = len(s)
+            del s
+        whole = {"DATA.ON_DEVICE_WHOLE_IMAGES": True, "DATA.TRAIN_ORIGINAL_IMAGES_DIR": whole_dir, "DATA.CROP_STEP": HR}
         runs = {
             "device": lambda: time_device_tensors(gt_dir, a.skip, a.steps),
             "host": lambda: time_train(gt_dir, "tl_host", a.skip, a.steps),
             "host_lr": lambda: time_train(gt_dir, "tl_host_lr", a.skip, a.steps, **{"KERNEL.LR_ON_DEVICE": True}),
             "on_device": lambda: time_train(gt_dir, "tl_on_device", a.skip, a.steps, **{"DATA.ON_DEVICE": True}),
+            "whole_images": lambda: time_train(gt_dir, "tl_whole", a.skip, a.steps, **whole),
+            "whole_images_aug": lambda: time_train(gt_dir, "tl_whole_aug", a.skip, a.steps, **whole,
+                                                   **{"DATA.RANDOM_CROP": True, "DATA.AUGMENT": True}),
         }
-        for c in cases:
-            sec = runs[c]()
-            out[f"{c}_ms_per_step"] = round(sec * 1e3, 3)
-            out[f"{c}_img_s"] = round(B / sec, 1)
-            print(f"# {c}: {sec * 1e3:.3f} ms/step, {B / sec:.1f} img/s", file=sys.stderr, flush=True)
+        for rep in range(a.repeat):
+            for c in cases:
+                sec = runs[c]()
+                out[f"{c}_ms_per_step"] = round(sec * 1e3, 3)           # (the last repeat's)
+                out[f"{c}_img_s"] = round(B / sec, 1)
+                out.setdefault(f"{c}_ms_per_step_repeats", []).append(round(sec * 1e3, 3))
+                print(f"# {c} [{rep + 1}/{a.repeat}]: {sec * 1e3:.3f} ms/step, {B / sec:.1f} img/s", file=sys.stderr, flush=True)
         if "device" in cases and "on_device" in cases:
             out["on_device_vs_device_tensors"] = round(out["device_ms_per_step"] / out["on_device_ms_per_step"], 4)
     print(json.dumps(out))
