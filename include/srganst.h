@@ -37,6 +37,17 @@ int sst_st_loss_fwd(const float* sr, const float* gt, float* loss, float* gS, fl
 int sst_st_loss_bwd(const float* sr, const float* gS, float* dsr, const float* scale_dev,
                     float scale_host, int accumulate, int B, int H, int W, float sigma, float rho,
                     void* stream);
+/* ---- structure-tensor maps (analysis, no gradient): the fields the loss integrates, from the loss's own tile code -------
+ * x, gt: NCHW [B,3,H,W]; gt may be null when only maps of x are asked for.  Every output is optional (null = not computed):
+ *   Sx, Sgt   [B,3,H,W] (Jxx, Jyy, Jxy) of x / gt;   Fx, Fgt  [B,3,H,W] (t, c2, s2) with t = Jxx + Jyy,
+ *   c2 = (Jxx - Jyy) / (t + 1e-12), s2 = 2 Jxy / (t + 1e-12);   d  [B,H,W] the per-pixel distance (the loss's integrand);
+ *   tile_sums [B,tiles] fp32 sum of d over each 32x32 tile's valid pixels (tiles row-major; sst_st_maps_workspace() floats in all) -
+ *   the caller sums them per image (fp64, index order) for a per-image distance.  Sgt, Fgt, d and tile_sums need gt.
+ * Axis convention of the reference (utils.py:219): "x" is the HEIGHT axis - Jxx is the energy of row-to-row variation (c2 = +1).
+ * One launch; no atomics, no counter, no allocation, no sync; bit-identical from call to call.                          */
+int sst_st_maps_workspace(int B, int H, int W, int64_t* tile_floats);
+int sst_st_maps(const float* x, const float* gt, float* Sx, float* Sgt, float* Fx, float* Fgt, float* d, float* tile_sums,
+                int B, int H, int W, float sigma, float rho, int normalize, void* stream);
 /* The same two launches with the pixel criterion of the step riding along (reference train.py:129-140 evaluates "Pixel" =
  * MSE / L1, config.py:88-90, and "ST" on the same sr / gt): pix_mode 0 = MSE, 1 = L1.
  * fwd: also pix_loss[0] = mean over all B*3*H*W elements (pix_partials: as many floats as `partials`).

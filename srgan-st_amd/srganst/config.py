@@ -62,6 +62,11 @@ class Config:
         # results cross to the host in one copy after the loop.  Images must be at least 11 px on each side.  (Beside
         # DATA.ON_DEVICE, not under KERNEL: KERNEL holds the training engine's schedule switches, a set the tests pin exactly)
         self.DATA.VALIDATE_ON_DEVICE = False
+        # True: validation also reports the structure-tensor distance of every test image (st.st_distance: the per-image mean of the
+        # distance the ``ST`` criterion integrates, with that criterion's sigma / rho / normalize when one is configured, else its
+        # defaults): _metrics.txt and the printed line gain an ``ST:`` column, the drivers log Test/ST.  Checkpoint selection is
+        # unchanged.  Works with either validation path; on the device path the values cross to the host once, after the loop
+        self.DATA.VALIDATE_ST = False
 
         # True: the drivers keep the WHOLE training images of TRAIN_ORIGINAL_IMAGES_DIR (any sizes, e.g. DIV2K as distributed) in
         # device memory and one HIP launch per batch cuts, transforms, converts and downscales the samples (device_data.py:

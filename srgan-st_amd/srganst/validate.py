@@ -1,7 +1,9 @@
 """Validation / test path.  Mirrors reference validate.py:18-137: batch-1 full-image generator forward
 under no_grad -> tensor2img -> /255 -> Y channel -> PSNR / SSIM (no border shave), mean +- CI.
 The generator forward is the HIP path in eval mode (BatchNorm folded to scale/shift from running stats).
-With config.DATA.VALIDATE_ON_DEVICE (or on_device=True) the metrics are taken on the device too (metrics.py)."""
+With config.DATA.VALIDATE_ON_DEVICE (or on_device=True) the metrics are taken on the device too (metrics.py).
+With config.DATA.VALIDATE_ST (or with_st=True, or --st) every image also gets its structure-tensor distance (st.st_distance): the
+quantity the ``ST`` criterion optimises, reported next to PSNR and SSIM."""
 from __future__ import annotations
 
 import argparse
@@ -16,6 +18,7 @@ from .bicubic import Bicubic, NearestNeighbourUpscale
 from .config import Config
 from .dataset import TestImageDataset
 from .model import Generator
+from .st import st_distance
 from .utils import PSNR, SSIM, bgr2ycbcr, load_state_dict, tensor2img
 
 
@@ -41,12 +44,22 @@ def _save_png(path, bgr_u8):
     Image.fromarray(np.ascontiguousarray(bgr_u8[..., ::-1])).save(path)
 
 
-def _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt):
+def _st_params(config):
+    """(sigma, rho, normalize) of the configured ``ST`` criterion, else StructureTensorLoss's defaults."""
+    crit = config.MODEL.G_LOSS.CRITERIONS.get("ST")
+    if crit is None:
+        return 0.5, 2.0, True
+    return float(crit.sigma), float(crit.rho), bool(crit.normalize)
+
+
+def _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params=None):
     """The per-image loop of _validate with everything on the device: generator forward -> sst_image_metrics into row idx of one
     [N,2] result buffer, ONE device-to-host copy after the loop.  Nothing syncs per image unless save_images is set (the uint8
-    images tensor2img would make then cross per image and are written by _save_png)."""
+    images tensor2img would make then cross per image and are written by _save_png).  st_params: also st_distance(output, hr) per
+    image into an [N] buffer that crosses once as well -> third list."""
     from .metrics import image_metrics_device, psnr_from_mse
     results = torch.empty(len(val_loader), 2, dtype=torch.float64, device=config.DEVICE)
+    st_results = torch.empty(len(val_loader), dtype=torch.float64, device=config.DEVICE) if st_params else None
     with torch.no_grad():
         for idx, (hr_img, lr_img) in enumerate(val_loader):
             lr_img = lr_img.to(config.DEVICE, non_blocking=True)
@@ -61,26 +74,36 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
                 _save_png(f"{path}/{idx}.png", np.concatenate([o, g[0].cpu().numpy()], axis=1) if concat_with_gt else o)
             else:
                 image_metrics_device(output, hr_img, out=row)
+            if st_params:
+                st_results[idx:idx + 1].copy_(st_distance(output, hr_img, *st_params))
     host = results.cpu().tolist()
-    return [psnr_from_mse(mse) for mse, _ in host], [ssim for _, ssim in host]
+    return [psnr_from_mse(mse) for mse, _ in host], [ssim for _, ssim in host], st_results.cpu().tolist() if st_params else []
 
 
-def _validate(generator, val_loader, config, save_images=False, concat_with_gt=False, save_metrics=False, on_device=None):
+def _validate(generator, val_loader, config, save_images=False, concat_with_gt=False, save_metrics=False, on_device=None,
+              with_st=None):
     """on_device: None = config.DATA.VALIDATE_ON_DEVICE; True = metrics by the HIP kernel, one host copy per pass
-    (_metrics_on_device); False = the host loop below.  Same averages, same printed line, same _metrics.txt either way."""
+    (_metrics_on_device); False = the host loop below.  Same averages, same printed line, same _metrics.txt either way.
+    with_st: None = config.DATA.VALIDATE_ST; True = every image also gets st.st_distance(output, hr) with the configured ``ST``
+    criterion's (sigma, rho, normalize), _metrics.txt and the printed line gain an ``ST:`` column and the return value becomes
+    (psnr, ssim, st); False = everything as without the option."""
     if on_device is None:
         on_device = bool(config.DATA.get("VALIDATE_ON_DEVICE", False))
+    if with_st is None:
+        with_st = bool(config.DATA.get("VALIDATE_ST", False))
+    st_params = _st_params(config) if with_st else None
     file = None
     if save_metrics:
         path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
         os.makedirs(path, exist_ok=True)
         file = open(os.path.join(path, "_metrics.txt"), mode="w")
-    all_psnr, all_ssim = [], []
+    all_psnr, all_ssim, all_st = [], [], []
     if on_device:
-        all_psnr, all_ssim = _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt)
+        all_psnr, all_ssim, all_st = _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params)
         if file:
             for idx, (psnr, ssim) in enumerate(zip(all_psnr, all_ssim)):
-                file.write(f"{idx}.png | PSNR: {psnr:.2f} | SSIM: {ssim:.4f}\n")
+                st_col = f" | ST: {all_st[idx]:.4f}" if with_st else ""
+                file.write(f"{idx}.png | PSNR: {psnr:.2f} | SSIM: {ssim:.4f}{st_col}\n")
     else:
         with torch.no_grad():
             for idx, (hr_img, lr_img) in enumerate(val_loader):
@@ -95,20 +118,29 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
                 psnr, ssim = image_metrics(output, hr_img)
                 all_psnr.append(psnr)
                 all_ssim.append(ssim)
+                st_col = ""
+                if with_st:                                   # the host-metric path syncs per image anyway
+                    all_st.append(st_distance(output, hr_img, *st_params).item())
+                    st_col = f" | ST: {all_st[-1]:.4f}"
                 if file:
-                    file.write(f"{idx}.png | PSNR: {psnr:.2f} | SSIM: {ssim:.4f}\n")
+                    file.write(f"{idx}.png | PSNR: {psnr:.2f} | SSIM: {ssim:.4f}{st_col}\n")
     avg_psnr = sum(all_psnr) / len(all_psnr)
     avg_ssim = sum(all_ssim) / len(all_ssim)
     out = (f"[Test] | PSNR: {avg_psnr:.2f} ± {confidence_interval(all_psnr):.2f} | "
-           f"SSIM: {avg_ssim:.4f} ± {confidence_interval(all_ssim):.4f} | \n")
+           f"SSIM: {avg_ssim:.4f} ± {confidence_interval(all_ssim):.4f} | ")
+    if with_st:
+        avg_st = sum(all_st) / len(all_st)
+        out += f"ST: {avg_st:.4f} ± {confidence_interval(all_st):.4f} | "
+    out += "\n"
     print(out)
     if file:
         file.write("\n" + out + "\n")
         file.close()
-    return avg_psnr, avg_ssim
+    return (avg_psnr, avg_ssim, avg_st) if with_st else (avg_psnr, avg_ssim)
 
 
-def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_gt: bool = False, dataset=None, on_device=None):
+def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_gt: bool = False, dataset=None, on_device=None,
+         with_st=None):
     if not g_path:
         g_path = f"results/{config.EXP.NAME}/g_best.pth"
     ds = dataset if dataset is not None else TestImageDataset(config.DATA.TEST_GT_IMAGES_DIR, config.DATA.TEST_LR_IMAGES_DIR)
@@ -122,7 +154,7 @@ def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_
         generator = load_state_dict(generator, torch.load(g_path, map_location=config.DEVICE, weights_only=True))
         generator.eval()
     return _validate(generator, loader, config, save_images=save_images, concat_with_gt=concat_w_gt, save_metrics=True,
-                     on_device=on_device)
+                     on_device=on_device, with_st=with_st)
 
 
 if __name__ == "__main__":
@@ -132,6 +164,7 @@ if __name__ == "__main__":
     parser.add_argument("--test-set", type=str, default=None)
     parser.add_argument("--no-images", action="store_true")
     parser.add_argument("--on-device", action="store_true", help="PSNR / SSIM by the HIP kernel (DATA.VALIDATE_ON_DEVICE)")
+    parser.add_argument("--st", action="store_true", help="also the structure-tensor distance per image (DATA.VALIDATE_ST)")
     a = parser.parse_args()
     cfg = Config()
     if a.name:
@@ -140,4 +173,5 @@ if __name__ == "__main__":
         cfg.DATA.TEST_SET = a.test_set
         cfg.DATA.TEST_GT_IMAGES_DIR = f"/work3/{cfg.EXP.USER}/data/{a.test_set}/GTmod12"
         cfg.DATA.TEST_LR_IMAGES_DIR = f"/work3/{cfg.EXP.USER}/data/{a.test_set}/LRbicx4"
-    test(cfg, save_images=not a.no_images, g_path=a.g_path, on_device=True if a.on_device else None)
+    test(cfg, save_images=not a.no_images, g_path=a.g_path, on_device=True if a.on_device else None,
+         with_st=True if a.st else None)

@@ -88,11 +88,13 @@ def warmup(config: Config, train_dataset=None, test_dataset=None, max_steps_per_
             print(f"[Epoch {epoch+1}/{config.EXP.N_EPOCHS}] [Batch {batch_num}/{len(train_loader)}] [G losses: {vals}]")
         generator.eval()
         if rank == 0:
-            psnr, ssim = _validate(generator, test_loader, config)
+            psnr, ssim, *st = _validate(generator, test_loader, config)      # (psnr, ssim, st) with DATA.VALIDATE_ST
             if epoch % config.LOG_VALIDATION_PERIOD == 0:
                 print(f"[Test: {epoch+1}/{config.EXP.N_EPOCHS}] [PSNR: {psnr}] [SSIM: {ssim}]")
             writer.add_scalar("Test/PSNR", psnr, epoch + 1)
             writer.add_scalar("Test/SSIM", ssim, epoch + 1)
+            if st:
+                writer.add_scalar("Test/ST", st[0], epoch + 1)
             results_dir = f"results/{config.EXP.NAME}"
             os.makedirs(results_dir, exist_ok=True)
             torch.save(generator.state_dict(), results_dir + "/g_last.pth")
