@@ -82,8 +82,9 @@ int sst_conv_mtiles(int B, int Ho, int Wo);
 /* first dimension of stats / stats_cnt / epi_partial written by the NHWC-store conv of this shape (input H x W):
  * one tile per band when the band kernel takes the shape, else sst_conv_mtiles of the output size */
 int sst_conv_stat_tiles(int B, int H, int W, int Cin, int Cout, int ksize, int stride);
-/* kernel the conv / weight-gradient entries dispatch to for a shape (rocprofv3 spelling, no argument list): labels for
- * bench.py's roofline rows, to be matched against profiles/ */
+/* kernel the conv / weight-gradient entries dispatch to for a shape when called plain - no bias, input affine, activation,
+ * statistics or residual - in rocprofv3 spelling without the argument list: labels for bench.py's roofline rows, to be matched
+ * against profiles/.  Both report the launcher's own selection (conv_fwd_select / wgrad_plan), dev switches included. */
 const char* sst_conv_kernel_name(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int out_mode, int fused_in);
 const char* sst_conv_wgrad_kernel_name(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int njobs);
 long sst_debug_big_tile_launches(void);   /* test hook: launches of the 64x64-tile conv kernel so far */
@@ -209,8 +210,9 @@ int sst_conv_dgrad_fused(const float* g, const float* y2, const float* cA, const
                          int ksize, void* stream);
 /* dW[Cout][Cin][k][k] (+)= sum_pixels X'(shifted) * dY ; slab = sst_conv_wgrad_chunks*k*k*Cout*Cin floats */
 int sst_conv_wgrad_chunks(int B, int Ho, int Wo, int Cin, int Cout, int ksize);   /* general (per-tap) kernel only */
-/* chunk count sst_conv_wgrad (njobs = 1) / sst_conv_wgrad_grouped (njobs layers) actually use; H, W = input size.
- * 3x3 stride-1 layers with Cin, Cout multiples of 64 run the all-taps band kernel (csrc/conv_wgrad.hip). */
+/* chunk count to size the slab of sst_conv_wgrad (njobs = 1) / sst_conv_wgrad_grouped (njobs layers) with; H, W = input size.
+ * It is the launcher's own plan (wgrad_plan, csrc/conv_wgrad.hip): the chunks its kernel writes, or - where input affine, activation
+ * or a dev switch decide between kernels of different chunk counts - the largest of them. */
 int sst_conv_wgrad_chunks2(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int njobs);
 int sst_conv_wgrad(const float* x, const float* dy, float* slab, float* dw, const float* in_scale,
                    const float* in_shift, const float* in_slope, float in_slope_const, int in_act,
@@ -224,7 +226,7 @@ int sst_conv_wgrad_grp(const float* x, const float* dy, float* slab, float* dw, 
                    int B, int H, int W, int Cin, int Cout, int stride, int ksize, int accumulate,
                        int grp_images, void* stream);
 /* Slab reduces of a whole backward pass in one launch: sst_conv_wgrad_grp with accumulate bit 2 (value 4) leaves its slab un-reduced
- * where sst_conv_wgrad_pending_reduce(...) > 0 (= the slab's chunk count; 0: that launch writes dW itself and ignores the bit); the
+ * where sst_conv_wgrad_pending_reduce(...) > 0 (= the chunks the launcher's own plan writes for these arguments; 0: that launch writes dW itself and ignores the bit); the
  * caller then hands sst_wgrad_reduce_multi a HOST array of up to 24 jobs {const float* slab; float* dw; int nchunk, kk, Cout, Cin,
  * accumulate, reserved;} (40 bytes each).  Same arithmetic per job as the per-layer reduce (bit-identical dW). */
 int sst_conv_wgrad_pending_reduce(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int has_in_scale, int in_act);
@@ -258,7 +260,8 @@ int sst_conv_s2_dgrad(const float* dy, const float* wp, float* dx, int B, int H,
 /* one BatchNorm-backward stage around the stride-2 data-gradient (contract of sst_conv_dgrad_fused; g / y2 / dy_out live on the
  * conv's output side [B,Ho,Wo,Cout], dx / epi_y are [B,H,W,Cin]); epi_partial [sst_conv_s2_dgrad_tiles(B,H,W)][3][Cin] */
 int sst_conv_s2_dgrad_tiles(int B, int H, int W);
-/* kernel the two entries above launch for this shape, as rocprofv3 prints it (profiling labels) */
+/* kernel the two entries above launch for this shape, as rocprofv3 prints it (profiling labels): the launcher's own selection.
+ * Where the four parity classes go out one launch each, it is the kernel of the class-0 launch. */
 const char* sst_conv_s2_dgrad_kernel_name(int B, int H, int W, int Cin, int Cout, int fused);
 int sst_conv_s2_dgrad_fused(const float* g, const float* y2, const float* cA, const float* cB, const float* cC,
                             const float* in_scale, const float* in_shift, const float* in_slope, float in_slope_const,

@@ -923,6 +923,71 @@ SST_API int sst_conv_stat_tiles(int B, int H, int W, int Cin, int Cout, int ksiz
   return sst_conv_mtiles(B, (H + 2 * p - ksize) / stride + 1, (W + 2 * p - ksize) / stride + 1);
 }
 
+// ---- which kernel takes a forward-form conv launch (sst_conv_fwd and the data-gradient / fused entries that go through
+// conv_fwd_impl), with the launch parameters that follow from the choice.  conv_fwd_impl launches from it and sst_conv_kernel_name
+// reports it: a new kernel is added HERE and nowhere else.
+namespace {
+enum class FwdKind { TO3, C3IN_MFMA, C3IN, BAND, BIG_TILES, GENERAL };
+struct FwdSel {
+  FwdKind kind;
+  int nsp, nmt;      // TO3: column splits of a row, 16-column MFMA tiles per split
+  int wgs;           // C3IN_MFMA: workgroups of 4 tiles
+  int R;             // BAND: rows per band
+  size_t lds;        // TO3, C3IN: dynamic LDS bytes
+  const char* name;  // rocprofv3 spelling, without the argument list
+};
+
+// the shape half of Conv3Args for a k x k conv with padding k / 2
+void conv_shape_args(Conv3Args& a, int B, int H, int W, int Cin, int Cout, int ksize, int stride) {
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+  a.ksy = a.ksx = ksize; a.pad_y = a.pad_x = ksize / 2; a.sub_y = a.sub_x = 0; a.Hy = a.Wy = 0;
+  a.Ho = (H + 2 * (ksize / 2) - ksize) / stride + 1;
+  a.Wo = (W + 2 * (ksize / 2) - ksize) / stride + 1;
+}
+
+FwdSel conv_fwd_select(const Conv3Args& a, int ksize, int stride, int dbg_bits) {
+  FwdSel s{};
+  // the 3-channel kernels take 3x3 stride-1 NHWC convs with nothing fused around them (C3IN* may carry a bias)
+  const bool bare = ksize == 3 && stride == 1 && a.out_mode == OUT_NHWC && !a.in_scale && a.in_act == ACT_NONE && !a.residual && !a.stats &&
+                    !a.y_pre && !a.epi_partial && !a.in2 && dbg_bits == 0;
+  if (bare && a.Cin == 64 && a.Cout == 3 && !a.bias && !sst_env("SST_NO_TO3")) {
+    s.nsp = (a.W % 32 == 0 && a.W >= 64 && !sst_env("SST_TO3_NO_SPLIT")) ? 2 : 1;
+    s.nmt = (a.W / s.nsp + 2 + 15) / 16;
+    s.lds = (size_t)4 * s.nmt * 16 * 12 * sizeof(float);
+    if (s.lds <= 60 * 1024) {
+      s.kind = FwdKind::TO3; s.name = "conv3_to3_kernel";
+      return s;
+    }
+  }
+  if (bare && a.Cin == 3 && (a.Cout & 3) == 0 && CONV_NT % (a.Cout >> 2) == 0 && !sst_env("SST_NO_C3IN")) {
+    if ((a.W & 31) == 0 && a.Cout == 64 && !sst_env("SST_NO_C3IN_MFMA")) {
+      s.kind = FwdKind::C3IN_MFMA; s.name = "conv3_c3in_mfma_kernel";
+      s.wgs = (a.B * a.H * (a.W >> 5) + 3) / 4;
+      return s;
+    }
+    s.lds = (size_t)3 * ((a.W + 2) * 3 + 1) * sizeof(float);
+    if (s.lds <= 48 * 1024) {
+      s.kind = FwdKind::C3IN; s.name = "conv3_c3in_kernel";
+      return s;
+    }
+  }
+  if (a.out_mode == OUT_NHWC && !(dbg_bits & 8)) {
+    s.R = sst_conv_band_rows(a.B, a.H, a.W, a.Cin, a.Cout, ksize, stride);
+    if (s.R) {
+      s.kind = FwdKind::BAND; s.name = s.R * a.W / 16 == 9 ? "conv_band_kernel<9>" : "conv_band_kernel<3>";
+      return s;
+    }
+  }
+  if (dbg_bits == 0 && use_big_tiles(a, ksize)) {
+    s.kind = FwdKind::BIG_TILES; s.name = stride == 1 ? "conv_fwd2_kernel<1>" : "conv_fwd2_kernel<2>";
+    return s;
+  }
+  s.kind = FwdKind::GENERAL;
+  s.name = ksize != 3 ? "conv_fwd_kernel<9, 1>" : (stride == 1 ? "conv_fwd_kernel<3, 1>" : "conv_fwd_kernel<3, 2>");
+  return s;
+}
+}  // namespace
+
 // y = conv(act(x*in_scale+in_shift), w) (+bias) (+residual), stored per out_mode; optional BN partial stats.
 static int conv_fwd_impl(const float* x, const float* wp, float* y, float* y_pre, const float* bias, const float* in_scale,
                          const float* in_shift, const float* in_slope, float in_slope_const, int in_act,
@@ -953,10 +1018,7 @@ static int conv_fwd_impl(const float* x, const float* wp, float* y, float* y_pre
   a.in2 = in2; a.in_cA = in_cA; a.in_cB = in_cB; a.in_cC = in_cC; a.side_out = side_out;
   SST_REQUIRE(!in2 || ((Cin & 3) == 0 && stride == 1), "sst_conv_fwd: fused BN-backward input needs Cin %% 4 == 0, stride 1");
   SST_REQUIRE(!in_cA || (in2 && in_cB && in_cC), "sst_conv_fwd: cA/cB/cC need in2");
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-  a.ksy = a.ksx = ksize; a.pad_y = a.pad_x = ksize / 2; a.sub_y = a.sub_x = 0; a.Hy = a.Wy = 0;
-  a.Ho = (H + 2 * (ksize / 2) - ksize) / stride + 1;
-  a.Wo = (W + 2 * (ksize / 2) - ksize) / stride + 1;
+  conv_shape_args(a, B, H, W, Cin, Cout, ksize, stride);
   SST_REQUIRE(out_mode != OUT_UNSHUFFLE || ((a.Ho & 1) == 0 && (a.Wo & 1) == 0), "sst_conv_fwd: unshuffle needs even Ho,Wo");
   const int64_t mt = sst_conv_mtiles(B, a.Ho, a.Wo);
   SST_REQUIRE(mt < (1ll << 31), "sst_conv_fwd: too many tiles");
@@ -964,69 +1026,41 @@ static int conv_fwd_impl(const float* x, const float* wp, float* y, float* y_pre
   hipStream_t st = sst_stream(stream);
   const size_t extra_lds = (size_t)(dbg_bits >> 4) * 1024;   // dev knob: pad LDS to cap workgroups per CU
   a.dbg = dbg_bits & 15;
-  if (ksize == 3 && stride == 1 && Cin == 64 && Cout == 3 && out_mode == OUT_NHWC && !bias && !in_scale && in_act == ACT_NONE && !residual &&
-      !stats && !y_pre && !epi_partial && !in2 && dbg_bits == 0 && !sst_env("SST_NO_TO3")) {
-    const int nsp = (W % 32 == 0 && W >= 64 && !sst_env("SST_TO3_NO_SPLIT")) ? 2 : 1;
-    const int nmt = (W / nsp + 2 + 15) / 16;
-    const size_t lds = (size_t)4 * nmt * 16 * 12 * sizeof(float);
-    if (lds <= 60 * 1024) {
-      conv3_to3_kernel<<<(unsigned)((B * H * nsp + 3) / 4), CONV_NT, lds, st>>>(x, wp, y, B, H, W, nmt, nsp);
-      SST_LAUNCH_CHECK("conv3_to3_kernel");
-      return SST_OK;
-    }
+  const FwdSel s = conv_fwd_select(a, ksize, stride, dbg_bits);
+  switch (s.kind) {
+    case FwdKind::TO3:
+      conv3_to3_kernel<<<(unsigned)((B * H * s.nsp + 3) / 4), CONV_NT, s.lds, st>>>(x, wp, y, B, H, W, s.nmt, s.nsp);
+      break;
+    case FwdKind::C3IN_MFMA:
+      conv3_c3in_mfma_kernel<<<(unsigned)(s.wgs < 768 ? s.wgs : 768), CONV_NT, 0, st>>>(x, wp, bias, y, B, H, W, B * H * (W >> 5));
+      break;
+    case FwdKind::C3IN:
+      conv3_c3in_kernel<<<(unsigned)(B * H), CONV_NT, s.lds, st>>>(x, wp, bias, y, B, H, W, Cout);
+      break;
+    case FwdKind::BAND: return sst_launch_conv_band(a, s.R, st, band_acc);
+    case FwdKind::BIG_TILES: return sst_launch_conv_fwd2(a, stride, st);
+    case FwdKind::GENERAL:
+      if (ksize == 3 && stride == 1)
+        conv_fwd_kernel<3, 1><<<grid, CONV_NT, extra_lds, st>>>(a);
+      else if (ksize == 3)
+        conv_fwd_kernel<3, 2><<<grid, CONV_NT, 0, st>>>(a);
+      else
+        conv_fwd_kernel<9, 1><<<grid, CONV_NT, 0, st>>>(a);
+      break;
   }
-  if (ksize == 3 && stride == 1 && Cin == 3 && (Cout & 3) == 0 && CONV_NT % (Cout >> 2) == 0 && out_mode == OUT_NHWC && !in_scale &&
-      in_act == ACT_NONE && !residual && !stats && !y_pre && !epi_partial && !in2 && dbg_bits == 0 && !sst_env("SST_NO_C3IN")) {
-    if ((W & 31) == 0 && Cout == 64 && !sst_env("SST_NO_C3IN_MFMA")) {
-      const int ntiles = B * H * (W >> 5);
-      const int wgs = (ntiles + 3) / 4;
-      conv3_c3in_mfma_kernel<<<(unsigned)(wgs < 768 ? wgs : 768), CONV_NT, 0, st>>>(x, wp, bias, y, B, H, W, ntiles);
-      SST_LAUNCH_CHECK("conv3_c3in_mfma_kernel");
-      return SST_OK;
-    }
-    const size_t lds = (size_t)3 * ((W + 2) * 3 + 1) * sizeof(float);
-    if (lds <= 48 * 1024) {
-      conv3_c3in_kernel<<<(unsigned)(B * H), CONV_NT, lds, st>>>(x, wp, bias, y, B, H, W, Cout);
-      SST_LAUNCH_CHECK("conv3_c3in_kernel");
-      return SST_OK;
-    }
-  }
-  if (out_mode == OUT_NHWC && !(dbg_bits & 8)) {
-    const int R = sst_conv_band_rows(B, H, W, Cin, Cout, ksize, stride);
-    if (R) return sst_launch_conv_band(a, R, st, band_acc);
-  }
-  if (dbg_bits == 0 && use_big_tiles(a, ksize)) return sst_launch_conv_fwd2(a, stride, st);
-  if (ksize == 3 && stride == 1)
-    conv_fwd_kernel<3, 1><<<grid, CONV_NT, extra_lds, st>>>(a);
-  else if (ksize == 3)
-    conv_fwd_kernel<3, 2><<<grid, CONV_NT, 0, st>>>(a);
-  else
-    conv_fwd_kernel<9, 1><<<grid, CONV_NT, 0, st>>>(a);
-  SST_LAUNCH_CHECK("conv_fwd_kernel");
+  SST_LAUNCH_CHECK(s.name);
   return SST_OK;
 }
 
-// Name of the kernel sst_conv_fwd / sst_conv_dgrad_* dispatch to for this shape (as rocprofv3 prints it, without the
-// argument list) - bench.py labels its roofline rows with it so that they can be matched against profiles/.
+// Name of the kernel sst_conv_fwd / sst_conv_dgrad_* dispatch to for this shape when called plain - no bias, input affine,
+// activation, statistics or residual; fused_in: with the two-tensor input of the fused entries - as rocprofv3 prints it, without
+// the argument list.  It is conv_fwd_impl's own selection; bench.py labels its roofline rows with it.
 SST_API const char* sst_conv_kernel_name(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int out_mode, int fused_in) {
-  const int p = ksize / 2;
   Conv3Args a{};
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.out_mode = out_mode;
-  a.Ho = (H + 2 * p - ksize) / stride + 1;
-  a.Wo = (W + 2 * p - ksize) / stride + 1;
-  a.in2 = fused_in ? reinterpret_cast<const float*>(1) : nullptr;
-  if (ksize == 3 && stride == 1 && Cin == 64 && Cout == 3 && out_mode == OUT_NHWC && !fused_in && !sst_env("SST_NO_TO3") &&
-      (size_t)4 * ((W + 2 + 15) / 16) * 16 * 12 * sizeof(float) <= 60 * 1024)
-    return "conv3_to3_kernel";       // (when called plain, as the data-gradient of a 3-channel-input layer is)
-  if (ksize == 3 && stride == 1 && Cin == 3 && (Cout & 3) == 0 && CONV_NT % (Cout >> 2) == 0 && out_mode == OUT_NHWC && !fused_in)
-    return ((W & 31) == 0 && Cout == 64 && !sst_env("SST_NO_C3IN_MFMA")) ? "conv3_c3in_mfma_kernel" : "conv3_c3in_kernel";   // (when called without input affine / activation / residual / statistics)
-  if (out_mode == OUT_NHWC) {
-    const int R = sst_conv_band_rows(B, H, W, Cin, Cout, ksize, stride);
-    if (R) return R * W / 16 == 9 ? "conv_band_kernel<9>" : "conv_band_kernel<3>";
-  }
-  if (use_big_tiles(a, ksize)) return stride == 1 ? "conv_fwd2_kernel<1>" : "conv_fwd2_kernel<2>";
-  if (ksize == 3) return stride == 1 ? "conv_fwd_kernel<3, 1>" : "conv_fwd_kernel<3, 2>";
-  return "conv_fwd_kernel<9, 1>";
+  conv_shape_args(a, B, H, W, Cin, Cout, ksize, stride);
+  a.out_mode = out_mode;
+  a.in2 = fused_in ? reinterpret_cast<const float*>(1) : nullptr;      // sentinel: only tested, never read
+  return conv_fwd_select(a, ksize, stride, 0).name;
 }
 
 SST_API int sst_conv_fwd(const float* x, const float* wp, float* y, float* y_pre, const float* bias, const float* in_scale,
@@ -1165,95 +1199,110 @@ SST_API int sst_conv_s2_dgrad_tiles(int B, int H, int W) {
   }
   return t;
 }
+// ---- which launch form takes a stride-2 data-gradient: all four parity classes in one grid of the four-class kernel (MERGED4) or
+// of the class-per-z kernel (MERGED), or one forward-form launch per class (PER_CLASS: a class is empty or large enough for the
+// 64x64-tile kernel, or SST_S2_SPLIT asks for it).  conv_s2_dgrad_impl launches from it and sst_conv_s2_dgrad_kernel_name reports
+// it: a new form is added HERE and nowhere else.
+namespace {
+enum class S2Kind { MERGED4, MERGED, PER_CLASS };
+struct S2Sel {
+  S2Kind kind;
+  S2Classes c;
+  int max_tiles;
+  const char* name;      // PER_CLASS: the kernel of the class-0 launch
+};
+
+// the conv of one parity class (cls < 0: the merged launches, which take the class geometry from S2Classes) in forward form -
+// roles swap: its "input" is dy
+Conv3Args s2_dgrad_args(const float* dy, const float* wp, float* dx, int B, int H, int W, int Cin, int Cout, int cls) {
+  Conv3Args a{};
+  const int py = cls < 0 ? 0 : cls >> 1, px = cls < 0 ? 0 : cls & 1;
+  a.x = dy; a.wp = cls < 0 ? wp : wp + s2_class_offset(cls, Cin, Cout); a.y = dx;
+  a.in_act = ACT_NONE; a.out_mode = OUT_STRIDE2;
+  a.B = B; a.H = (H - 1) / 2 + 1; a.W = (W - 1) / 2 + 1; a.Cin = Cout; a.Cout = Cin;
+  a.ksy = 1 + py; a.ksx = 1 + px; a.sub_y = py; a.sub_x = px;
+  if (cls >= 0) { a.Ho = (H - py + 1) / 2; a.Wo = (W - px + 1) / 2; }      // pixels of this parity class
+  a.Hy = H; a.Wy = W;
+  return a;
+}
+
+S2Sel s2_dgrad_select(int B, int H, int W, int Cin, int Cout, bool fused) {
+  S2Sel s{};
+  bool ok = !sst_env("SST_S2_SPLIT") || fused;
+  int tbase = 0;
+  for (int cls = 0; cls < 4; ++cls) {
+    const Conv3Args t = s2_dgrad_args(nullptr, nullptr, nullptr, B, H, W, Cin, Cout, cls);
+    S2Classes& c = s.c;
+    c.nh[cls] = t.Ho;
+    c.nw[cls] = t.Wo;
+    c.wp_off[cls] = s2_class_offset(cls, Cin, Cout);
+    c.tiles[cls] = (t.Ho > 0 && t.Wo > 0) ? sst_conv_mtiles(B, t.Ho, t.Wo) : 0;
+    c.tile_base[cls] = tbase;
+    tbase += c.tiles[cls];
+    if (!fused && (c.tiles[cls] == 0 || use_big_tiles(t, 3))) ok = false;
+    if (cls == 0) s.name = use_big_tiles(t, 3) ? "conv_fwd2_kernel<1>" : "conv_fwd_kernel<3, 1>";
+    s.max_tiles = c.tiles[cls] > s.max_tiles ? c.tiles[cls] : s.max_tiles;
+  }
+  const bool s2d4 = !(sst_env("SST_S2DGRAD4") && atoi(sst_env("SST_S2DGRAD4")) == 0);
+  s.kind = S2Kind::PER_CLASS;
+  if (ok && s2d4 && !(H & 1) && !(W & 1) && !(Cout & 3) && !(Cin & 3)) {
+    s.kind = S2Kind::MERGED4;
+    s.name = fused ? "conv_s2dgrad4_kernel<true>" : "conv_s2dgrad4_kernel<false>";
+  } else if (ok) {
+    s.kind = S2Kind::MERGED;
+    s.name = "conv_s2dgrad_kernel";
+  }
+  return s;
+}
+}  // namespace
+
 static int conv_s2_dgrad_impl(const float* dy, const float* wp, float* dx, int B, int H, int W, int Cin, int Cout, void* stream,
                               const S2Fused* f) {
   SST_REQUIRE(dy && wp && dx && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "sst_conv_s2_dgrad: bad argument");
-  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-  {
-    // merged launch (all classes non-empty and none of them large enough for the 64x64-tile kernel)
-    Conv3Args a;
-    a.x = dy; a.wp = wp; a.y = dx; a.y_pre = nullptr; a.bias = nullptr;
-    a.in_scale = a.in_shift = a.in_slope = nullptr; a.in_slope_const = 0.f; a.in_act = ACT_NONE;
-    a.residual = nullptr; a.stats = nullptr; a.stats_cnt = nullptr; a.out_mode = OUT_STRIDE2; a.dbg = 0;
-    a.epi_y = a.epi_scale = a.epi_shift = a.epi_slope = nullptr; a.epi_slope_const = 0.f; a.epi_act = 0; a.epi_partial = nullptr;
-    a.in2 = a.in_cA = a.in_cB = a.in_cC = nullptr; a.side_out = nullptr;
-    if (f) {
-      a.in2 = f->in2; a.in_cA = f->cA; a.in_cB = f->cB; a.in_cC = f->cC; a.side_out = f->dy_out;
-      a.in_scale = f->in_scale; a.in_shift = f->in_shift; a.in_slope = f->in_slope; a.in_slope_const = f->in_slope_const;
-      a.in_act = f->in_act;
-      a.epi_y = f->epi_y; a.epi_scale = f->epi_scale; a.epi_shift = f->epi_shift; a.epi_slope = f->epi_slope;
-      a.epi_slope_const = f->epi_slope_const; a.epi_act = f->epi_act; a.epi_partial = f->epi_partial;
-    }
-    a.B = B; a.H = Ho; a.W = Wo; a.Cin = Cout; a.Cout = Cin;
-    a.ksy = a.ksx = 1; a.pad_y = a.pad_x = 0; a.sub_y = a.sub_x = 0; a.Ho = a.Wo = 0; a.Hy = H; a.Wy = W;
-    S2Classes c;
-    bool ok = !sst_env("SST_S2_SPLIT") || f;
-    int max_tiles = 0, tbase = 0;
-    for (int cls = 0; cls < 4; ++cls) {
-      const int py = cls >> 1, px = cls & 1;
-      c.nh[cls] = (H - py + 1) / 2;
-      c.nw[cls] = (W - px + 1) / 2;
-      c.wp_off[cls] = s2_class_offset(cls, Cin, Cout);
-      c.tiles[cls] = (c.nh[cls] > 0 && c.nw[cls] > 0) ? sst_conv_mtiles(B, c.nh[cls], c.nw[cls]) : 0;
-      c.tile_base[cls] = tbase;
-      tbase += c.tiles[cls];
-      if (c.tiles[cls] == 0 && !f) ok = false;
-      Conv3Args t = a;
-      t.Ho = c.nh[cls]; t.Wo = c.nw[cls];
-      if (!f && c.tiles[cls] && use_big_tiles(t, 3)) ok = false;
-      max_tiles = c.tiles[cls] > max_tiles ? c.tiles[cls] : max_tiles;
-    }
-    static const bool s2d4 = !(sst_env("SST_S2DGRAD4") && atoi(sst_env("SST_S2DGRAD4")) == 0);
-    if (ok && s2d4 && !(H & 1) && !(W & 1) && !(Cout & 3) && !(Cin & 3)) {
-      a.Ho = c.nh[0]; a.Wo = c.nw[0];
-      dim3 grid((unsigned)c.tiles[0], (Cin + 31) / 32);
-      if (f)
-        conv_s2dgrad4_kernel<true><<<grid, CONV_NT, 0, sst_stream(stream)>>>(a, c);
-      else
-        conv_s2dgrad4_kernel<false><<<grid, CONV_NT, 0, sst_stream(stream)>>>(a, c);
-      SST_LAUNCH_CHECK("conv_s2dgrad4_kernel");
-      return SST_OK;
-    }
-    if (ok) {
-      dim3 grid((unsigned)max_tiles, (Cin + 31) / 32, 4);
-      conv_s2dgrad_kernel<<<grid, CONV_NT, 0, sst_stream(stream)>>>(a, c);
-      SST_LAUNCH_CHECK("conv_s2dgrad_kernel");
-      return SST_OK;
-    }
+  const S2Sel s = s2_dgrad_select(B, H, W, Cin, Cout, f != nullptr);
+  hipStream_t st = sst_stream(stream);
+  if (s.kind == S2Kind::PER_CLASS) {
     SST_REQUIRE(!f, "sst_conv_s2_dgrad_fused: merged launch not possible");
-  }
-  for (int cls = 0; cls < 4; ++cls) {
-    const int py = cls >> 1, px = cls & 1;
-    const int nh = (H - py + 1) / 2, nw = (W - px + 1) / 2;   // pixels of this parity class
-    if (nh <= 0 || nw <= 0) continue;
-    Conv3Args a;
-    a.x = dy; a.wp = wp + s2_class_offset(cls, Cin, Cout); a.y = dx; a.y_pre = nullptr; a.bias = nullptr;
-    a.in_scale = a.in_shift = a.in_slope = nullptr; a.in_slope_const = 0.f; a.in_act = ACT_NONE;
-    a.residual = nullptr; a.stats = nullptr; a.stats_cnt = nullptr; a.out_mode = OUT_STRIDE2; a.dbg = 0;
-    a.epi_y = a.epi_scale = a.epi_shift = a.epi_slope = nullptr; a.epi_slope_const = 0.f; a.epi_act = 0; a.epi_partial = nullptr;
-    a.in2 = a.in_cA = a.in_cB = a.in_cC = nullptr; a.side_out = nullptr;
-    a.B = B; a.H = Ho; a.W = Wo; a.Cin = Cout; a.Cout = Cin;     // roles swap: the "input" of this conv is dy
-    a.ksy = 1 + py; a.ksx = 1 + px; a.pad_y = a.pad_x = 0; a.sub_y = py; a.sub_x = px;
-    a.Ho = nh; a.Wo = nw; a.Hy = H; a.Wy = W;
-    if (use_big_tiles(a, 3)) {
-      const int rc = sst_launch_conv_fwd2(a, 1, sst_stream(stream));
-      if (rc != SST_OK) return rc;
-      continue;
+    for (int cls = 0; cls < 4; ++cls) {
+      if (s.c.tiles[cls] == 0) continue;
+      const Conv3Args a = s2_dgrad_args(dy, wp, dx, B, H, W, Cin, Cout, cls);
+      if (use_big_tiles(a, 3)) {
+        const int rc = sst_launch_conv_fwd2(a, 1, st);
+        if (rc != SST_OK) return rc;
+        continue;
+      }
+      conv_fwd_kernel<3, 1><<<dim3((unsigned)s.c.tiles[cls], (Cin + 31) / 32), CONV_NT, 0, st>>>(a);
+      SST_LAUNCH_CHECK("conv_fwd_kernel<3,1> (s2 dgrad)");
     }
-    dim3 grid((unsigned)sst_conv_mtiles(B, nh, nw), (Cin + 31) / 32);
-    conv_fwd_kernel<3, 1><<<grid, CONV_NT, 0, sst_stream(stream)>>>(a);
-    SST_LAUNCH_CHECK("conv_fwd_kernel<3,1> (s2 dgrad)");
+    return SST_OK;
   }
+  Conv3Args a = s2_dgrad_args(dy, wp, dx, B, H, W, Cin, Cout, -1);
+  if (f) {
+    a.in2 = f->in2; a.in_cA = f->cA; a.in_cB = f->cB; a.in_cC = f->cC; a.side_out = f->dy_out;
+    a.in_scale = f->in_scale; a.in_shift = f->in_shift; a.in_slope = f->in_slope; a.in_slope_const = f->in_slope_const;
+    a.in_act = f->in_act;
+    a.epi_y = f->epi_y; a.epi_scale = f->epi_scale; a.epi_shift = f->epi_shift; a.epi_slope = f->epi_slope;
+    a.epi_slope_const = f->epi_slope_const; a.epi_act = f->epi_act; a.epi_partial = f->epi_partial;
+  }
+  if (s.kind == S2Kind::MERGED4) {
+    a.Ho = s.c.nh[0]; a.Wo = s.c.nw[0];
+    const dim3 grid((unsigned)s.c.tiles[0], (Cin + 31) / 32);
+    if (f)
+      conv_s2dgrad4_kernel<true><<<grid, CONV_NT, 0, st>>>(a, s.c);
+    else
+      conv_s2dgrad4_kernel<false><<<grid, CONV_NT, 0, st>>>(a, s.c);
+  } else {
+    conv_s2dgrad_kernel<<<dim3((unsigned)s.max_tiles, (Cin + 31) / 32, 4), CONV_NT, 0, st>>>(a, s.c);
+  }
+  SST_LAUNCH_CHECK(s.name);
   return SST_OK;
 }
 
 // Name of the kernel sst_conv_s2_dgrad (fused = 0) / sst_conv_s2_dgrad_fused (fused = 1) launch for this shape (rocprofv3
-// spelling): the merged-classes kernel for even H, W with channel counts that are multiples of 4, else the per-class launch.
+// spelling): the launcher's own selection.  Where the classes go out one launch each (a class is empty or large enough for the
+// 64x64-tile kernel), it is the kernel of the class-0 launch: conv_fwd2_kernel<1> or conv_fwd_kernel<3, 1>.
 SST_API const char* sst_conv_s2_dgrad_kernel_name(int B, int H, int W, int Cin, int Cout, int fused) {
-  (void)B;
-  const bool off = sst_env("SST_S2DGRAD4") && atoi(sst_env("SST_S2DGRAD4")) == 0;
-  if (!off && !(H & 1) && !(W & 1) && !(Cout & 3) && !(Cin & 3)) return fused ? "conv_s2dgrad4_kernel<true>" : "conv_s2dgrad4_kernel<false>";
-  return "conv_s2dgrad_kernel";
+  return s2_dgrad_select(B, H, W, Cin, Cout, fused != 0).name;
 }
 
 SST_API int sst_conv_s2_dgrad(const float* dy, const float* wp, float* dx, int B, int H, int W, int Cin, int Cout,

@@ -584,8 +584,8 @@ __global__ __launch_bounds__(1024) void c3m_reduce_kernel(const float* __restric
 inline bool k3c3_mfma_applies(int W, int Cout) { return (W & 31) == 0 && Cout == 64 && !sst_env("SST_WGRAD_NO_K3C3_MFMA"); }
 inline int k3c3_mfma_chunks(int B, int H, int W) { return (B * H * (W >> 5) + 4 * C3M_TPW - 1) / (4 * C3M_TPW); }
 
-inline bool k3c3_applies(int Cin, int ksize, int stride, const float* in_scale, int in_act) {
-  return Cin == 3 && ksize == 3 && stride == 1 && !in_scale && in_act == ACT_NONE;
+inline bool k3c3_applies(int Cin, int ksize, int stride, bool has_in_scale, int in_act) {
+  return Cin == 3 && ksize == 3 && stride == 1 && !has_in_scale && in_act == ACT_NONE;
 }
 
 // Plan of the band variant: rows per band R, bands per chunk, number of chunks - or R = 0 when the shape is not covered.
@@ -1092,55 +1092,124 @@ static int launch_wgrad_band(WgradArgs& a, const WgBandPlan& pl, int njobs, hipS
   return SST_OK;
 }
 
-// Chunk count (slab floats per layer = chunks*k*k*Cout*Cin) that sst_conv_wgrad (njobs = 1) / sst_conv_wgrad_grouped use
-// for this shape; H, W are the INPUT size.
-SST_API int sst_conv_wgrad_chunks2(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int njobs) {
-  if (njobs == 1) {
-    const WgS2Plan p2 = wgrad_s2_plan(B, H, W, Cin, Cout, ksize, stride);
-    if (p2.th) return p2.nchunk;
-  }
-  const WgBandPlan pl = wgrad_band_plan(B, H, W, Cin, Cout, ksize, stride, njobs);
-  if (pl.R) return pl.nchunk;
-  const int pad = ksize / 2;
-  if (Cin == 3 && ksize == 3 && stride == 1) {         // 3-channel-input kernels (one chunk per workgroup) or the general one
-    int a = B * ((H + C3_ROWS - 1) / C3_ROWS);
-    const int g = sst_conv_wgrad_chunks(B, H, W, Cin, Cout, ksize);
-    if (k3c3_mfma_applies(W, Cout) && k3c3_mfma_chunks(B, H, W) > a) a = k3c3_mfma_chunks(B, H, W);
-    return a > g ? a : g;
-  }
-  return sst_conv_wgrad_chunks(B, (H + 2 * pad - ksize) / stride + 1, (W + 2 * pad - ksize) / stride + 1, Cin, Cout, ksize);
-}
+// ---- the plan of one weight-gradient launch: which kernel takes the shape, how many chunks it writes into the slab and what it
+// leaves for a later reduce.  Both launchers run it (sst_conv_wgrad_grp: njobs = 1; sst_conv_wgrad_grouped: njobs layers of one
+// shape per launch) and the sizing / naming entries below only report it - a new kernel is added HERE and nowhere else.
+namespace {
+enum class WgKind { TILE, BAND, K3C3_MFMA, K3C3, GENERAL_VEC, GENERAL_SCALAR };
+struct WgradPlan {
+  WgKind kind;
+  int nchunk;         // chunks the launch writes into the slab
+  int pending;        // chunks left for sst_wgrad_reduce_multi under accumulate bit 2; 0: the launch writes dW itself
+  int slab_chunks;    // chunks to size the slab for: >= nchunk whatever input affine / activation the call carries, whichever
+                      // 3-channel form is switched off and however many layers share a grouped launch (callers size before they know)
+  int chunk_px;       // GENERAL_*: pixels per chunk (multiple of SUB)
+  WgS2Plan tile;      // TILE
+  WgBandPlan band;    // BAND
+  const char* name;   // rocprofv3 spelling of the kernel
+};
 
-// Name of the main kernel sst_conv_wgrad (njobs = 1) / sst_conv_wgrad_grouped launch for this shape (rocprofv3 spelling).
-SST_API const char* sst_conv_wgrad_kernel_name(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int njobs) {
-  if (njobs == 1) {
-    const WgS2Plan p2 = wgrad_s2_plan(B, H, W, Cin, Cout, ksize, stride);
-    if (p2.th) {
-      static thread_local char nm[56];
-      snprintf(nm, sizeof(nm), "conv_wgrad_tile_kernel<%d, %d, %d, %d>", stride, p2.th, p2.tw, p2.nw);
-      return nm;
+// grouped: the launch is sst_conv_wgrad_grouped's (one grid for njobs layers): the per-layer forms (TILE, K3C3*) are not taken
+WgradPlan wgrad_plan(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int njobs, bool has_in_scale, int in_act,
+                     bool grouped) {
+  WgradPlan p{};
+  if (!grouped) p.tile = wgrad_s2_plan(B, H, W, Cin, Cout, ksize, stride);
+  if (p.tile.th) {
+    static const char* const names[2][2] = {{"conv_wgrad_tile_kernel<1, 4, 8, 8>", "conv_wgrad_tile_kernel<1, 4, 6, 8>"},
+                                            {"conv_wgrad_tile_kernel<2, 2, 8, 8>", "conv_wgrad_tile_kernel<2, 2, 6, 8>"}};
+    const bool direct = p.tile.nchunk == 1 && !sst_env("SST_WGRAD_TILE_NO_DIRECT");      // the single chunk goes straight into dW
+    p.kind = WgKind::TILE;
+    p.nchunk = p.slab_chunks = p.tile.nchunk;
+    p.pending = direct ? 0 : p.nchunk;
+    p.name = names[stride == 2][p.tile.tw == 6];
+    return p;
+  }
+  p.band = wgrad_band_plan(B, H, W, Cin, Cout, ksize, stride, njobs);
+  if (p.band.R) {
+    p.kind = WgKind::BAND;
+    p.nchunk = p.slab_chunks = p.band.nchunk;
+    p.pending = grouped ? 0 : p.nchunk;
+    p.name = ((p.band.R + 2) * (W + 2) * 16 + CONV_NT - 1) / CONV_NT <= 7 ? "conv_wgrad_band_kernel<7>" : "conv_wgrad_band_kernel<10>";
+    return p;
+  }
+  const int pad = ksize / 2, Ho = (H + 2 * pad - ksize) / stride + 1, Wo = (W + 2 * pad - ksize) / stride + 1;
+  const int64_t M = (int64_t)B * Ho * Wo;
+  int nchunk = sst_conv_wgrad_chunks(B, Ho, Wo, Cin, Cout, ksize);
+  p.slab_chunks = nchunk;
+  if (Cin == 3 && ksize == 3 && stride == 1) {           // 3-channel-input kernels: one chunk per workgroup
+    const int rows = B * ((H + C3_ROWS - 1) / C3_ROWS);
+    const bool mfma = k3c3_mfma_applies(W, Cout);
+    if (rows > p.slab_chunks) p.slab_chunks = rows;
+    if (mfma && k3c3_mfma_chunks(B, H, W) > p.slab_chunks) p.slab_chunks = k3c3_mfma_chunks(B, H, W);
+    if (!grouped && k3c3_applies(Cin, ksize, stride, has_in_scale, in_act)) {
+      if (mfma) {                                        // (its own reduce follows in the same call)
+        p.kind = WgKind::K3C3_MFMA;
+        p.nchunk = k3c3_mfma_chunks(B, H, W);
+        p.name = "wgrad_k3c3_mfma_kernel";
+        return p;
+      }
+      if (!sst_env("SST_WGRAD_NO_K3C3")) {
+        p.kind = WgKind::K3C3;
+        p.nchunk = p.pending = rows;
+        p.name = "wgrad_k3c3_kernel";
+        return p;
+      }
     }
   }
-  const WgBandPlan pl = wgrad_band_plan(B, H, W, Cin, Cout, ksize, stride, njobs);
-  if (pl.R) return ((pl.R + 2) * (W + 2) * 16 + CONV_NT - 1) / CONV_NT <= 7 ? "conv_wgrad_band_kernel<7>" : "conv_wgrad_band_kernel<10>";
-  if (Cin == 3 && ksize == 3 && stride == 1) return k3c3_mfma_applies(W, Cout) ? "wgrad_k3c3_mfma_kernel" : "wgrad_k3c3_kernel";
-  return ((Cin & 3) == 0 && (Cout & 3) == 0) ? "conv_wgrad_kernel<true>" : "conv_wgrad_kernel<false>";
+  if (grouped) {
+    // With many layers in one grid the chip is full without fine pixel chunks: aim at ~target workgroups in total
+    // (fewer, longer chunks = less slab traffic).  Never more chunks than the per-layer slab was sized for.
+    int target = 2048;
+    if (const char* e = sst_env("SST_WGRAD_GROUP_WGS")) target = atoi(e);
+    const int nblk = ((Cout + 63) / 64) * ((Cin + 63) / 64);
+    int want = (target + ksize * ksize * nblk * njobs - 1) / (ksize * ksize * nblk * njobs);
+    if (want < 1) want = 1;
+    if (target > 0 && want < nchunk) {
+      const int64_t cpx = ((M + want - 1) / want + SUB - 1) / SUB * SUB;
+      nchunk = (int)((M + cpx - 1) / cpx);
+    }
+  }
+  const bool vec = (Cin & 3) == 0 && (Cout & 3) == 0;
+  p.kind = vec ? WgKind::GENERAL_VEC : WgKind::GENERAL_SCALAR;
+  p.nchunk = nchunk;
+  p.pending = grouped ? 0 : nchunk;
+  p.chunk_px = (int)(((M + nchunk - 1) / nchunk + SUB - 1) / SUB * SUB);
+  p.name = vec ? "conv_wgrad_kernel<true>" : "conv_wgrad_kernel<false>";
+  return p;
+}
+
+// the shape half of WgradArgs, shared by the two launchers
+void wgrad_shape_args(WgradArgs& a, const WgradPlan& pl, int B, int H, int W, int Cin, int Cout, int ksize, int stride) {
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.stride = stride; a.KS = ksize; a.pad = ksize / 2;
+  a.Ho = (H + 2 * a.pad - ksize) / stride + 1;
+  a.Wo = (W + 2 * a.pad - ksize) / stride + 1;
+  a.chunk_px = pl.chunk_px;
+}
+}  // namespace
+
+// Chunk count to size a layer's slab with (slab floats = chunks*k*k*Cout*Cin) for sst_conv_wgrad (njobs = 1) / sst_conv_wgrad_grouped
+// launches of this shape; H, W are the INPUT size.
+SST_API int sst_conv_wgrad_chunks2(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int njobs) {
+  return wgrad_plan(B, H, W, Cin, Cout, ksize, stride, njobs, false, ACT_NONE, njobs > 1).slab_chunks;
+}
+
+// Name of the main kernel sst_conv_wgrad (njobs = 1) / sst_conv_wgrad_grouped launch for this shape when called plain: no input
+// affine, no activation (rocprofv3 spelling).
+SST_API const char* sst_conv_wgrad_kernel_name(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int njobs) {
+  return wgrad_plan(B, H, W, Cin, Cout, ksize, stride, njobs, false, ACT_NONE, njobs > 1).name;
 }
 
 // Does sst_conv_wgrad_grp take this shape with coefficient groups of grp_images images (the all-taps tile kernel does; a layer whose
 // input has no BatchNorm affine needs no groups at all)?
 SST_API int sst_conv_wgrad_groups_ok(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int grp_images) {
-  return grp_images > 0 && B % grp_images == 0 && wgrad_s2_plan(B, H, W, Cin, Cout, ksize, stride).th != 0;
+  return grp_images > 0 && B > 0 && B % grp_images == 0 &&
+         wgrad_plan(B, H, W, Cin, Cout, ksize, stride, 1, true, ACT_NONE, false).kind == WgKind::TILE;
 }
 
-SST_API int sst_conv_wgrad_grp(const float* x, const float* dy, float* slab, float* dw, const float* in_scale,
-                               const float* in_shift, const float* in_slope, float in_slope_const, int in_act, int B, int H,
-                               int W, int Cin, int Cout, int stride, int ksize, int accumulate, int grp_images, void* stream);
-SST_API int sst_conv_wgrad(const float* x, const float* dy, float* slab, float* dw, const float* in_scale,
-                           const float* in_shift, const float* in_slope, float in_slope_const, int in_act, int B, int H,
-                           int W, int Cin, int Cout, int stride, int ksize, int accumulate, void* stream) {
-  return sst_conv_wgrad_grp(x, dy, slab, dw, in_scale, in_shift, in_slope, in_slope_const, in_act, B, H, W, Cin, Cout, stride, ksize,
-                            accumulate, 0, stream);
+// Chunks of slab that sst_conv_wgrad_grp leaves for sst_wgrad_reduce_multi when called with accumulate bit 2 (value 4) for this shape;
+// 0: the launch writes dW itself (single-chunk tile kernel, 3-channel MFMA kernel with its own reduce) and the bit changes nothing.
+SST_API int sst_conv_wgrad_pending_reduce(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int has_in_scale, int in_act) {
+  return wgrad_plan(B, H, W, Cin, Cout, ksize, stride, 1, has_in_scale != 0, in_act, false).pending;
 }
 
 // grp_images > 0: in_scale / in_shift are [B / grp_images][Cin] - images b*grp_images .. use row b (several passes of the network
@@ -1149,92 +1218,77 @@ SST_API int sst_conv_wgrad_grp(const float* x, const float* dy, float* slab, flo
                                const float* in_shift, const float* in_slope, float in_slope_const, int in_act, int B, int H,
                                int W, int Cin, int Cout, int stride, int ksize, int accumulate, int grp_images, void* stream) {
   SST_REQUIRE(x && dy && slab && dw, "sst_conv_wgrad: null pointer");
-  const bool grouped = grp_images > 0 && grp_images < B && in_scale;
-  SST_REQUIRE(!grouped || sst_conv_wgrad_groups_ok(B, H, W, Cin, Cout, ksize, stride, grp_images),
-              "sst_conv_wgrad: coefficient groups are only taken by the all-taps tile kernel (B=%d H=%d W=%d Cin=%d Cout=%d stride=%d)", B, H, W,
-              Cin, Cout, stride);
   SST_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && (stride == 1 || stride == 2) && (ksize & 1) && ksize <= 9,
               "sst_conv_wgrad: bad shape");
+  const WgradPlan pl = wgrad_plan(B, H, W, Cin, Cout, ksize, stride, 1, in_scale != nullptr, in_act, false);
+  const bool grouped = grp_images > 0 && grp_images < B && in_scale;
+  SST_REQUIRE(!grouped || (B % grp_images == 0 && pl.kind == WgKind::TILE),
+              "sst_conv_wgrad: coefficient groups are only taken by the all-taps tile kernel (B=%d H=%d W=%d Cin=%d Cout=%d stride=%d)", B, H, W,
+              Cin, Cout, stride);
   WgradArgs a;
   a.grouped = 0; a.nchunk = 0;
   static const WgJobTab no_tab{};
   a.x = x; a.dy = dy; a.slab = slab; a.in_scale = in_scale; a.in_shift = in_shift; a.in_slope = in_slope;
   a.in_slope_const = in_slope_const; a.in_act = in_act;
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.stride = stride; a.KS = ksize; a.pad = ksize / 2;
-  a.Ho = (H + 2 * a.pad - ksize) / stride + 1;
-  a.Wo = (W + 2 * a.pad - ksize) / stride + 1;
-  const int64_t M = (int64_t)B * a.Ho * a.Wo;
-  SST_REQUIRE(M < (1ll << 31), "sst_conv_wgrad: too many pixels");
-  int nchunk = sst_conv_wgrad_chunks(B, a.Ho, a.Wo, Cin, Cout, ksize);
-  a.chunk_px = (int)(((M + nchunk - 1) / nchunk + SUB - 1) / SUB * SUB);
+  wgrad_shape_args(a, pl, B, H, W, Cin, Cout, ksize, stride);
+  SST_REQUIRE((int64_t)B * a.Ho * a.Wo < (1ll << 31), "sst_conv_wgrad: too many pixels");
   {
     const char* e = sst_env("SST_WGRAD_DBG");
     a.dbg = e ? atoi(e) : 0;
   }
   const int KK = ksize * ksize;
-  dim3 grid(nchunk, KK, ((Cout + 63) / 64) * ((Cin + 63) / 64));
-  const WgS2Plan p2 = wgrad_s2_plan(B, H, W, Cin, Cout, ksize, stride);
-  const WgBandPlan pl = p2.th ? WgBandPlan{0, 0, 0, 0, 0} : wgrad_band_plan(B, H, W, Cin, Cout, ksize, stride, 1);
-  if (pl.R) {
-    const int rc = launch_wgrad_band(a, pl, 1, sst_stream(stream), no_tab);
-    if (rc != SST_OK) return rc;
-    nchunk = pl.nchunk;
-  } else if (p2.th) {
-    WgS2Args s2;
-    s2.x = x; s2.dy = dy; s2.slab = slab; s2.in_scale = in_scale; s2.in_shift = in_shift; s2.in_slope = in_slope;
-    s2.in_slope_const = in_slope_const; s2.in_act = in_act;
-    s2.B = B; s2.H = H; s2.W = W; s2.Cin = Cin; s2.Cout = Cout; s2.Ho = a.Ho; s2.Wo = a.Wo;
-    s2.dbg = sst_env("SST_WGRAD_S2_DBG") ? atoi(sst_env("SST_WGRAD_S2_DBG")) : 0;
-    const bool direct = p2.nchunk == 1 && !sst_env("SST_WGRAD_TILE_NO_DIRECT");
-    s2.dw = direct ? dw : nullptr;
-    s2.accumulate = accumulate & 1;
-    s2.gB = grouped ? grp_images : 0;
-    s2.tiles_x = a.Wo / p2.tw; s2.tiles_img = (a.Ho / p2.th) * s2.tiles_x; s2.ntiles = p2.ntiles; s2.tpc = p2.tpc;
-    int rc;
-    if (stride == 2) rc = p2.tw == 8 ? launch_wgrad_s2_t<2, 2, 8, 8>(s2, p2, sst_stream(stream)) : launch_wgrad_s2_t<2, 2, 6, 8>(s2, p2, sst_stream(stream));
-    else rc = p2.tw == 8 ? launch_wgrad_s2_t<1, 4, 8, 8>(s2, p2, sst_stream(stream)) : launch_wgrad_s2_t<1, 4, 6, 8>(s2, p2, sst_stream(stream));
-    if (rc != SST_OK) return rc;
-    if (direct) {
-      SST_LAUNCH_CHECK("conv_wgrad_tile_kernel");
-      return SST_OK;                            // the single chunk went straight into dW
+  const dim3 grid(pl.nchunk, KK, ((Cout + 63) / 64) * ((Cin + 63) / 64));      // GENERAL_*
+  hipStream_t st = sst_stream(stream);
+  switch (pl.kind) {
+    case WgKind::BAND: {
+      const int rc = launch_wgrad_band(a, pl.band, 1, st, no_tab);
+      if (rc != SST_OK) return rc;
+      break;
     }
-    nchunk = p2.nchunk;
-  } else if (k3c3_applies(Cin, ksize, stride, in_scale, in_act) && k3c3_mfma_applies(W, Cout)) {
-    nchunk = k3c3_mfma_chunks(B, H, W);
-    wgrad_k3c3_mfma_kernel<<<nchunk, CONV_NT, 0, sst_stream(stream)>>>(x, dy, slab, B, H, W, B * H * (W >> 5));
-    SST_LAUNCH_CHECK("wgrad_k3c3_mfma_kernel");
-    c3m_reduce_kernel<<<9 * 64 * 3 / C3R_OUT, 1024, 0, sst_stream(stream)>>>(slab, dw, nchunk, accumulate);
-    SST_LAUNCH_CHECK("c3m_reduce_kernel");
-    return SST_OK;
-  } else if (k3c3_applies(Cin, ksize, stride, in_scale, in_act) && !sst_env("SST_WGRAD_NO_K3C3")) {
-    nchunk = B * ((H + C3_ROWS - 1) / C3_ROWS);
-    const size_t lds = (size_t)(C3_ROWS + 2) * ((W + 2) * 3 + 3) * sizeof(float);
-    SST_REQUIRE(lds <= 48 * 1024, "sst_conv_wgrad: image too wide for the 3-channel-input kernel (W=%d)", W);
-    wgrad_k3c3_kernel<<<dim3(nchunk, 1), CONV_NT, lds, sst_stream(stream)>>>(x, dy, slab, B, H, W, Cout);
-  } else if ((Cin & 3) == 0 && (Cout & 3) == 0)
-    conv_wgrad_kernel<true><<<grid, CONV_NT, 0, sst_stream(stream)>>>(a, no_tab);
-  else
-    conv_wgrad_kernel<false><<<grid, CONV_NT, 0, sst_stream(stream)>>>(a, no_tab);
-  SST_LAUNCH_CHECK("conv_wgrad_kernel");
-  if (accumulate & 4) return SST_OK;             // the caller reduces the slab later (sst_wgrad_reduce_multi)
-  launch_wgrad_reduce(slab, dw, nchunk, KK, Cout, Cin, accumulate, nullptr, 1, sst_stream(stream));
+    case WgKind::TILE: {
+      const WgS2Plan& p2 = pl.tile;
+      WgS2Args s2;
+      s2.x = x; s2.dy = dy; s2.slab = slab; s2.in_scale = in_scale; s2.in_shift = in_shift; s2.in_slope = in_slope;
+      s2.in_slope_const = in_slope_const; s2.in_act = in_act;
+      s2.B = B; s2.H = H; s2.W = W; s2.Cin = Cin; s2.Cout = Cout; s2.Ho = a.Ho; s2.Wo = a.Wo;
+      s2.dbg = sst_env("SST_WGRAD_S2_DBG") ? atoi(sst_env("SST_WGRAD_S2_DBG")) : 0;
+      s2.dw = pl.pending ? nullptr : dw;
+      s2.accumulate = accumulate & 1;
+      s2.gB = grouped ? grp_images : 0;
+      s2.tiles_x = a.Wo / p2.tw; s2.tiles_img = (a.Ho / p2.th) * s2.tiles_x; s2.ntiles = p2.ntiles; s2.tpc = p2.tpc;
+      int rc;
+      if (stride == 2) rc = p2.tw == 8 ? launch_wgrad_s2_t<2, 2, 8, 8>(s2, p2, st) : launch_wgrad_s2_t<2, 2, 6, 8>(s2, p2, st);
+      else rc = p2.tw == 8 ? launch_wgrad_s2_t<1, 4, 8, 8>(s2, p2, st) : launch_wgrad_s2_t<1, 4, 6, 8>(s2, p2, st);
+      if (rc != SST_OK) return rc;
+      break;
+    }
+    case WgKind::K3C3_MFMA:
+      wgrad_k3c3_mfma_kernel<<<pl.nchunk, CONV_NT, 0, st>>>(x, dy, slab, B, H, W, B * H * (W >> 5));
+      SST_LAUNCH_CHECK("wgrad_k3c3_mfma_kernel");
+      c3m_reduce_kernel<<<9 * 64 * 3 / C3R_OUT, 1024, 0, st>>>(slab, dw, pl.nchunk, accumulate & 1);      // (bit 2 changes nothing here)
+      SST_LAUNCH_CHECK("c3m_reduce_kernel");
+      return SST_OK;
+    case WgKind::K3C3: {
+      const size_t lds = (size_t)(C3_ROWS + 2) * ((W + 2) * 3 + 3) * sizeof(float);
+      SST_REQUIRE(lds <= 48 * 1024, "sst_conv_wgrad: image too wide for the 3-channel-input kernel (W=%d)", W);
+      wgrad_k3c3_kernel<<<dim3(pl.nchunk, 1), CONV_NT, lds, st>>>(x, dy, slab, B, H, W, Cout);
+      break;
+    }
+    case WgKind::GENERAL_VEC: conv_wgrad_kernel<true><<<grid, CONV_NT, 0, st>>>(a, no_tab); break;
+    case WgKind::GENERAL_SCALAR: conv_wgrad_kernel<false><<<grid, CONV_NT, 0, st>>>(a, no_tab); break;
+  }
+  SST_LAUNCH_CHECK(pl.name);
+  if (pl.pending == 0 || (accumulate & 4)) return SST_OK;      // dW is written / the caller reduces the slab later (sst_wgrad_reduce_multi)
+  launch_wgrad_reduce(slab, dw, pl.nchunk, KK, Cout, Cin, accumulate, nullptr, 1, st);
   SST_LAUNCH_CHECK("wgrad_reduce_kernel");
   return SST_OK;
 }
 
-// Chunks of slab that sst_conv_wgrad_grp leaves for sst_wgrad_reduce_multi when called with accumulate bit 2 (value 4) for this shape;
-// 0: the launch writes dW itself (single-chunk tile kernel, 3-channel MFMA kernel with its own reduce) and the bit changes nothing.
-SST_API int sst_conv_wgrad_pending_reduce(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int has_in_scale, int in_act) {
-  const WgS2Plan p2 = wgrad_s2_plan(B, H, W, Cin, Cout, ksize, stride);
-  if (p2.th) return (p2.nchunk == 1 && !sst_env("SST_WGRAD_TILE_NO_DIRECT")) ? 0 : p2.nchunk;
-  const WgBandPlan pl = wgrad_band_plan(B, H, W, Cin, Cout, ksize, stride, 1);
-  if (pl.R) return pl.nchunk;
-  static const float one = 0.f;
-  const bool c3 = k3c3_applies(Cin, ksize, stride, has_in_scale ? &one : nullptr, in_act);
-  if (c3 && k3c3_mfma_applies(W, Cout)) return 0;
-  if (c3 && !sst_env("SST_WGRAD_NO_K3C3")) return B * ((H + C3_ROWS - 1) / C3_ROWS);
-  const int pad = ksize / 2;
-  return sst_conv_wgrad_chunks(B, (H + 2 * pad - ksize) / stride + 1, (W + 2 * pad - ksize) / stride + 1, Cin, Cout, ksize);
+SST_API int sst_conv_wgrad(const float* x, const float* dy, float* slab, float* dw, const float* in_scale,
+                           const float* in_shift, const float* in_slope, float in_slope_const, int in_act, int B, int H,
+                           int W, int Cin, int Cout, int stride, int ksize, int accumulate, void* stream) {
+  return sst_conv_wgrad_grp(x, dy, slab, dw, in_scale, in_shift, in_slope, in_slope_const, in_act, B, H, W, Cin, Cout, stride, ksize,
+                            accumulate, 0, stream);
 }
 
 // jobs: HOST array of njobs <= 24 records {slab, dw, nchunk, k*k, Cout, Cin, accumulate, 0} (two pointers + six ints = 40 bytes):
@@ -1265,7 +1319,7 @@ SST_API int sst_wgrad_reduce_multi(const void* jobs, int njobs, void* stream) {
 // Weight gradients of `njobs` layers of IDENTICAL shape in one launch (+ one grouped slab reduce).
 // jobs: HOST array of WgJob {x, dy, slab, dw, in_scale, in_shift, in_slope, in_slope_const, in_act} (64 bytes each, device
 // pointers inside); it travels to the kernels as a by-value argument, at most WG_TAB_MAX = 40 jobs per call.
-// every job's slab holds sst_conv_wgrad_chunks(...) * k*k*Cout*Cin floats.
+// every job's slab holds sst_conv_wgrad_chunks2(..., njobs) * k*k*Cout*Cin floats.
 SST_API int sst_conv_wgrad_grouped(const void* jobs, int njobs, int B, int H, int W, int Cin, int Cout, int stride, int ksize,
                                    int accumulate, void* stream) {
   static_assert(sizeof(WgJob) == 64, "WgJob layout");
@@ -1273,44 +1327,26 @@ SST_API int sst_conv_wgrad_grouped(const void* jobs, int njobs, int B, int H, in
                   (ksize & 1) && ksize <= 9, "sst_conv_wgrad_grouped: bad argument (at most %d jobs per call)", WG_TAB_MAX);
   WgJobTab tab{};
   memcpy(tab.j, jobs, (size_t)njobs * sizeof(WgJob));
+  const WgradPlan pl = wgrad_plan(B, H, W, Cin, Cout, ksize, stride, njobs, true, ACT_NONE, true);      // BAND or GENERAL_*
   WgradArgs a;
   a.grouped = 1;
   a.x = a.dy = nullptr; a.slab = nullptr; a.in_scale = a.in_shift = a.in_slope = nullptr; a.in_slope_const = 0.f; a.in_act = 0;
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.stride = stride; a.KS = ksize; a.pad = ksize / 2;
-  a.Ho = (H + 2 * a.pad - ksize) / stride + 1;
-  a.Wo = (W + 2 * a.pad - ksize) / stride + 1;
-  const int64_t M = (int64_t)B * a.Ho * a.Wo;
-  SST_REQUIRE(M < (1ll << 31), "sst_conv_wgrad_grouped: too many pixels");
-  // With many layers in one grid the chip is full without fine pixel chunks: aim at ~target workgroups in total
-  // (fewer, longer chunks = less slab traffic).  Never more chunks than the per-layer slab was sized for.
-  int nchunk = sst_conv_wgrad_chunks(B, a.Ho, a.Wo, Cin, Cout, ksize);
-  {
-    int target = 2048;
-    if (const char* e = sst_env("SST_WGRAD_GROUP_WGS")) target = atoi(e);
-    const int nblk = ((Cout + 63) / 64) * ((Cin + 63) / 64);
-    int want = (target + ksize * ksize * nblk * njobs - 1) / (ksize * ksize * nblk * njobs);
-    if (want < 1) want = 1;
-    if (target > 0 && want < nchunk) {
-      const int64_t cpx = ((M + want - 1) / want + SUB - 1) / SUB * SUB;
-      nchunk = (int)((M + cpx - 1) / cpx);
-    }
-  }
-  a.nchunk = nchunk;
-  a.chunk_px = (int)(((M + nchunk - 1) / nchunk + SUB - 1) / SUB * SUB);
+  wgrad_shape_args(a, pl, B, H, W, Cin, Cout, ksize, stride);
+  SST_REQUIRE((int64_t)B * a.Ho * a.Wo < (1ll << 31), "sst_conv_wgrad_grouped: too many pixels");
+  a.nchunk = pl.nchunk;
   a.dbg = 0;
   const int KK = ksize * ksize;
-  dim3 grid((unsigned)nchunk * njobs, KK, ((Cout + 63) / 64) * ((Cin + 63) / 64));
-  const WgBandPlan pl = wgrad_band_plan(B, H, W, Cin, Cout, ksize, stride, njobs);
-  if (pl.R) {
-    const int rc = launch_wgrad_band(a, pl, njobs, sst_stream(stream), tab);
+  const dim3 grid((unsigned)pl.nchunk * njobs, KK, ((Cout + 63) / 64) * ((Cin + 63) / 64));
+  hipStream_t st = sst_stream(stream);
+  if (pl.kind == WgKind::BAND) {
+    const int rc = launch_wgrad_band(a, pl.band, njobs, st, tab);
     if (rc != SST_OK) return rc;
-    nchunk = pl.nchunk;
-  } else if ((Cin & 3) == 0 && (Cout & 3) == 0)
-    conv_wgrad_kernel<true><<<grid, CONV_NT, 0, sst_stream(stream)>>>(a, tab);
+  } else if (pl.kind == WgKind::GENERAL_VEC)
+    conv_wgrad_kernel<true><<<grid, CONV_NT, 0, st>>>(a, tab);
   else
-    conv_wgrad_kernel<false><<<grid, CONV_NT, 0, sst_stream(stream)>>>(a, tab);
+    conv_wgrad_kernel<false><<<grid, CONV_NT, 0, st>>>(a, tab);
   SST_LAUNCH_CHECK("conv_wgrad_kernel (grouped)");
-  launch_wgrad_reduce(nullptr, nullptr, nchunk, KK, Cout, Cin, accumulate, &tab, njobs, sst_stream(stream));
+  launch_wgrad_reduce(nullptr, nullptr, pl.nchunk, KK, Cout, Cin, accumulate, &tab, njobs, st);
   SST_LAUNCH_CHECK("wgrad_reduce_kernel (grouped)");
   return SST_OK;
 }

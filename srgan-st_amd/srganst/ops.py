@@ -58,6 +58,16 @@ def _prof_end(e0, name, flops):
         PROFILE.append((name, flops, e0, e1))
 
 
+def _launch(fn, args, what, flops, name_fn, keep):
+    """One conv launch fn(*args, stream): checked, timed into PROFILE and registered in TRACE (with a closure that re-issues the
+    identical launch and holds `keep` alive) under name_fn(), which is evaluated only when one of the two is on."""
+    e0 = _prof_begin()
+    check(fn(*args, stream_ptr()), what)
+    name = name_fn() if (PROFILE is not None or TRACE is not None) else ""
+    _prof_end(e0, name, flops)
+    _trace(name, flops, lambda: fn(*args, stream_ptr()), *keep)
+
+
 def _conv_name(B, H, W, cin, cout, ksize, stride, out_mode=0, fused_in=0):
     return _abi.lib().sst_conv_kernel_name(B, H, W, cin, cout, ksize, stride, int(out_mode) & 0xff, int(fused_in)).decode()
 
@@ -123,15 +133,11 @@ def conv_fwd(x, wp, cout, ksize=3, stride=1, bias=None, in_scale=None, in_shift=
         mt = _abi.lib().sst_conv_stat_tiles(B, H, W, cin, cout, ksize, stride)
         stats = _f32(mt, 2, cout, like=x)
         cnt = _f32(mt, like=x)
-    e0 = _prof_begin()
     args = (ptr(x), ptr(wp), ptr(y), ptr(y_pre), ptr(bias), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const),
             int(in_act), ptr(residual), ptr(stats), ptr(cnt), int(out_mode), B, H, W, cin, cout, ksize, stride)
-    check(_abi.lib().sst_conv_fwd(*args, stream_ptr()), "sst_conv_fwd")
-    flops = 2.0 * B * ho * wo * cout * cin * ksize * ksize
-    name = _conv_name(B, H, W, cin, cout, ksize, stride, out_mode) if (PROFILE is not None or TRACE is not None) else ""
-    _prof_end(e0, name, flops)
-    _trace(name, flops, lambda: _abi.lib().sst_conv_fwd(*args, stream_ptr()),
-           x, wp, y, y_pre, bias, in_scale, in_shift, in_slope, residual, stats, cnt)
+    _launch(_abi.lib().sst_conv_fwd, args, "sst_conv_fwd", 2.0 * B * ho * wo * cout * cin * ksize * ksize,
+            lambda: _conv_name(B, H, W, cin, cout, ksize, stride, out_mode),
+            (x, wp, y, y_pre, bias, in_scale, in_shift, in_slope, residual, stats, cnt))
     return y, y_pre, stats, cnt
 
 
@@ -166,19 +172,16 @@ def _conv_pipe(x, wp, y, cout, ksize, stride, bias=None, in_scale=None, in_shift
     e = epi or {}
     if epi is not None:
         partial = _f32(L.sst_conv_pipe_stat_tiles(*shp), 3, cout, like=x)
+    ho, wo = conv_out_hw(H, W, ksize, stride)
+    flops = 2.0 * B * ho * wo * cout * cin * ksize * ksize
     if CONV_NS and L.sst_conv_ns_supported(*shp, int(out_mode)):
         # the N-split form (csrc/conv_nsplit.hip): same tiling, statistics rows and packed weights, no split-K workspace
         nargs = (ptr(x), ptr(wp), ptr(y), ptr(bias), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const), int(in_act),
                  ptr(stats), ptr(cnt), ptr(e.get("y")), ptr(e.get("scale")), ptr(e.get("shift")), ptr(e.get("slope")),
                  float(e.get("slope_const", 0.0)), int(e.get("act", 0)), ptr(partial), *shp, int(out_mode), int(grp))
-        e0 = _prof_begin()
-        check(L.sst_conv_ns_fwd(*nargs, stream_ptr()), "sst_conv_ns_fwd")
-        ho, wo = conv_out_hw(H, W, ksize, stride)
-        flops = 2.0 * B * ho * wo * cout * cin * ksize * ksize
-        name = f"conv_ns_kernel<{stride}, {L.sst_conv_ns_supported(*shp, int(out_mode))}>" if (PROFILE is not None or TRACE is not None) else ""
-        _prof_end(e0, name, flops)
-        _trace(name, flops, lambda: L.sst_conv_ns_fwd(*nargs, stream_ptr()),
-               x, wp, y, bias, in_scale, in_shift, in_slope, stats, cnt, partial, *[v for v in e.values() if torch.is_tensor(v)])
+        _launch(L.sst_conv_ns_fwd, nargs, "sst_conv_ns_fwd", flops,
+                lambda: f"conv_ns_kernel<{stride}, {L.sst_conv_ns_supported(*shp, int(out_mode))}>",
+                (x, wp, y, bias, in_scale, in_shift, in_slope, stats, cnt, partial, *[v for v in e.values() if torch.is_tensor(v)]))
         return y, stats, cnt, partial
     assert out_mode == OUT_NHWC
     nws = L.sst_conv_pipe_ws_floats(*shp)
@@ -186,27 +189,25 @@ def _conv_pipe(x, wp, y, cout, ksize, stride, bias=None, in_scale=None, in_shift
     args = (ptr(x), ptr(wp), ptr(y), ptr(bias), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const), int(in_act),
             ptr(stats), ptr(cnt), ptr(e.get("y")), ptr(e.get("scale")), ptr(e.get("shift")), ptr(e.get("slope")),
             float(e.get("slope_const", 0.0)), int(e.get("act", 0)), ptr(partial), ptr(ws), *shp, int(grp))
-    e0 = _prof_begin()
-    check(L.sst_conv_pipe_fwd_grp(*args, stream_ptr()), "sst_conv_pipe_fwd")
-    ho, wo = conv_out_hw(H, W, ksize, stride)
-    flops = 2.0 * B * ho * wo * cout * cin * ksize * ksize
-    name = f"conv_pipe_kernel<{stride}, {L.sst_conv_pipe_supported(*shp)}, 0>" if (PROFILE is not None or TRACE is not None) else ""
-    _prof_end(e0, name, flops)
-    _trace(name, flops, lambda: L.sst_conv_pipe_fwd_grp(*args, stream_ptr()),
-           x, wp, y, bias, in_scale, in_shift, in_slope, stats, cnt, partial, ws, *[v for v in e.values() if torch.is_tensor(v)])
+    _launch(L.sst_conv_pipe_fwd_grp, args, "sst_conv_pipe_fwd", flops, lambda: f"conv_pipe_kernel<{stride}, {L.sst_conv_pipe_supported(*shp)}, 0>",
+            (x, wp, y, bias, in_scale, in_shift, in_slope, stats, cnt, partial, ws, *[v for v in e.values() if torch.is_tensor(v)]))
     return y, stats, cnt, partial
 
 
 _ONES = {}
 
 
+def _ones(x, cin):
+    key = (x.device, cin)
+    if key not in _ONES:
+        _ONES[key] = torch.ones(cin, device=x.device, dtype=torch.float32)
+    return _ONES[key]
+
+
 def conv_fwd_resin(x, y2, bn_scale, bn_shift, wp, cout, ksize=3, bias=None, want_stats=False):
     """y = conv(h) with h = x + y2*bn_scale + bn_shift formed while staging (and returned): (y, h, stats|None, cnt|None)."""
     B, H, W, cin = x.shape
-    key = (x.device, cin)
-    ones = _ONES.get(key)
-    if ones is None:
-        ones = _ONES[key] = torch.ones(cin, device=x.device, dtype=torch.float32)
+    ones = _ones(x, cin)
     y = _f32(B, H, W, cout, like=x)
     h = torch.empty_like(x)
     stats = cnt = None
@@ -216,13 +217,8 @@ def conv_fwd_resin(x, y2, bn_scale, bn_shift, wp, cout, ksize=3, bias=None, want
         cnt = _f32(mt, like=x)
     args = (ptr(x), ptr(y2), ptr(ones), ptr(bn_scale), ptr(bn_shift), ptr(h), ptr(wp), ptr(y), ptr(bias), ptr(stats), ptr(cnt),
             B, H, W, cin, cout, ksize)
-    e0 = _prof_begin()
-    check(_abi.lib().sst_conv_fwd_resin(*args, stream_ptr()), "sst_conv_fwd_resin")
-    flops = 2.0 * B * H * W * cout * cin * ksize * ksize
-    name = _conv_name(B, H, W, cin, cout, ksize, 1, 0, 1) if (PROFILE is not None or TRACE is not None) else ""
-    _prof_end(e0, name, flops)
-    _trace(name, flops, lambda: _abi.lib().sst_conv_fwd_resin(*args, stream_ptr()),
-           x, y2, ones, bn_scale, bn_shift, h, wp, y, bias, stats, cnt)
+    _launch(_abi.lib().sst_conv_fwd_resin, args, "sst_conv_fwd_resin", 2.0 * B * H * W * cout * cin * ksize * ksize,
+            lambda: _conv_name(B, H, W, cin, cout, ksize, 1, 0, 1), (x, y2, ones, bn_scale, bn_shift, h, wp, y, bias, stats, cnt))
     return y, h, stats, cnt
 
 
@@ -242,25 +238,16 @@ def conv_fwd_acc(x, wp, cout, ksize=3, in2=None, bias=None, in_slope=None, in_sl
     B, H, W, cin = x.shape
     y = _f32(B, H, W, cout, like=x)
     h = torch.empty_like(x) if in2 is not None else None
-    ones = None
-    if in2 is not None:
-        key = (x.device, cin)
-        ones = _ONES.get(key)
-        if ones is None:
-            ones = _ONES[key] = torch.ones(cin, device=x.device, dtype=torch.float32)
+    ones = _ones(x, cin) if in2 is not None else None
     g, bta = in_bn if in_bn is not None else (None, None)
     om, orr, osc, osh = out_stats if out_stats is not None else (None, None, None, None)
     rm, rv = run_stats if run_stats is not None else (None, None)
     args = (ptr(x), ptr(in2), ptr(h), ptr(ones), ptr(wp), ptr(y), ptr(bias), ptr(in_slope), float(in_slope_const), int(in_act),
             _dptr(in_acc), ptr(g), ptr(bta), float(n), float(BN_EPS), float(BN_MOMENTUM), ptr(om), ptr(orr), ptr(osc), ptr(osh),
             ptr(rm), ptr(rv), _dptr(st_acc), ACC_NREP, B, H, W, cin, cout, ksize)
-    e0 = _prof_begin()
-    check(_abi.lib().sst_conv_fwd_acc(*args, stream_ptr()), "sst_conv_fwd_acc")
-    flops = 2.0 * B * H * W * cout * cin * ksize * ksize
-    name = _conv_name(B, H, W, cin, cout, ksize, 1, 0, 1) if (PROFILE is not None or TRACE is not None) else ""
-    _prof_end(e0, name, flops)
-    _trace(name, flops, lambda: _abi.lib().sst_conv_fwd_acc(*args, stream_ptr()),
-           x, in2, h, ones, wp, y, bias, in_slope, in_acc, g, bta, om, orr, osc, osh, rm, rv, st_acc)
+    _launch(_abi.lib().sst_conv_fwd_acc, args, "sst_conv_fwd_acc", 2.0 * B * H * W * cout * cin * ksize * ksize,
+            lambda: _conv_name(B, H, W, cin, cout, ksize, 1, 0, 1),
+            (x, in2, h, ones, wp, y, bias, in_slope, in_acc, g, bta, om, orr, osc, osh, rm, rv, st_acc))
     return y, h
 
 
@@ -277,14 +264,10 @@ def conv_dgrad_fused_acc(g, wd, cout, ksize=3, y2=None, in_scale=None, in_shift=
             ptr(residual), ptr(epi_y), ptr(epi_scale), ptr(epi_shift), ptr(epi_slope), float(epi_slope_const), int(epi_act),
             _dptr(bw_in_acc), ptr(mean), ptr(rstd), ptr(gamma), float(n), ptr(dgamma), ptr(dbeta), ptr(dslope), _dptr(bw_st_acc),
             ACC_NREP, B, H, W, cin, cout, ksize)
-    e0 = _prof_begin()
-    check(_abi.lib().sst_conv_dgrad_fused_acc(*args, stream_ptr()), "sst_conv_dgrad_fused_acc")
-    flops = 2.0 * B * H * W * cout * cin * ksize * ksize
-    name = _conv_name(B, H, W, cin, cout, ksize, 1, 0, 1) if (PROFILE is not None or TRACE is not None) else ""
-    _prof_end(e0, name, flops)
-    _trace(name, flops, lambda: _abi.lib().sst_conv_dgrad_fused_acc(*args, stream_ptr()),
-           g, y2, in_scale, in_shift, in_slope, dy, wd, out, residual, epi_y, epi_scale, epi_shift, epi_slope, bw_in_acc, mean, rstd, gamma,
-           dgamma, dbeta, dslope, bw_st_acc)
+    _launch(_abi.lib().sst_conv_dgrad_fused_acc, args, "sst_conv_dgrad_fused_acc", 2.0 * B * H * W * cout * cin * ksize * ksize,
+            lambda: _conv_name(B, H, W, cin, cout, ksize, 1, 0, 1),
+            (g, y2, in_scale, in_shift, in_slope, dy, wd, out, residual, epi_y, epi_scale, epi_shift, epi_slope, bw_in_acc, mean, rstd, gamma,
+             dgamma, dbeta, dslope, bw_st_acc))
     return out, dy
 
 
@@ -318,7 +301,6 @@ def conv_wgrad(x, dy, dw_out, ksize=3, stride=1, in_scale=None, in_shift=None, i
     assert tuple(dy.shape) == (B, ho, wo, cout) and tuple(dw_out.shape) == (cout, cin, ksize, ksize)
     nch = _abi.lib().sst_conv_wgrad_chunks2(B, H, W, cin, cout, ksize, stride, 1)
     slab = _f32(nch * ksize * ksize * cout * cin, like=x)
-    e0 = _prof_begin()
     pend = 0
     if defer_reduce is not None and PROFILE is None and TRACE is None:
         pend = _abi.lib().sst_conv_wgrad_pending_reduce(B, H, W, cin, cout, ksize, stride, int(in_scale is not None), int(in_act))
@@ -327,15 +309,12 @@ def conv_wgrad(x, dy, dw_out, ksize=3, stride=1, in_scale=None, in_shift=None, i
             defer_reduce.append((slab, dw_out, pend, ksize * ksize, cout, cin, int(bool(accumulate))))
     args = (ptr(x), ptr(dy), ptr(slab), ptr(dw_out), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const),
             int(in_act), B, H, W, cin, cout, stride, ksize, int(bool(accumulate)) | (4 if pend else 0), int(grp))
-    check(_abi.lib().sst_conv_wgrad_grp(*args, stream_ptr()), "sst_conv_wgrad")
-    flops = 2.0 * B * ho * wo * cout * cin * ksize * ksize
-    name = ""
-    if PROFILE is not None or TRACE is not None:
-        name = _wgrad_name(B, H, W, cin, cout, ksize, stride, 1)
-        name += "+c3m_reduce_kernel" if name == "wgrad_k3c3_mfma_kernel" else "+wgrad_reduce_kernel"
-    _prof_end(e0, name, flops)
-    _trace(name, flops, lambda: _abi.lib().sst_conv_wgrad_grp(*args, stream_ptr()),
-           x, dy, slab, dw_out, in_scale, in_shift, in_slope)
+
+    def name():
+        n = _wgrad_name(B, H, W, cin, cout, ksize, stride, 1)
+        return n + ("+c3m_reduce_kernel" if n == "wgrad_k3c3_mfma_kernel" else "+wgrad_reduce_kernel")
+    _launch(_abi.lib().sst_conv_wgrad_grp, args, "sst_conv_wgrad", 2.0 * B * ho * wo * cout * cin * ksize * ksize, name,
+            (x, dy, slab, dw_out, in_scale, in_shift, in_slope))
     return dw_out
 
 
@@ -566,20 +545,12 @@ def conv_s2_dgrad(dy, wp, H, W, cin, epi=None, grp=0):
                 ptr(e.get("scale")) if partial is not None else None, ptr(e.get("shift")) if partial is not None else None,
                 ptr(e.get("slope")) if partial is not None else None, float(e.get("slope_const", 0.0)), int(e.get("act", 0)),
                 ptr(partial), B, H, W, cin, cout, int(grp) if partial is not None else 0)
-        e0 = _prof_begin()
-        check(L.sst_conv_s2_dgrad_pipe_bwdstats_grp(*args, stream_ptr()), "sst_conv_s2_dgrad_pipe")
-        if PROFILE is not None or TRACE is not None:
-            name, flops = f"conv_pipe_kernel<1, {L.sst_conv_s2_dgrad_pipe_supported(B, H, W, cin, cout)}, 1>", 2.0 * B * ho * wo * cout * cin * 9
-            _prof_end(e0, name, flops)
-            _trace(name, flops, lambda: L.sst_conv_s2_dgrad_pipe_bwdstats_grp(*args, stream_ptr()), dy, wp, dx, ws, partial,
-                   e.get("y"), e.get("scale"), e.get("shift"), e.get("slope"))
+        _launch(L.sst_conv_s2_dgrad_pipe_bwdstats_grp, args, "sst_conv_s2_dgrad_pipe", 2.0 * B * ho * wo * cout * cin * 9,
+                lambda: f"conv_pipe_kernel<1, {L.sst_conv_s2_dgrad_pipe_supported(B, H, W, cin, cout)}, 1>",
+                (dy, wp, dx, ws, partial, e.get("y"), e.get("scale"), e.get("shift"), e.get("slope")))
         return (dx, partial) if epi is not None else dx
-    e0 = _prof_begin()
-    check(_abi.lib().sst_conv_s2_dgrad(ptr(dy), ptr(wp), ptr(dx), B, H, W, cin, cout, stream_ptr()), "sst_conv_s2_dgrad")
-    if PROFILE is not None or TRACE is not None:
-        name, flops = _abi.lib().sst_conv_s2_dgrad_kernel_name(B, H, W, cin, cout, 0).decode(), 2.0 * B * ho * wo * cout * cin * 9
-        _prof_end(e0, name, flops)
-        _trace(name, flops, lambda: _abi.lib().sst_conv_s2_dgrad(ptr(dy), ptr(wp), ptr(dx), B, H, W, cin, cout, stream_ptr()), dy, wp, dx)
+    _launch(L.sst_conv_s2_dgrad, (ptr(dy), ptr(wp), ptr(dx), B, H, W, cin, cout), "sst_conv_s2_dgrad", 2.0 * B * ho * wo * cout * cin * 9,
+            lambda: L.sst_conv_s2_dgrad_kernel_name(B, H, W, cin, cout, 0).decode(), (dy, wp, dx))
     return (dx, None) if epi is not None else dx
 
 
@@ -594,13 +565,9 @@ def conv_s2_dgrad_fused(g, y2, wp, H, W, cin, cA=None, cB=None, cC=None, in_scal
     args = (ptr(g), ptr(y2), ptr(cA), ptr(cB), ptr(cC), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const), int(in_act),
             ptr(dy), ptr(wp), ptr(dx), ptr(epi_y), ptr(epi_scale), ptr(epi_shift), ptr(epi_slope), float(epi_slope_const), int(epi_act),
             ptr(partial), B, H, W, cin, cout)
-    e0 = _prof_begin()
-    check(_abi.lib().sst_conv_s2_dgrad_fused(*args, stream_ptr()), "sst_conv_s2_dgrad_fused")
-    flops = 2.0 * B * ho * wo * cout * cin * 9
-    name = _abi.lib().sst_conv_s2_dgrad_kernel_name(B, H, W, cin, cout, 1).decode() if (PROFILE is not None or TRACE is not None) else ""
-    _prof_end(e0, name, flops)
-    _trace(name, flops, lambda: _abi.lib().sst_conv_s2_dgrad_fused(*args, stream_ptr()),
-           g, y2, cA, cB, cC, in_scale, in_shift, in_slope, dy, wp, dx, epi_y, epi_scale, epi_shift, epi_slope, partial)
+    _launch(_abi.lib().sst_conv_s2_dgrad_fused, args, "sst_conv_s2_dgrad_fused", 2.0 * B * ho * wo * cout * cin * 9,
+            lambda: _abi.lib().sst_conv_s2_dgrad_kernel_name(B, H, W, cin, cout, 1).decode(),
+            (g, y2, cA, cB, cC, in_scale, in_shift, in_slope, dy, wp, dx, epi_y, epi_scale, epi_shift, epi_slope, partial))
     return dx, dy, partial
 
 
@@ -936,13 +903,8 @@ def conv_dgrad_bwdstats(dy, wd, cout, ksize, epi_y, residual=None, epi_scale=Non
     partial = _f32(mt, 3, cout, like=dy)
     args = (ptr(dy), ptr(wd), ptr(g), ptr(residual), ptr(epi_y), ptr(epi_scale), ptr(epi_shift), ptr(epi_slope),
             float(epi_slope_const), int(epi_act), ptr(partial), B, H, W, cin, cout, ksize)
-    e0 = _prof_begin()
-    check(_abi.lib().sst_conv_dgrad_bwdstats(*args, stream_ptr()), "sst_conv_dgrad_bwdstats")
-    flops = 2.0 * B * H * W * cout * cin * ksize * ksize
-    name = _conv_name(B, H, W, cin, cout, ksize, 1) if (PROFILE is not None or TRACE is not None) else ""
-    _prof_end(e0, name, flops)
-    _trace(name, flops, lambda: _abi.lib().sst_conv_dgrad_bwdstats(*args, stream_ptr()),
-           dy, wd, g, residual, epi_y, epi_scale, epi_shift, epi_slope, partial)
+    _launch(_abi.lib().sst_conv_dgrad_bwdstats, args, "sst_conv_dgrad_bwdstats", 2.0 * B * H * W * cout * cin * ksize * ksize,
+            lambda: _conv_name(B, H, W, cin, cout, ksize, 1), (dy, wd, g, residual, epi_y, epi_scale, epi_shift, epi_slope, partial))
     return g, partial
 
 
@@ -969,13 +931,9 @@ def conv_dgrad_fused(g, y2, wd, cout, ksize, cA=None, cB=None, cC=None, in_scale
     args = (ptr(g), ptr(y2), ptr(cA), ptr(cB), ptr(cC), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const),
             int(in_act), ptr(dy), ptr(wd), ptr(out), ptr(residual), ptr(epi_y), ptr(epi_scale), ptr(epi_shift), ptr(epi_slope),
             float(epi_slope_const), int(epi_act), ptr(partial), B, H, W, cin, cout, ksize)
-    e0 = _prof_begin()
-    check(_abi.lib().sst_conv_dgrad_fused(*args, stream_ptr()), "sst_conv_dgrad_fused")
-    flops = 2.0 * B * H * W * cout * cin * ksize * ksize
-    name = _conv_name(B, H, W, cin, cout, ksize, 1, 0, 1) if (PROFILE is not None or TRACE is not None) else ""
-    _prof_end(e0, name, flops)
-    _trace(name, flops, lambda: _abi.lib().sst_conv_dgrad_fused(*args, stream_ptr()),
-           g, y2, cA, cB, cC, in_scale, in_shift, in_slope, dy, wd, out, residual, epi_y, epi_scale, epi_shift, epi_slope, partial)
+    _launch(_abi.lib().sst_conv_dgrad_fused, args, "sst_conv_dgrad_fused", 2.0 * B * H * W * cout * cin * ksize * ksize,
+            lambda: _conv_name(B, H, W, cin, cout, ksize, 1, 0, 1),
+            (g, y2, cA, cB, cC, in_scale, in_shift, in_slope, dy, wd, out, residual, epi_y, epi_scale, epi_shift, epi_slope, partial))
     return out, dy, partial
 
 
@@ -1094,14 +1052,9 @@ class WgradGroup:
             import ctypes
             flatw = [w for r in rows for w in r]
             arr = (ctypes.c_longlong * len(flatw))(*flatw)
-            e0 = _prof_begin()
             args = (ctypes.cast(arr, ctypes.c_void_p), len(js), B, H, W, cin, cout, s, k, 0)
-            check(_abi.lib().sst_conv_wgrad_grouped(*args, stream_ptr()), "sst_conv_wgrad_grouped")
-            flops = 2.0 * B * dys[1] * dys[2] * cout * cin * k * k * len(js)
-            name = (_wgrad_name(B, H, W, cin, cout, k, s, len(js)) + "(grouped)+wgrad_reduce_kernel") if (PROFILE is not None or TRACE is not None) else ""
-            _prof_end(e0, name, flops)
-            _trace(name, flops,
-                   lambda args=args: _abi.lib().sst_conv_wgrad_grouped(*args, stream_ptr()), js, slab, arr)
+            _launch(_abi.lib().sst_conv_wgrad_grouped, args, "sst_conv_wgrad_grouped", 2.0 * B * dys[1] * dys[2] * cout * cin * k * k * len(js),
+                    lambda shp=(B, H, W, cin, cout, k, s, len(js)): _wgrad_name(*shp) + "(grouped)+wgrad_reduce_kernel", (js, slab, arr))
         self.jobs = []
 
 

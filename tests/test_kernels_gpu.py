@@ -726,3 +726,57 @@ def test_multi_pack_9x9_modes_equal_standalone_packers():
     assert torch.equal(out[2], t3)
     assert torch.equal(out[3], c3(w3, 1))
     assert torch.equal(out[0], ops.pack_conv(wt, 0)) and torch.equal(out[4], ops.pack_conv(wt, 1))
+
+
+@pytest.mark.parametrize("case", [("TILE", (1, 4, 16, 32, 32, 2), None, False, "conv_wgrad_tile_kernel<2, 2, 8, 8>"),
+                                  ("TILE", (1, 4, 8, 32, 64, 1), ("SST_WGRAD_S1T", "1"), False, "conv_wgrad_tile_kernel<1, 4, 8, 8>"),
+                                  ("BAND", (2, 6, 8, 64, 64, 1), ("SST_WGRAD_BAND", "1"), False, "conv_wgrad_band_kernel<7>"),
+                                  ("K3C3_MFMA", (1, 1, 32, 3, 64, 1), None, False, "wgrad_k3c3_mfma_kernel"),
+                                  ("K3C3", (2, 13, 9, 3, 64, 1), None, False, "wgrad_k3c3_kernel"),
+                                  ("GENERAL_SCALAR", (2, 13, 9, 3, 64, 1), None, True, None),         # (3 input channels: the scalar instance)
+                                  ("GENERAL_VEC", (1, 5, 7, 8, 12, 1), None, False, "conv_wgrad_kernel<true>"),
+                                  ("GENERAL_SCALAR", (1, 5, 7, 6, 10, 2), None, False, "conv_wgrad_kernel<false>")],
+                         ids=lambda c: f"{c[0]}-{'x'.join(map(str, c[1]))}{'-affine' if c[3] else ''}")
+def test_conv_wgrad_slab_is_what_the_plan_says(ops, case, monkeypatch):
+    """Every kind of weight-gradient launch at the smallest shape that reaches it, called through sst_conv_wgrad_grp itself with a slab
+    of exactly sst_conv_wgrad_chunks2 chunks and dW, each between two 4096-float sentinel bands: the bands stay untouched, dW meets the
+    fp64 conv2d weight gradient, and with accumulate bit 2 it does so after one wgrad_reduce_flush over sst_conv_wgrad_pending_reduce
+    chunks (0: the launch wrote dW itself, no flush).  The affine row is the route a plain kernel name cannot describe: the input
+    affine sends the 3-channel shape to the general kernel."""
+    kind, (B, H, W, Cin, Cout, stride), switch, affine, plain_name = case
+    if switch:
+        monkeypatch.setenv(*switch)
+    L = ops._abi.lib()
+    shp = (B, H, W, Cin, Cout, 3, stride)
+    if plain_name:
+        assert L.sst_conv_wgrad_kernel_name(*shp, 1).decode() == plain_name
+    g = torch.Generator().manual_seed(107)
+    ho, wo = ops.conv_out_hw(H, W, 3, stride)
+    x = torch.randn(B, Cin, H, W, generator=g)
+    dy = torch.randn(B, Cout, ho, wo, generator=g)
+    sc, sh = torch.rand(Cin, generator=g) + 0.5, torch.randn(Cin, generator=g) * 0.3
+    w = torch.zeros(Cout, Cin, 3, 3, dtype=torch.float64, requires_grad=True)
+    xin = F.leaky_relu(x.double() * sc.double().view(1, -1, 1, 1) + sh.double().view(1, -1, 1, 1), 0.2) if affine else x.double()
+    F.conv2d(xin, w, None, stride, 1).backward(dy.double())
+    xd, dyd, scd, shd = nhwc(x).cuda(), nhwc(dy).cuda(), sc.cuda(), sh.cuda()
+    BAND, SENT = 4096, -7.25
+    nch, per = L.sst_conv_wgrad_chunks2(*shp, 1), 9 * Cout * Cin
+    pend = L.sst_conv_wgrad_pending_reduce(*shp, int(affine), ops.ACT_SLOPE if affine else ops.ACT_NONE)
+    print(f"{kind} {shp}: chunks2 {nch}, pending_reduce {pend}")
+    assert 0 <= pend <= nch
+    for bit in (0, 4):
+        slab_buf = torch.full((2 * BAND + nch * per,), SENT, device="cuda")
+        dw_buf = torch.full((2 * BAND + per,), SENT, device="cuda")
+        slab, dw = slab_buf[BAND:BAND + nch * per], dw_buf[BAND:BAND + per].view(Cout, Cin, 3, 3)
+        ops._abi.check(L.sst_conv_wgrad_grp(xd.data_ptr(), dyd.data_ptr(), slab.data_ptr(), dw.data_ptr(), scd.data_ptr() if affine else None,
+                                            shd.data_ptr() if affine else None, None, 0.2 if affine else 0.0,
+                                            ops.ACT_SLOPE if affine else ops.ACT_NONE, B, H, W, Cin, Cout, stride, 3, bit, 0,
+                                            ops._abi.stream_ptr()), "sst_conv_wgrad_grp")
+        if bit and pend:
+            ops.wgrad_reduce_flush([(slab, dw, pend, 9, Cout, Cin, 0)])
+        torch.cuda.synchronize()
+        for buf in (slab_buf, dw_buf):
+            assert bool((buf[:BAND] == SENT).all()) and bool((buf[-BAND:] == SENT).all()), (kind, bit)
+        err = rel_err(dw.cpu(), w.grad)
+        print(f"  accumulate bit 2 {'set' if bit else 'clear'}: rel err {err:.2e}")
+        assert err < TOL, (kind, bit, err)
