@@ -10,31 +10,36 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from ._state import KeptPass, state
 from .ops import ACT_SLOPE
 
 LRELU = 0.2
+
+
+def param_dict(module):
+    """(parameter names in the reference's order, {name: detached parameter}): what the functions below take as `p`."""
+    names = [n for n, _ in module.named_parameters()]
+    return names, dict(zip(names, [t.detach() for t in module.parameters()]))
+
+
 # (conv index, bn index or None, stride) in module.features                           model.py:30-59
 PLAN = [(0, None, 1), (2, 3, 2), (5, 6, 1), (8, 9, 2), (11, 12, 1), (14, 15, 2), (17, 18, 1), (20, 21, 2)]
 
 
 def _packs(module, p, with_dgrad, counter_add=0):
     """(forward packs by name, stride-1 data-gradient packs by name, stride-2 data-gradient packs by name) - the last two None
-    without with_dgrad.  One multi-tensor launch + one launch per stride-2 layer.
-
-    Re-use: the discriminator runs up to three forward and three backward passes between two updates of its weights
-    (train.py:125-161: D(sr) in the generator step, D(gt) and D(sr) in its own step).  An owner that controls those updates
-    (engine.TrainEngine) sets module._packs_managed and clears module._packs_fresh after every optimizer step; while the flag
-    is set (and no parameter was rebound or modified through torch, see _version) the packed buffers are handed out again
-    without a launch.  Without an owner every call packs, as before.
+    without with_dgrad.  One multi-tensor launch + one launch per stride-2 layer, or none: while the module has an owner and its
+    packs are fresh they are handed out again (HipState.owner).
     counter_add > 0 (the owner's call at the head of an iteration, which always packs): the BatchNorm batch counters' add for the
     iteration's passes rides in the pack launch."""
-    cache = module.__dict__.setdefault("_hip_cache", {})
+    hs = state(module)
+    cache = hs.cache
     names = [f"features.{ci}.weight" for ci, _, s in PLAN]
     n1 = [f"features.{ci}.weight" for ci, _, s in PLAN if s == 1]
     n2 = [f"features.{ci}.weight" for ci, _, s in PLAN if s == 2]
     sig = tuple((p[n].data_ptr(), p[n]._version) for n in names)
     st = cache.get("pack_state")
-    if (module.__dict__.get("_packs_managed") and module.__dict__.get("_packs_fresh") and st is not None and st["sig"] == sig
+    if (hs.owner is not None and hs.packs_fresh and st is not None and st["sig"] == sig
             and (st["wd"] is not None or not with_dgrad)):
         assert not counter_add, "the packs are fresh: nothing to ride along with"
         return st["wp"], st["wd"], st["ws2"]
@@ -50,7 +55,7 @@ def _packs(module, p, with_dgrad, counter_add=0):
         for n in n2:
             cache[("s2", n)] = ws2[n]
     cache["pack_state"] = {"sig": sig, "wp": wp, "wd": wd, "ws2": ws2}
-    module.__dict__["_packs_fresh"] = True
+    hs.packs_fresh = True
     return wp, wd, ws2
 
 
@@ -135,7 +140,7 @@ def forward(module, x, p, training, need_grad=False, arena=None):
             raise NotImplementedError("batched passes are a train-mode schedule (eval mode has no per-pass statistics to keep apart)")
     sv = {"layers": [], "groups": groups, "gB": gB}
     wp, sv["wd"], sv["ws2"] = _packs(module, p, need_grad)
-    if training and not module.__dict__.get("_counters_external"):
+    if training and not state(module).counters_external:
         ops.flatten_bn_counters(module).add_(groups)
     if groups > 1:
         _, c3, hh, ww = x[0].shape
@@ -193,7 +198,7 @@ def replay_running_stats(module, p, sv):
     the discriminator step's D(sr.detach()) (train.py:158), which repeats the generator step's D(sr) (train.py:136) before any
     weight has changed."""
     groups = sv.get("groups", 1)
-    if not module.__dict__.get("_counters_external"):
+    if not state(module).counters_external:
         ops.flatten_bn_counters(module).add_(groups)
     for rec in sv["layers"]:
         if rec["bi"] is None:
@@ -204,22 +209,20 @@ def replay_running_stats(module, p, sv):
 
 
 def _grad_views(module, p, need_param_grads):
-    """Per-parameter gradient views of ONE flat buffer + whether this pass accumulates into it.
-    Two backward passes per D step (D(gt) and D(sr), train.py:155-161): when the step engine opened an accumulation scope
-    (module._grad_accum), the second pass ADDS into the first pass's flat buffer with the kernels' accumulate flag and hands
-    autograd nothing - p.grad stays a view of ONE flat buffer (flat Adam, single RCCL message) and autograd's own
-    out-of-place sum of two 94 MB gradient sets disappears."""
+    """Per-parameter gradient views of ONE flat buffer + whether this pass accumulates into it: the second and later passes
+    inside an accumulation scope do (HipState.grad_accum)."""
     names = list(p.keys())
-    scope = module.__dict__.get("_grad_accum") if need_param_grads else None
-    acc = scope is not None and scope.get("flat") is not None
+    hs = state(module)
+    scope = hs.grad_accum if need_param_grads else None
+    acc = scope is not None and scope.flat is not None
     if acc:
         plist = [p[n] for n in names]
         offs, _ = ops.flat_layout(plist)
-        views = {n: scope["flat"][o:o + t.numel()].view(t.shape) for n, t, o in zip(names, plist, offs)}
+        views = {n: scope.flat[o:o + t.numel()].view(t.shape) for n, t, o in zip(names, plist, offs)}
     else:
         views = ops.flat_grads(module, names, [p[n] for n in names]) if need_param_grads else {}
         if scope is not None:
-            scope["flat"] = module.__dict__["_flat_grads"][-1]
+            scope.flat = hs.flat_grads[-1]
     return views, acc
 
 
@@ -341,21 +344,20 @@ def backward(module, p, sv, dout, need_param_grads, need_dx):
 class DiscriminatorFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, module, grad_mode, *params):
-        names = [n for n, _ in module.named_parameters()]
-        p = dict(zip(names, [t.detach() for t in params]))
+        names, p = param_dict(module)                # (`params` are module.parameters(), handed in for autograd to see them)
         need_param = grad_mode and any(ctx.needs_input_grad[3:])
         need_dx = grad_mode and ctx.needs_input_grad[0]
         need_grad = need_param or need_dx
         if need_grad and not module.training:
             raise NotImplementedError("Discriminator backward in eval() mode is not on the reference's path (train.py:110)")
-        keep = module.__dict__.get("_keep_pass") and need_grad and module.training
-        req = module.__dict__.get("_arena_request") if keep else None          # (slots, slot): write this pass into a fresh PassArena
+        hs = state(module)
+        keep = hs.keep_pass and need_grad and module.training
+        req = hs.arena_request if keep else None          # (slots, slot): write this pass into a fresh PassArena
         arena = (PassArena(req[0]), req[1]) if req is not None else None
         out, sv = forward(module, x, p, module.training, need_grad, arena=arena)
         if keep:
             # the step engine re-uses this pass (replay_running_stats): input identity, logits, saved activations
-            module.__dict__["_last_pass"] = {"x_ptr": x.data_ptr(), "x_shape": tuple(x.shape), "out": out, "sv": sv, "p": p,
-                                             "arena": arena[0] if arena is not None else None}
+            hs.last_pass = KeptPass(x.data_ptr(), tuple(x.shape), out, sv, p, arena[0] if arena is not None else None)
         if need_grad:
             ctx.module, ctx.sv, ctx.p, ctx.names = module, sv, p, names
             ctx.need_param, ctx.need_dx = need_param, need_dx

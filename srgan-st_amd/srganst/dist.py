@@ -19,6 +19,8 @@ import os
 import torch
 import torch.distributed as td
 
+from ._state import state
+
 
 def init_from_env(backend: str | None = None) -> tuple[int, int, int]:
     """torchrun-style env (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*) -> (rank, local_rank, world)."""
@@ -84,21 +86,14 @@ def allreduce_grads(params, pg=None, buckets: int = 1, force: bool = False) -> N
 
 def allreduce_module_grads(module, pg=None, buckets: int = 1, force: bool = False) -> None:
     """Like allreduce_grads(module.parameters()), but if the module's backward left its gradients as views of one
-    flat buffer (srganst graphs do: module._flat_grad) and they still live there, that buffer is all-reduced in place -
+    flat buffer (srganst graphs do: module_flat_grad) and they still live there, that buffer is all-reduced in place -
     one message (or `buckets` contiguous slices of it), no flatten / unflatten copies."""
     world = world_size(pg)
     if world == 1 and not (force and td.is_available() and td.is_initialized()):
         return
-    ps = [p for p in module.parameters() if p.grad is not None]
-    flat = None
-    for cand in reversed(module.__dict__.get("_flat_grads", [])):
-        lo, hi = cand.data_ptr(), cand.data_ptr() + cand.numel() * 4
-        if ps and all(lo <= p.grad.data_ptr() < hi and p.grad.is_contiguous() for p in ps) and \
-                sum((p.grad.numel() + 15) // 16 * 16 for p in ps) == cand.numel():
-            flat = cand
-            break
+    flat = module_flat_grad(module)
     if flat is None:
-        return allreduce_grads(ps, pg, buckets, force)
+        return allreduce_grads(module.parameters(), pg, buckets, force)
     n = flat.numel()
     step = (n + buckets - 1) // buckets
     # RCCL averages inside the collective (one elementwise pass less); gloo (CPU tests) has no AVG: sum, then scale
@@ -139,7 +134,7 @@ class AsyncAllReduce:
 def module_flat_grad(module):
     """The flat buffer the module's parameter gradients are views of (srganst graphs leave them that way), or None."""
     ps = [p for p in module.parameters() if p.grad is not None]
-    for cand in reversed(module.__dict__.get("_flat_grads", [])):
+    for cand in reversed(state(module).flat_grads):
         lo, hi = cand.data_ptr(), cand.data_ptr() + cand.numel() * 4
         if ps and all(lo <= p.grad.data_ptr() < hi and p.grad.is_contiguous() for p in ps) and \
                 sum((p.grad.numel() + 15) // 16 * 16 for p in ps) == cand.numel():

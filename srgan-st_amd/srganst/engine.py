@@ -15,6 +15,7 @@ Same semantics as the reference step by step; what differs is execution:
 from __future__ import annotations
 
 from collections import OrderedDict
+from contextlib import nullcontext
 
 import os
 
@@ -22,6 +23,7 @@ import torch
 
 from . import dist as sdist
 from . import ops as _ops
+from ._state import state
 
 
 def make_adam(module, lr, betas, eps, weight_decay, capturable):
@@ -284,10 +286,8 @@ class TrainEngine:
         self.d_loss = self.pred_gt = self.pred_sr = None
         g = use_graph
         self.dp = self.world > 1 or force_dp     # force_dp: the split-graph + collective path even with one rank (tests)
-        # D's packed weights are made once per iteration, by the D(sr) of the generator step, and re-used by the forward and
-        # backward passes of the discriminator step (disc_graph._packs): this engine owns every update of D's weights
-        self.D.__dict__["_packs_managed"] = True
-        self.D.__dict__["_packs_fresh"] = False
+        self._ds = state(self.D)
+        self._ds.owner, self._ds.packs_fresh = self, False      # this engine owns every update of D's weights (HipState.owner)
         # A captured graph bakes in the tensors that exist at capture time (D's graph reads the generator graph's static `sr`):
         # a mixed eager / graph state would replay on stale buffers, so ONE failed capture sends the whole engine back to eager.
         f = self._drop_graphs
@@ -344,52 +344,58 @@ class TrainEngine:
         return bool(st) and all(s.graph is not None for s in st)
 
     # -- generator half: train.py:125-144
-    def _g_fwd_bwd(self):
+    def _g_forward(self, branch, counter_add=0, stamps=False):
+        """Generator forward through the criterion total (train.py:125-140); returns the total, leaves self.sr / self.loss_values.
+        branch: the discriminator step forks from this forward (the two-stream schedules): D's D(sr) pass is kept for it (into a
+        two-pass arena where _arena_slot allows) and D's weights are packed on the side stream, beside the generator's forward
+        (KERNEL.EARLY_D_PACK).  counter_add: the passes of the iteration, added to D's BatchNorm batch counters here (_iter_gd).
+        stamps: ops.debug_stamp 0-2."""
+        from . import disc_graph, ops
         cfg = self.config
+        crits = cfg.MODEL.G_LOSS.CRITERIONS
+        stamp = ops.debug_stamp if stamps else (lambda slot: None)
         for p in self.D.parameters():
             p.requires_grad = False
         self.g_opt.zero_grad(set_to_none=True)
-        self.D.__dict__["_packs_fresh"] = False      # the generator step always packs D's current weights (also when captured)
-        sr = self.G(self.lr)
-        total, vals = _criterion_total(sr, self.gt, cfg.MODEL.G_LOSS.CRITERIONS, cfg.MODEL.G_LOSS.CRITERION_WEIGHTS,
-                                       adversarial=lambda crit: crit(self.D(sr), self.real),
-                                       adv_logits=lambda: self.D(sr), adv_label=self.real)
-        total.backward(_one(total))
+        self._ds.packs_fresh = False      # the generator step always packs D's current weights (also when captured)
+        early_pack = bool(branch and cfg.KERNEL.EARLY_D_PACK and "Adversarial" in crits)
+        with self._ds.keeping_pass(self._arena_slot()) if branch else nullcontext():
+            if counter_add and not early_pack:      # ... otherwise the add rides in the early pack launch below
+                ops.flatten_bn_counters(self.D).add_(counter_add)
+            stamp(0)
+            if early_pack:
+                # D's weights are packed (one multi-tensor launch + one per stride-2 layer, 67 us) for all passes of the iteration on
+                # the side stream, beside the generator's forward, instead of in front of D(sr) on the critical path
+                main, side = torch.cuda.current_stream(), self._side_stream()
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    disc_graph._packs(self.D, disc_graph.param_dict(self.D)[1], True, counter_add=counter_add)
+            sr = self.G(self.lr)
+            if early_pack:
+                main.wait_stream(side)               # D(sr) below reads the packed weights
+            stamp(1)
+            total, vals = _criterion_total(sr, self.gt, crits, cfg.MODEL.G_LOSS.CRITERION_WEIGHTS,
+                                           adversarial=lambda crit: crit(self.D(sr), self.real),
+                                           adv_logits=lambda: self.D(sr), adv_label=self.real)
         self.sr = sr.detach()
         self.loss_values = vals
-        return vals
+        stamp(2)
+        return total
+
+    def _side_stream(self):
+        if self._side_d is None:
+            self._side_d = torch.cuda.Stream()
+        return self._side_d
+
+    def _g_fwd_bwd(self):
+        total = self._g_forward(branch=False)
+        total.backward(_one(total))
+        return self.loss_values
 
     # the same half in two parts (data-parallel schedule: the discriminator branch forks between them)
     def _g_fwd(self):
-        cfg = self.config
-        for p in self.D.parameters():
-            p.requires_grad = False
-        self.g_opt.zero_grad(set_to_none=True)
-        self.D.__dict__["_packs_fresh"] = False
-        self.D.__dict__["_keep_pass"], self.D.__dict__["_last_pass"] = True, None      # _d_fwd_cls re-uses the D(sr) pass
-        self._request_arena()
-        early_pack = cfg.KERNEL.EARLY_D_PACK and "Adversarial" in cfg.MODEL.G_LOSS.CRITERIONS
-        if early_pack:                             # D's weight packing beside the generator's forward (as in _iter_gd)
-            from . import disc_graph
-            main = torch.cuda.current_stream()
-            if self._side_d is None:
-                self._side_d = torch.cuda.Stream()
-            names = [n for n, _ in self.D.named_parameters()]
-            self._side_d.wait_stream(main)
-            with torch.cuda.stream(self._side_d):
-                disc_graph._packs(self.D, dict(zip(names, [t.detach() for t in self.D.parameters()])), True)
-        sr = self.G(self.lr)
-        if early_pack:
-            main.wait_stream(self._side_d)
-        total, vals = _criterion_total(sr, self.gt, cfg.MODEL.G_LOSS.CRITERIONS, cfg.MODEL.G_LOSS.CRITERION_WEIGHTS,
-                                       adversarial=lambda crit: crit(self.D(sr), self.real),
-                                       adv_logits=lambda: self.D(sr), adv_label=self.real)
-        self.D.__dict__["_keep_pass"] = False
-        self.D.__dict__.pop("_arena_request", None)
-        self.sr = sr.detach()
-        self.loss_values = vals
-        self._g_total = total
-        return vals
+        self._g_total = self._g_forward(branch=True)      # _d_fwd_cls re-uses the D(sr) pass
+        return self.loss_values
 
     def _g_bwd(self):
         self._g_total.backward(_one(self._g_total))
@@ -408,21 +414,16 @@ class TrainEngine:
         self.g_opt.step()
         return v
 
-    def _request_arena(self):
+    def _arena_slot(self):
         """KERNEL.REUSE_D_SR + KERNEL.BATCH_D_STEP: the generator step's D(sr) pass writes its activations into slot 1 of a two-pass arena
-        (disc_graph.PassArena); the discriminator step's D(gt) fills slot 0 and ONE backward runs over both (_d_fwd_cls)."""
+        (disc_graph.PassArena); the discriminator step's D(gt) fills slot 0 and ONE backward runs over both (_d_fwd_cls).  (slots, slot)
+        for HipState.arena_request, or None."""
+        from . import disc_graph
         cfg = self.config
         ok = (cfg.KERNEL.REUSE_D_SR and cfg.KERNEL.BATCH_D_STEP and "Adversarial" in cfg.MODEL.G_LOSS.CRITERIONS
-              and self.batch_num % cfg.SOLVER.D_UPDATE_INTERVAL == 0 and self.gt is not None)
-        if ok:
-            from . import disc_graph
-            names = [n for n, _ in self.D.named_parameters()]
-            pd = dict(zip(names, [t.detach() for t in self.D.parameters()]))
-            ok = disc_graph.groups_supported(self.D, pd, self.gt.shape[0], 2, self.gt.shape[2], self.gt.shape[3])
-        if ok:
-            self.D.__dict__["_arena_request"] = (2, 1)
-        else:
-            self.D.__dict__.pop("_arena_request", None)
+              and self.batch_num % cfg.SOLVER.D_UPDATE_INTERVAL == 0 and self.gt is not None
+              and disc_graph.groups_supported(self.D, disc_graph.param_dict(self.D)[1], self.gt.shape[0], 2, self.gt.shape[2], self.gt.shape[3]))
+        return (2, 1) if ok else None
 
     # -- discriminator half: train.py:149-164
     def _d_fwd_bwd(self):
@@ -434,16 +435,12 @@ class TrainEngine:
         pred_sr = self.D(self.sr)                            # train.py:158 detaches + clones; self.sr is detached and D only reads it
         loss_fake = self.adv(pred_sr, self.fake)
         d_loss = loss_real + loss_fake
-        scope = {"flat": None}
-        self.D.__dict__["_grad_accum"] = scope               # both backward passes write ONE flat gradient buffer (disc_graph.backward)
-        try:
+        with self._ds.accumulating_grads() as scope:         # both backward passes write ONE flat gradient buffer (disc_graph.backward)
             d_loss.backward(_one(d_loss))
-        finally:
-            self.D.__dict__.pop("_grad_accum", None)
         # The scope relies on autograd ADOPTING the first pass's views as p.grad (no clone) while the second pass adds into the
         # same buffer and returns nothing.  If a torch version / a hook ever clones instead, the second pass's half of the
         # gradient would be lost silently: check the aliasing once per (eager or capturing) call.
-        flat = scope["flat"]
+        flat = scope.flat
         if flat is not None:
             lo, hi = flat.data_ptr(), flat.data_ptr() + 4 * flat.numel()
             for n, p in self.D.named_parameters():
@@ -462,56 +459,48 @@ class TrainEngine:
         for p in D.parameters():
             p.requires_grad = True
         self.d_opt.zero_grad(set_to_none=True)
-        names = [n for n, _ in D.named_parameters()]
-        pd = dict(zip(names, [t.detach() for t in D.parameters()]))
+        names, pd = disc_graph.param_dict(D)
         B = self.gt.shape[0]
-        kept = D.__dict__.get("_last_pass") if self.config.KERNEL.REUSE_D_SR else None
+        ds = self._ds
+        kept = ds.last_pass if self.config.KERNEL.REUSE_D_SR else None
         if self.config.KERNEL.BATCH_D_STEP:
             if kept is None and self.sr.shape == self.gt.shape and disc_graph.groups_supported(D, pd, B, 2, self.gt.shape[2], self.gt.shape[3]):
                 # Both passes of the step as ONE batch [gt ; sr] with per-pass BatchNorm statistics (running statistics move in the
                 # reference's order: gt, then sr), one backward over 2B images.
-                D.__dict__.pop("_last_pass", None)
+                ds.last_pass = None
                 pred, sv = disc_graph.forward(D, [self.gt, self.sr], pd, True, True)
                 return self._d_cls_batched(pd, names, pred[:B], pred[B:], sv)
-            if (kept is not None and kept.get("arena") is not None and tuple(self.gt.shape) == tuple(self.sr.shape)
-                    and self._is_sr_pass(kept, pd, names)):
+            if (kept is not None and kept.arena is not None and tuple(self.gt.shape) == tuple(self.sr.shape)
+                    and kept.is_pass_over(self.sr, pd, names)):
                 # The kept D(sr) pass sits in slot 1 of a two-pass arena: D(gt) fills slot 0, the running statistics take D(sr.detach())'s
                 # step (replayed, as below), and ONE backward runs over the 2B images with per-pass BatchNorm rows.
-                D.__dict__.pop("_last_pass", None)
-                arena = kept["arena"]
-                pred_gt, sv_gt = disc_graph.forward(D, self.gt, pd, True, True, arena=(arena, 0))
-                disc_graph.replay_running_stats(D, pd, kept["sv"])
+                ds.last_pass = None
+                pred_gt, sv_gt = disc_graph.forward(D, self.gt, pd, True, True, arena=(kept.arena, 0))
+                disc_graph.replay_running_stats(D, pd, kept.sv)
                 self.d_sr_reused = True
-                return self._d_cls_batched(pd, names, pred_gt, kept["out"].detach(), disc_graph.batched_saved(arena, sv_gt))
+                return self._d_cls_batched(pd, names, pred_gt, kept.out.detach(), disc_graph.batched_saved(kept.arena, sv_gt))
         pred_gt, sv_gt = disc_graph.forward(D, self.gt, pd, True, True)
         loss_real, dl_gt = ops.bce_logits(pred_gt, self.real, want_loss=True, want_grad=True)
         # D(sr.detach()) (train.py:158) repeats the generator step's D(sr) (train.py:136): same input, same weights (D's Adam comes
         # after both), train-mode BatchNorm both times - every kernel is deterministic, so the pass would reproduce the saved
         # activations and logits bit for bit.  It is not run again: its side effects (running statistics, batch counter) are
         # replayed in the reference's order (after D(gt)'s) and the backward works on the generator step's saved pass.
-        kept = D.__dict__.pop("_last_pass", None) if self.config.KERNEL.REUSE_D_SR else None
-        if kept is not None and self._is_sr_pass(kept, pd, names):
-            disc_graph.replay_running_stats(D, pd, kept["sv"])
-            pred_sr, sv_sr = kept["out"].detach(), kept["sv"]
+        if kept is not None:
+            ds.last_pass = None              # taken: re-used below or stale
+        if kept is not None and kept.is_pass_over(self.sr, pd, names):
+            disc_graph.replay_running_stats(D, pd, kept.sv)
+            pred_sr, sv_sr = kept.out.detach(), kept.sv
             self.d_sr_reused = True
         else:
             pred_sr, sv_sr = disc_graph.forward(D, self.sr, pd, True, True)
         loss_fake, dl_sr = ops.bce_logits(pred_sr, self.fake, want_loss=True, want_grad=True)
         self.d_loss, self.pred_gt, self.pred_sr = loss_real + loss_fake, pred_gt, pred_sr
-        D.__dict__["_grad_accum"] = {"flat": None}
-        try:
+        with ds.accumulating_grads():
             st_sr = disc_graph.backward_classifier(D, pd, sv_sr, dl_sr, True)
             st_gt = disc_graph.backward_classifier(D, pd, sv_gt, dl_gt, True)
-        finally:
-            D.__dict__.pop("_grad_accum", None)
         self._d_state = (pd, sv_sr, st_sr, sv_gt, st_gt)
         self._cut_d_buckets(pd, names)
         return self.d_loss
-
-    def _is_sr_pass(self, kept, pd, names):
-        """Is the generator step's kept D(sr) pass (disc_graph.DiscriminatorFn) a pass over self.sr with D's current weights?"""
-        return (kept["x_ptr"] == self.sr.data_ptr() and kept["x_shape"] == tuple(self.sr.shape)
-                and all(kept["p"][n].data_ptr() == pd[n].data_ptr() and kept["p"][n]._version == pd[n]._version for n in names))
 
     def _d_cls_batched(self, pd, names, pred_gt, pred_sr, sv):
         """_d_fwd_cls on both passes as one batch of 2B images (logits of D(gt) first): the losses, their logit gradients in one
@@ -531,7 +520,7 @@ class TrainEngine:
     def _cut_d_buckets(self, pd, names):
         """The two all-reduce buckets of the discriminator's flat gradient buffer: (classifier, feature stack)."""
         from . import ops
-        flat = self.D.__dict__["_flat_grads"][-1]
+        flat = self._ds.flat_grads[-1]
         offs, total = ops.flat_layout([pd[n] for n in names])
         cut = offs[names.index("classifier.0.weight")]          # features.* come first in the reference's parameter order
         self._d_buckets = (flat[cut:total], flat[:cut])
@@ -557,50 +546,16 @@ class TrainEngine:
     # join (the generator's backward through D still reads D's weights).  Same kernels, same arguments, same order per tensor:
     # bit-identical to the sequential schedule.
     def _iter_gd(self):
-        try:
+        with self._ds.external_counters():
             return self._iter_gd_body()
-        finally:
-            self.D.__dict__["_counters_external"] = False
 
     def _iter_gd_body(self):
+        from . import ops
         cfg = self.config
-        for p in self.D.parameters():
-            p.requires_grad = False
-        self.g_opt.zero_grad(set_to_none=True)
-        self.D.__dict__["_packs_fresh"] = False
-        self.D.__dict__["_keep_pass"], self.D.__dict__["_last_pass"] = True, None
-        self._request_arena()
-        from . import disc_graph, ops
-        adv = "Adversarial" in cfg.MODEL.G_LOSS.CRITERIONS
         # the batch counters of D's BatchNorms move by one per pass (run or replayed): ONE add per iteration instead of three
-        self.D.__dict__["_counters_external"] = True
-        n_pass = 3 if adv else 2
-        early_pack = bool(adv and cfg.KERNEL.EARLY_D_PACK)      # ... and that add rides in the early pack launch below when there is one
-        if not early_pack:
-            ops.flatten_bn_counters(self.D).add_(n_pass)
-        ops.debug_stamp(0)
-        main = torch.cuda.current_stream()
-        if self._side_d is None:
-            self._side_d = torch.cuda.Stream()
-        side = self._side_d
-        if early_pack:
-            # D's weights are packed (one multi-tensor launch + one per stride-2 layer, 67 us) for all passes of the iteration on the
-            # side stream, beside the generator's forward, instead of in front of D(sr) on the critical path
-            names = [n for n, _ in self.D.named_parameters()]
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                disc_graph._packs(self.D, dict(zip(names, [t.detach() for t in self.D.parameters()])), True, counter_add=n_pass)
-        sr = self.G(self.lr)
-        if early_pack:
-            main.wait_stream(side)               # D(sr) below reads the packed weights
-        ops.debug_stamp(1)
-        total, vals = _criterion_total(sr, self.gt, cfg.MODEL.G_LOSS.CRITERIONS, cfg.MODEL.G_LOSS.CRITERION_WEIGHTS,
-                                       adversarial=lambda crit: crit(self.D(sr), self.real),
-                                       adv_logits=lambda: self.D(sr), adv_label=self.real)
-        self.D.__dict__["_keep_pass"] = False
-        self.D.__dict__.pop("_arena_request", None)
-        self.sr = sr.detach()
-        ops.debug_stamp(2)
+        n_pass = 3 if "Adversarial" in cfg.MODEL.G_LOSS.CRITERIONS else 2
+        total = self._g_forward(branch=True, counter_add=n_pass, stamps=True)
+        main, side = torch.cuda.current_stream(), self._side_stream()
         side.wait_stream(main)                  # the discriminator step's branch forks HERE
         with torch.cuda.stream(side):           # both passes on ONE side stream (a helper stream forked from it could only be joined into
             ops.debug_stamp(3)                  # `main`: ops.check_capture_join)
@@ -615,7 +570,6 @@ class TrainEngine:
         with torch.autograd.set_multithreading_enabled(False):      # backward on this thread: one thread feeds the open capture
             total.backward(_one(total))
         ops.debug_stamp(7)
-        self.loss_values = vals
         if self.one_graph_dp:
             self._g_allreduce()                 # 6.2 MB, behind the classifier bucket on the process group's stream
         self.g_opt.step()
@@ -643,13 +597,12 @@ class TrainEngine:
             ar_c.wait()                          # on the origin stream
             ar_f.wait()
         self._d_step()
-        self.D.__dict__["_counters_external"] = False
         ops.debug_stamp(9)
-        return vals
+        return self.loss_values
 
     def _d_step(self):
         self.d_opt.step()
-        self.D.__dict__["_packs_fresh"] = False      # weights changed
+        self._ds.packs_fresh = False      # weights changed
 
     def _d_full(self):
         v = self._d_fwd_bwd()
@@ -661,7 +614,8 @@ class TrainEngine:
         self._g_fb = self._g_op = self._d_fb = self._d_op = self._d_a = self._d_b = self._it = self._g_f = self._g_b = None
         self._g_total = None
         self._d_state = self._d_buckets = None
-        self.D.__dict__.pop("_last_pass", None)
+        # D is handed back: no owner, so it packs on every call again (a later optimizer step on it would not clear packs_fresh)
+        self._ds.owner, self._ds.packs_fresh, self._ds.last_pass = None, False, None
         self.gt = self.lr = self.sr = None
 
     def _step_overlapped(self):
@@ -673,9 +627,7 @@ class TrainEngine:
         did_d = self.batch_num % self.config.SOLVER.D_UPDATE_INTERVAL == 0
         self._g_f()
         if did_d:
-            if self._side_d is None:
-                self._side_d = torch.cuda.Stream()
-            side = self._side_d
+            side = self._side_stream()
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 self._d_a()

@@ -13,6 +13,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from ._state import state
 from .ops import ACT_SLOPE, OUT_NCHW_CLAMP, OUT_SHUFFLE
 
 
@@ -52,7 +53,7 @@ def _packs(module, p, with_dgrad, extras=()):
     """All packed weights of the generator from ONE multi-tensor launch: (forward packs by name, data-gradient packs by name or
     None, packs of the (kx, 3ch)-folded 9x9 kernels {"conv1", "conv3", "conv3.dgrad"}).  The data-gradient packs are made by
     the training forward and handed to backward() (the weights do not change in between).  extras: ops.PackPlan's riders."""
-    cache = module.__dict__.setdefault("_hip_cache", {})
+    cache = state(module).cache
     fast9 = _fast9(module, p)
     names = _conv_names(module, fast9)
     ws = [p[n] for n in names]
@@ -79,9 +80,9 @@ def _bn_accumulators(module, nblocks, C, device, zero, whole=False):
     """The fp64 statistics accumulators of the accumulator mode, forward [2*nblocks+1][NREP][C][2] and backward
     [2*nblocks][NREP][C][4], as views of ONE buffer so that one fill at the start of the forward clears both (whole: that buffer)."""
     nf, nbk = (2 * nblocks + 1) * ops.ACC_NREP * C * 2, 2 * nblocks * ops.ACC_NREP * C * 4
-    buf = module.__dict__.get("_bn_acc_buf")
+    buf = state(module).bn_acc_buf
     if buf is None or buf.numel() != nf + nbk or buf.device != device:
-        buf = module.__dict__["_bn_acc_buf"] = torch.zeros(nf + nbk, device=device, dtype=torch.float64)
+        buf = state(module).bn_acc_buf = torch.zeros(nf + nbk, device=device, dtype=torch.float64)
     if whole:
         return buf
     if zero == "all":
@@ -133,7 +134,7 @@ def forward(module, x, params, need_grad):
         # the NEXT conv derives the affine of its input from them in its prologue (csrc/conv_epilogue.h: BandAcc)
         nbn = 2 * len(module.trunk) + 1
         acc, _ = _bn_accumulators(module, len(module.trunk), C, z1.device, zero=None)       # cleared by the pack launch above
-        sv["acc_token"] = module.__dict__["_bn_acc_token"] = object()      # backward: its accumulators are still clear
+        sv["acc_token"] = state(module).bn_acc_token = object()      # backward: its accumulators are still clear
 
         def stat_tensors():
             return tuple(ops._f32(C, like=z1) for _ in range(4))
@@ -280,8 +281,8 @@ def backward(module, params, sv, dsr, need_dx=False):
         # ---- accumulator mode: every data-gradient conv adds the BatchNorm-backward sums of its result into fp64 accumulators,
         # the next stage derives its coefficients from them in its prologue (no finalize launches between the stages)
         _, bacc = _bn_accumulators(module, nb, C, y3.device, zero="bwd" if sv.get("acc_token") is None or
-                                   module.__dict__.get("_bn_acc_token") is not sv.get("acc_token") else None)
-        module.__dict__["_bn_acc_token"] = None          # the backward accumulators are dirty from here on
+                                   state(module).bn_acc_token is not sv.get("acc_token") else None)
+        state(module).bn_acc_token = None          # the backward accumulators are dirty from here on
         dh, _ = ops.conv_dgrad_fused_acc(dy3, wd["conv2.0.weight"], C, 3, epi_y=sv["blocks"][-1][6], bw_st_acc=bacc[2 * nb - 1])
         for i in reversed(range(nb)):
             pre = f"trunk.{i}.rcb"

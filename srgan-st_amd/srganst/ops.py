@@ -12,6 +12,7 @@ import torch
 
 from . import _abi
 from ._abi import check, ptr, stream_ptr
+from ._state import state
 
 OUT_NHWC, OUT_SHUFFLE, OUT_NCHW_CLAMP, OUT_UNSHUFFLE = 0, 1, 2, 3
 ACT_NONE, ACT_SLOPE = 0, 1
@@ -735,14 +736,14 @@ def flatten_bn_counters(module):
     bns = [m for m in module.modules() if isinstance(m, torch.nn.BatchNorm2d)]
     if not bns:
         return None
-    flat = getattr(module, "_nbt_flat", None)
+    flat = state(module).nbt_flat
     ok = flat is not None and flat.device == bns[0].num_batches_tracked.device and all(
         bn.num_batches_tracked.data_ptr() == flat.data_ptr() + 8 * i for i, bn in enumerate(bns))
     if not ok:
         flat = torch.stack([bn.num_batches_tracked.detach().to(torch.int64) for bn in bns])
         for i, bn in enumerate(bns):
             bn._buffers["num_batches_tracked"] = flat[i]
-        module._nbt_flat = flat
+        state(module).nbt_flat = flat
     return flat
 
 
@@ -950,27 +951,21 @@ def flat_layout(params):
 def flat_grads(module, names, params):
     """One flat fp32 buffer + per-parameter views (reference order).  The buffer is remembered on the module so that
     the data-parallel exchange can all-reduce it in place as ONE message (no flatten / unflatten copies) and the flat
-    Adam (srganst.optim.FlatAdam) can consume it as one array.
-    The buffers are PERSISTENT: a ring of FLAT_RING zero-initialised buffers per module, allocated at the first call (always an eager
-    warm-up call: never inside a graph capture) and handed out in turn.  The pad words between the views (flat_layout) are written by
-    nobody, so they stay zero for good - they travel through the flat Adam and the all-reduce with the real gradients, and an
-    uninitialised NaN there would poison any norm / isfinite check over the flat buffer.  A buffer comes round again after
-    FLAT_RING - 1 other backward passes of the module (at most two per step are alive at once: the two-stream discriminator step)."""
+    Adam (srganst.optim.FlatAdam) can consume it as one array.  The buffers are persistent (HipState.flat_ring)."""
     offs, total = flat_layout(params)
     dev = params[0].device
-    ring = module.__dict__.get("_flat_ring")
+    st = state(module)
+    ring = st.flat_ring
     if ring is None or ring["total"] != total or ring["device"] != dev:
         if torch.cuda.is_current_stream_capturing():
             raise _abi.HipPathError("flat_grads: the gradient buffers must exist before a graph capture (run an eager warm-up step first)")
         ring = {"total": total, "device": dev, "next": 0,
                 "bufs": [torch.zeros(total, device=dev, dtype=torch.float32) for _ in range(FLAT_RING)]}
-        module.__dict__["_flat_ring"] = ring
+        st.flat_ring = ring
     flat = ring["bufs"][ring["next"]]
     ring["next"] = (ring["next"] + 1) % FLAT_RING
     views = {n: flat[o:o + t.numel()].view(t.shape) for n, t, o in zip(names, params, offs)}
-    # remember the order of use: with two backward passes per step (D on gt and on sr) autograd accumulates into the
-    # FIRST pass's buffer, which is then the one holding p.grad
-    lst = module.__dict__.setdefault("_flat_grads", [])
+    lst = st.flat_grads                 # in order of use
     lst[:] = [t for t in lst if t is not flat] + [flat]
     del lst[:-4]
     return views
@@ -984,7 +979,7 @@ def flatten_params(module):
     layout flat_grads gives the gradients) and re-point the nn.Parameters at views of it.  Values, names, shapes and
     state_dict are unchanged.  Returns (flat, offsets, params)."""
     params = [p for _, p in module.named_parameters()]
-    ent = module.__dict__.get("_flat_params")
+    ent = state(module).flat_params
     if ent is not None and all(p.data_ptr() == ent[0].data_ptr() + 4 * o for p, o in zip(params, ent[1])):
         return ent[0], ent[1], params
     offs, total = flat_layout(params)
@@ -994,7 +989,7 @@ def flatten_params(module):
             v = flat[o:o + p.numel()].view(p.shape)
             v.copy_(p.data)
             p.data = v
-    module.__dict__["_flat_params"] = (flat, offs)
+    state(module).flat_params = (flat, offs)
     return flat, offs, params
 
 

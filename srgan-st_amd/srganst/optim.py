@@ -10,6 +10,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
+from ._state import state
 
 
 class FlatAdam(torch.optim.Adam):
@@ -57,7 +58,7 @@ class FlatAdam(torch.optim.Adam):
         if g0 is None:
             return None
         n = self._flat_p.numel()
-        for cand in reversed(self._module.__dict__.get("_flat_grads", [])):
+        for cand in reversed(state(self._module).flat_grads):
             b = cand.data_ptr()
             if cand.numel() != n or g0.data_ptr() != b + 4 * self._offs[0]:
                 continue

@@ -136,6 +136,7 @@ def test_discriminator_two_passes_as_one_batch(same_kernels, monkeypatch):
     routing the two sides are two fp32 summation orders of the discriminator's ill-conditioned BatchNorm gradients (see the
     iteration test below for the fp64-truth rule) and the bound is 2e-3."""
     from srganst import disc_graph, ops
+    from srganst._state import state
     if same_kernels:
         monkeypatch.setattr(ops, "CONV_NS", False)
     B = 8
@@ -156,10 +157,9 @@ def test_discriminator_two_passes_as_one_batch(same_kernels, monkeypatch):
             pa, sva = disc_graph.forward(D, a, pd, True, True)
             pb, svb = disc_graph.forward(D, b, pd, True, True)
             pred = torch.cat([pa, pb])
-            D.__dict__["_grad_accum"] = {"flat": None}
-            grads, _ = disc_graph.backward(D, pd, sva, dl[:B].contiguous(), True, False)
-            disc_graph.backward(D, pd, svb, dl[B:].contiguous(), True, False)
-            D.__dict__.pop("_grad_accum")
+            with state(D).accumulating_grads():
+                grads, _ = disc_graph.backward(D, pd, sva, dl[:B].contiguous(), True, False)
+                disc_graph.backward(D, pd, svb, dl[B:].contiguous(), True, False)
             rows = [(torch.stack([ra["scale"], rb["scale"]]), torch.stack([ra["shift"], rb["shift"]]))
                     for ra, rb in zip(sva["layers"], svb["layers"]) if ra["bi"] is not None]
         torch.cuda.synchronize()

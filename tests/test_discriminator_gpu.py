@@ -285,6 +285,7 @@ def test_train_engine_pack_reuse_equals_repacking(interval):
     """The engine lets the discriminator step re-use the weight packs made by the generator step's D(sr) (disc_graph._packs).
     Same run with the re-use switched off (every pass packs, as outside an engine): parameters, BatchNorm buffers and losses
     must be bit-identical, with D updated every step and every second step, under hipGraph replay."""
+    from srganst._state import state
     from srganst.engine import TrainEngine
     from srganst.loss import MSELoss, StructureTensorLoss
     from srganst.model import Discriminator, Generator
@@ -298,7 +299,7 @@ def test_train_engine_pack_reuse_equals_repacking(interval):
         cfg.SOLVER.D_UPDATE_INTERVAL = interval
         eng = TrainEngine(cfg, G, D, use_graph=True, adam_capturable=True)
         if not managed:
-            D.__dict__["_packs_managed"] = False
+            state(D).owner = None
         gen = torch.Generator().manual_seed(2)
         for _ in range(6):
             eng.step(torch.rand(4, 3, 96, 96, generator=gen).cuda(), torch.rand(4, 3, 24, 24, generator=gen).cuda())
@@ -312,6 +313,42 @@ def test_train_engine_pack_reuse_equals_repacking(interval):
     for k in d1:
         assert torch.equal(d1[k], d2[k]), k
     assert l1 == l2
+
+
+def test_train_engine_hands_discriminator_back():
+    """The engine's marks on the discriminator (srganst._state) are scoped: a generator criterion that raises in the middle of the
+    merged iteration - after D(sr) has run in "keep the pass" mode - leaves none of them set, and close() gives up the ownership,
+    so a plain D(x) with grad afterwards neither allocates a two-pass arena nor pins its activations."""
+    from srganst._state import state
+    from srganst.engine import TrainEngine
+    from srganst.loss import MSELoss, StructureTensorLoss
+    from srganst.model import Discriminator, Generator
+
+    def broken(sr, gt):
+        raise RuntimeError("criterion failed")
+
+    cfg = make_cfg(16, 2, 8)
+    torch.manual_seed(1)
+    D, G = Discriminator(cfg).cuda().train(), Generator(cfg).cuda().train()
+    cfg.add_g_criterion("Pixel", MSELoss(), 1.0)
+    cfg.add_g_criterion("ST", StructureTensorLoss(), 1 / 3)
+    cfg.add_g_criterion("Broken", broken, 1.0)
+    eng = TrainEngine(cfg, G, D, use_graph=False, adam_capturable=True)
+    assert state(D).owner is eng
+    gen = torch.Generator().manual_seed(2)
+    gt, lr = torch.rand(4, 3, 96, 96, generator=gen).cuda(), torch.rand(4, 3, 24, 24, generator=gen).cuda()
+    with pytest.raises(RuntimeError, match="criterion failed"):
+        eng.step(gt, lr)
+    st = state(D)
+    assert not st.keep_pass and st.arena_request is None
+    assert not st.counters_external
+    eng.close()
+    assert st.owner is None and not st.packs_fresh and st.last_pass is None
+    D.requires_grad_(True)               # the generator half froze it
+    D(gt).sum().backward()
+    torch.cuda.synchronize()
+    assert st.last_pass is None
+    assert all(p.grad is not None for p in D.parameters())
 
 
 @pytest.mark.parametrize("fail", ["g", "d"])

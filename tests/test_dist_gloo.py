@@ -65,6 +65,7 @@ def _async_worker(rank, world, port, q):
     sys.path.insert(0, os.path.join(here, "srgan-st_amd"))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     from srganst import dist as sdist
+    from srganst._state import state
     sdist.init_from_env("gloo")
     # a module whose gradients are views of ONE flat buffer with 16-float aligned slots (what the srganst graphs leave behind)
     torch.manual_seed(5)
@@ -78,7 +79,7 @@ def _async_worker(rank, world, port, q):
     flat = torch.randn(off, generator=g)
     for p, o in zip(ps, offs):
         p.grad = flat[o:o + p.numel()].view(p.shape)
-    model.__dict__["_flat_grads"] = [torch.zeros(3), flat]
+    state(model).flat_grads += [torch.zeros(3), flat]
     found = sdist.module_flat_grad(model)
     assert found is flat
     local = flat.clone()
