@@ -385,6 +385,26 @@ int sst_gather_crops(const uint8_t* arena, int64_t arena_bytes, const int64_t* t
 int sst_image_metrics_workspace(int B, int H, int W, int64_t* partial_doubles);
 int sst_image_metrics(const float* sr, const float* hr, int B, int H, int W, double* out, uint8_t* sr_u8, uint8_t* hr_u8,
                       double* workspace, void* stream);
+/* ---- tiled whole-image inference (upscale.py: Upscaler; csrc/tiles.hip).  t = 4*transpose + 2*vflip + 1*hflip as in
+ * sst_gather_crops; all offsets 64-bit; one launch each, no allocation, no sync.
+ * sst_tile_gather: one LR image [H,W] -> out fp32 [B,3,th',tw'] = the th x tw windows at (y0, x0) of desc [B,3] int32 (device) =
+ * (y0, x0, t), each transformed by dihedral(t); (th',tw') = (tw,th) when t&4.  One t per call: a row whose t differs, or whose window
+ * leaves the image, yields NaN for that tile and reads nothing.  Source, exactly one non-null: src_u8 HWC/RGB uint8 through lut [256]
+ * = float(u) / 255 (bit-identical to u8.float() / 255; base 16-byte aligned, src_bytes a multiple of 16 that covers the image: the
+ * buffer is padded) or src_f32 CHW fp32, copied (src_bytes >= 12*H*W). */
+int sst_tile_gather(const uint8_t* src_u8, const float* src_f32, int64_t src_bytes, int H, int W, const int* desc, int B, int th,
+                    int tw, int t, const float* lut, float* out, void* stream);
+/* sst_tile_scatter: tiles fp32 [B,3,scale*th',scale*tw'] (the generator's output for the tiles of one sst_tile_gather call with the
+ * same t) -> canvas fp32 [3,scale*H,scale*W].  rows [B,6] int32 (device) = (y0, x0, oy0, oy1, ox0, ox1) in LR pixels: of tile b,
+ * mapped back through the inverse of t, the rectangle [oy0,oy1) x [ox0,ox1) of the image that it OWNS (inside its window) is stored
+ * to the canvas, or added when accumulate != 0.  The owned rectangles of one call must be disjoint (no atomics); calls are ordered
+ * by the stream.  Pixels that no row owns are not touched; a row outside the image or its window is skipped. */
+int sst_tile_scatter(const float* tiles, const int* rows, int B, int H, int W, int th, int tw, int scale, int t, float* canvas,
+                     int accumulate, void* stream);
+/* sst_canvas_to_u8: canvas fp32 [3,H,W] -> out uint8 [H,W,3] RGB (4-byte aligned), q = rint(clamp(v * scale, 0, 1) * 255.f), NaN -> 0:
+ * utils.tensor2img's arithmetic (sst_image_metrics's quantiser), channels left in RGB order.  scale: 1, or 0.125 for the sum of the
+ * eight passes of the self-ensemble. */
+int sst_canvas_to_u8(const float* canvas, int H, int W, float scale, uint8_t* out, void* stream);
 /* ---- best-buddy losses (loss.py:78-142 BestBuddyLoss, loss.py:145-228 GramLoss, loss.py:292-375
  * PatchwiseStructureTensorLoss; ksize 3, stride 3, pad 0, squared-L2 matching):
  * sst_bb_patches cuts an image [B,3,H,W] into 27-vectors (unfold order) + squared norms inside the candidate table

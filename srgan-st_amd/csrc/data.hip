@@ -13,6 +13,7 @@
 // column sums V (LDS, fp32, HWC order) and the horizontal pass reads V.  LDS: 1 KiB LUT + 12*W B of V + (Ty + band) * 3W B
 // (192 px, x1/8: about 28 KiB).
 #include "common.h"
+#include "pixel_io.h"      // load_dword_unaligned
 
 namespace {
 
@@ -124,15 +125,6 @@ __global__ __launch_bounds__(GATHER_NT) void gather_batch_kernel(
 // multiples of 16), so nothing outside the arena is read.  The vertical pass leaves the column sums V indexed by x' (each sum is
 // one column's own, so its place in V changes no bit) and the horizontal pass reads V through the hflip map.
 constexpr int CROPS_NT = 256;
-
-// bytes a .. a+3 of the arena as one little-endian dword; only the first nvalid (1..4) of them have to be bytes of an image
-__device__ __forceinline__ uint32_t load_dword_unaligned(const uint8_t* __restrict__ arena, int64_t a, int nvalid) {
-  const int sh = (int)(a & 3);
-  const uint32_t* p = reinterpret_cast<const uint32_t*>(arena + (a - sh));
-  const uint32_t lo = p[0];
-  if (sh + nvalid <= 4) return lo >> (8 * sh);
-  return (uint32_t)((((uint64_t)p[1] << 32) | lo) >> (8 * sh));
-}
 
 __global__ __launch_bounds__(CROPS_NT) void gather_crops_kernel(
     const uint8_t* __restrict__ arena, int64_t arena_bytes, const int64_t* __restrict__ table, int64_t N,

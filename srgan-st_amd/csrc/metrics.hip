@@ -23,6 +23,7 @@
 // NaN: the clamp is written with comparisons that keep NaN (fminf / fmaxf would drop it), so a NaN anywhere in sr or hr makes that
 // image's MSE and SSIM NaN (every pixel lies in at least one SSIM window).  The uint8 output of a NaN pixel is 0.
 #include "common.h"
+#include "pixel_io.h"      // quantise, to_u8: tensor2img's quantisation
 
 #include <cmath>
 
@@ -59,14 +60,6 @@ static MetricTaps metric_taps() {
   for (int i = 0; i < MK; ++i) t.w[i] /= s;
   return t;
 }
-
-// tensor2img's quantisation; keeps NaN
-__device__ __forceinline__ float quantise(float x) {
-  const float c = x < 0.f ? 0.f : (x > 1.f ? 1.f : x);
-  return rintf(c * 255.f);
-}
-
-__device__ __forceinline__ uint8_t to_u8(float q) { return q == q ? (uint8_t)(int)q : (uint8_t)0; }
 
 // the value PSNR / SSIM receive for one pixel from its three quantised channels (0..255, RGB order)
 __device__ __forceinline__ float luma255(float qr, float qg, float qb) {

@@ -113,6 +113,9 @@ SIGNATURES = {
     "sst_gather_crops": (c_int, [P, c_int64, P, c_int64, P, c_int, c_int, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_image_metrics_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
     "sst_image_metrics": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P]),
+    "sst_tile_gather": (c_int, [P, P, c_int64, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P]),
+    "sst_tile_scatter": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int, P]),
+    "sst_canvas_to_u8": (c_int, [P, c_int, c_int, c_float, P, P]),
     "sst_feat_loss_fwd": (c_int, [P, P, P, P, c_float, c_int, P, P, P, c_int64, c_int, P]),
     "sst_feat_loss_bwd": (c_int, [P, P, P, P, c_float, c_int, P, P, c_float, c_int, c_int64, c_int, P]),
     "sst_bb_blocks": (c_int, [c_int, c_int, c_int]),

@@ -67,6 +67,9 @@ class Config:
         # defaults): _metrics.txt and the printed line gain an ``ST:`` column, the drivers log Test/ST.  Checkpoint selection is
         # unchanged.  Works with either validation path; on the device path the values cross to the host once, after the loop
         self.DATA.VALIDATE_ST = False
+        # T > 0: validation runs the generator tiled (upscale.Upscaler: windows of T LR pixels with the exact halo, so the whole-image
+        # forward's result) - test images of any size, beyond what one whole-image forward takes.  0: whole-image forwards
+        self.DATA.VALIDATE_TILE = 0
 
         # True: the drivers keep the WHOLE training images of TRAIN_ORIGINAL_IMAGES_DIR (any sizes, e.g. DIV2K as distributed) in
         # device memory and one HIP launch per batch cuts, transforms, converts and downscales the samples (device_data.py:

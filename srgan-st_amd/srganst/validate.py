@@ -3,7 +3,9 @@ under no_grad -> tensor2img -> /255 -> Y channel -> PSNR / SSIM (no border shave
 The generator forward is the HIP path in eval mode (BatchNorm folded to scale/shift from running stats).
 With config.DATA.VALIDATE_ON_DEVICE (or on_device=True) the metrics are taken on the device too (metrics.py).
 With config.DATA.VALIDATE_ST (or with_st=True, or --st) every image also gets its structure-tensor distance (st.st_distance): the
-quantity the ``ST`` criterion optimises, reported next to PSNR and SSIM."""
+quantity the ``ST`` criterion optimises, reported next to PSNR and SSIM.
+With config.DATA.VALIDATE_TILE = T > 0 (or tile=T, or --tile T) the generator runs tiled (upscale.Upscaler, windows of T LR pixels with
+the exact halo): test images of any size, the whole-image forward's result."""
 from __future__ import annotations
 
 import argparse
@@ -81,12 +83,19 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
 
 
 def _validate(generator, val_loader, config, save_images=False, concat_with_gt=False, save_metrics=False, on_device=None,
-              with_st=None):
+              with_st=None, tile=None):
     """on_device: None = config.DATA.VALIDATE_ON_DEVICE; True = metrics by the HIP kernel, one host copy per pass
     (_metrics_on_device); False = the host loop below.  Same averages, same printed line, same _metrics.txt either way.
     with_st: None = config.DATA.VALIDATE_ST; True = every image also gets st.st_distance(output, hr) with the configured ``ST``
     criterion's (sigma, rho, normalize), _metrics.txt and the printed line gain an ``ST:`` column and the return value becomes
-    (psnr, ssim, st); False = everything as without the option."""
+    (psnr, ssim, st); False = everything as without the option.
+    tile: None = config.DATA.VALIDATE_TILE; T > 0 = a Generator runs through upscale.Upscaler(tile=T) with the exact halo (an image
+    that fits in one window takes the plain forward, so small test sets give the numbers they give without the option); 0 = off."""
+    if tile is None:
+        tile = int(config.DATA.get("VALIDATE_TILE", 0))
+    if tile and isinstance(generator, Generator):
+        from .upscale import Upscaler
+        generator = Upscaler(generator, tile=tile)
     if on_device is None:
         on_device = bool(config.DATA.get("VALIDATE_ON_DEVICE", False))
     if with_st is None:
@@ -140,7 +149,7 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
 
 
 def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_gt: bool = False, dataset=None, on_device=None,
-         with_st=None):
+         with_st=None, tile=None):
     if not g_path:
         g_path = f"results/{config.EXP.NAME}/g_best.pth"
     ds = dataset if dataset is not None else TestImageDataset(config.DATA.TEST_GT_IMAGES_DIR, config.DATA.TEST_LR_IMAGES_DIR)
@@ -154,7 +163,7 @@ def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_
         generator = load_state_dict(generator, torch.load(g_path, map_location=config.DEVICE, weights_only=True))
         generator.eval()
     return _validate(generator, loader, config, save_images=save_images, concat_with_gt=concat_w_gt, save_metrics=True,
-                     on_device=on_device, with_st=with_st)
+                     on_device=on_device, with_st=with_st, tile=tile)
 
 
 if __name__ == "__main__":
@@ -165,6 +174,7 @@ if __name__ == "__main__":
     parser.add_argument("--no-images", action="store_true")
     parser.add_argument("--on-device", action="store_true", help="PSNR / SSIM by the HIP kernel (DATA.VALIDATE_ON_DEVICE)")
     parser.add_argument("--st", action="store_true", help="also the structure-tensor distance per image (DATA.VALIDATE_ST)")
+    parser.add_argument("--tile", type=int, default=None, help="run the generator tiled, windows of this many LR pixels (DATA.VALIDATE_TILE)")
     a = parser.parse_args()
     cfg = Config()
     if a.name:
@@ -174,4 +184,4 @@ if __name__ == "__main__":
         cfg.DATA.TEST_GT_IMAGES_DIR = f"/work3/{cfg.EXP.USER}/data/{a.test_set}/GTmod12"
         cfg.DATA.TEST_LR_IMAGES_DIR = f"/work3/{cfg.EXP.USER}/data/{a.test_set}/LRbicx4"
     test(cfg, save_images=not a.no_images, g_path=a.g_path, on_device=True if a.on_device else None,
-         with_st=True if a.st else None)
+         with_st=True if a.st else None, tile=a.tile)
