@@ -10,6 +10,8 @@ and last (conv3 stores NCHW + clamp) kernels.  Fusions relative to the reference
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import torch
 
 from . import ops
@@ -17,21 +19,96 @@ from ._state import state
 from .ops import ACT_SLOPE, OUT_NCHW_CLAMP, OUT_SHUFFLE
 
 
-class _P:
-    """name -> tensor view of the flat parameter / gradient lists of one Generator."""
+class _BN:
+    """A BatchNorm between the conv that produces its input and the kernels that consume its output.  Eval mode fills only
+    scale / shift.  Tile mode fills the four tensors with a bn_finalize launch right after the producer.  Accumulator mode
+    allocates them empty (stats()): the producer adds into its fp64 accumulator row `acc`, and the first consumer - the next
+    conv's prologue, or bn_finalize_acc ahead of a stand-alone kernel - fills them and moves the running statistics."""
+    __slots__ = ("mod", "name", "gamma", "beta", "acc", "mean", "rstd", "scale", "shift")
 
-    def __init__(self, module, tensors):
-        self.t = dict(zip(module._names, tensors))
+    def __init__(self, mod, name, gamma, beta, acc=None):
+        self.mod, self.name, self.gamma, self.beta, self.acc = mod, name, gamma, beta, acc     # name.weight / name.bias = gamma / beta
+        self.mean = self.rstd = self.scale = self.shift = None
 
-    def __getitem__(self, k):
-        return self.t[k]
+    def running(self):
+        return self.mod.running_mean, self.mod.running_var
+
+    def stats(self):
+        self.mean, self.rstd, self.scale, self.shift = (ops._f32(self.gamma.numel(), like=self.gamma) for _ in range(4))
+        return self.mean, self.rstd, self.scale, self.shift
 
 
-def _bn_buffers(bn, training):
-    return (bn.running_mean, bn.running_var) if training else (None, None)
+@dataclass
+class _Block:
+    """Residual block: input h, y1 = conv_a(h), y2 = conv_b(PReLU(bn1(y1))); its output h + bn2(y2) is formed by the next conv."""
+    h: torch.Tensor
+    y1: torch.Tensor
+    bn1: _BN
+    y2: torch.Tensor
+    bn2: _BN
 
 
-def _fast9(module, p):
+@dataclass
+class _Up:
+    """Up-sampling stage: input u (a pre-activation when slope is given), us = PixelShuffle(conv(PReLU(u))).  conv3 is saved as
+    one more stage: us = its output before the clamp."""
+    u: torch.Tensor
+    slope: torch.Tensor | None
+    us: torch.Tensor | None
+
+
+@dataclass
+class _Saved:
+    """What forward() keeps for backward()."""
+    x3: torch.Tensor
+    z1: torch.Tensor
+    blocks: list
+    h_last: torch.Tensor            # conv2's input (a pre-activation, z1, when there are no blocks)
+    y3: torch.Tensor
+    bn3: _BN
+    ups: list
+    last: _Up
+    wd: dict | None                 # data-gradient packs, made by the forward's multi-tensor launch
+    w9: dict
+    fast9: bool
+    acc_mode: bool
+    acc_token: object = None        # accumulator mode: see _Accumulators
+
+
+class _Accumulators:
+    """The fp64 BatchNorm accumulators of the accumulator mode.  ONE buffer (HipState.bn_acc_buf) holds the forward rows
+    [2*nblocks+1, NREP, C, 2] (sum, sum of squares per BatchNorm) and behind them the backward rows [2*nblocks, NREP, C, 4].
+    The training forward clears the whole buffer with a rider on its pack launch (`buf` goes into the riders) and leaves a
+    fresh token on HipState.bn_acc_token and in its saved record.  A backward that still finds its forward's token adds into
+    the clear backward rows; any other (a second backward, or another forward in between) clears them again first.  Every
+    backward drops the token: its rows are dirty from then on."""
+
+    def __init__(self, module, nblocks, C, device):
+        nf, nbk = (2 * nblocks + 1) * ops.ACC_NREP * C * 2, 2 * nblocks * ops.ACC_NREP * C * 4
+        self.st = state(module)
+        buf = self.st.bn_acc_buf
+        if buf is None or buf.numel() != nf + nbk or buf.device != device:
+            buf = self.st.bn_acc_buf = torch.zeros(nf + nbk, device=device, dtype=torch.float64)
+        self.buf, self.nf = buf, nf
+        self.fwd = buf[:nf].view(2 * nblocks + 1, ops.ACC_NREP, C, 2)
+        self.bwd = buf[nf:].view(2 * nblocks, ops.ACC_NREP, C, 4)
+
+    def new_token(self):
+        self.st.bn_acc_token = token = object()
+        return token
+
+    def backward_rows(self, token):
+        if token is None or self.st.bn_acc_token is not token:
+            self.buf[self.nf:].zero_()
+        self.st.bn_acc_token = None
+        return self.bwd
+
+
+def _act(slope):
+    return ACT_SLOPE if slope is not None else 0
+
+
+def _fast9(p):
     """The 9x9 convs take the (kx, 3ch)-folded kernels when their small side has exactly 3 channels (the reference's
     RGB configuration) and C is a multiple of 4 that the wgrad kernel supports."""
     C = p["conv1.0.weight"].shape[0]
@@ -49,12 +126,11 @@ def _conv_names(module, fast9):
     return names
 
 
-def _packs(module, p, with_dgrad, extras=()):
+def _packs(module, p, fast9, with_dgrad, extras=()):
     """All packed weights of the generator from ONE multi-tensor launch: (forward packs by name, data-gradient packs by name or
     None, packs of the (kx, 3ch)-folded 9x9 kernels {"conv1", "conv3", "conv3.dgrad"}).  The data-gradient packs are made by
     the training forward and handed to backward() (the weights do not change in between).  extras: ops.PackPlan's riders."""
     cache = state(module).cache
-    fast9 = _fast9(module, p)
     names = _conv_names(module, fast9)
     ws = [p[n] for n in names]
     modes = [ops.PACK_FWD] * len(ws)
@@ -76,272 +152,184 @@ def _packs(module, p, with_dgrad, extras=()):
     return wp, wd, w9
 
 
-def _bn_accumulators(module, nblocks, C, device, zero, whole=False):
-    """The fp64 statistics accumulators of the accumulator mode, forward [2*nblocks+1][NREP][C][2] and backward
-    [2*nblocks][NREP][C][4], as views of ONE buffer so that one fill at the start of the forward clears both (whole: that buffer)."""
-    nf, nbk = (2 * nblocks + 1) * ops.ACC_NREP * C * 2, 2 * nblocks * ops.ACC_NREP * C * 4
-    buf = state(module).bn_acc_buf
-    if buf is None or buf.numel() != nf + nbk or buf.device != device:
-        buf = state(module).bn_acc_buf = torch.zeros(nf + nbk, device=device, dtype=torch.float64)
-    if whole:
-        return buf
-    if zero == "all":
-        buf.zero_()
-    elif zero == "bwd":
-        buf[nf:].zero_()
-    return buf[:nf].view(2 * nblocks + 1, ops.ACC_NREP, C, 2), buf[nf:].view(2 * nblocks, ops.ACC_NREP, C, 4)
-
-
 def forward(module, x, params, need_grad):
-    p = _P(module, params)
+    p = dict(zip(module._names, params))
     training = module.training
-    sv = {}                                       # saved for backward
     C = p["conv1.0.weight"].shape[0]
+    B, H, W = x.shape[0], x.shape[2], x.shape[3]
+    nb = len(module.trunk)
+    # accumulator mode: no BatchNorm finalize launches - each trunk conv adds its output statistics into fp64 accumulators and
+    # the NEXT conv derives the affine of its input from them in its prologue (csrc/conv_epilogue.h: BandAcc)
+    acc_mode = bool(training and nb and ops.conv_acc_supported(B, H, W, C, C))
+    fast9 = _fast9(p)
     # the batch counters' add and the clearing of the statistics accumulators (two one-line launches at the head of the serial chain)
     # ride in the pack launch
-    B_, H_, W_ = x.shape[0], x.shape[2], x.shape[3]
-    use_acc = bool(training and len(module.trunk) and ops.conv_acc_supported(B_, H_, W_, C, C))
     extras = []
     counters = ops.flatten_bn_counters(module) if training else None
     if counters is not None:
         extras.append(("add", counters, 1))
-    if use_acc:
-        extras.append(("zero", _bn_accumulators(module, len(module.trunk), C, x.device, zero=None, whole=True)))
-    wp, sv["wd"], w9 = _packs(module, p, need_grad, tuple(extras))
-    sv["w9"] = w9
+    if acc_mode:
+        accs = _Accumulators(module, nb, C, x.device)
+        extras.append(("zero", accs.buf))
+    wp, wd, w9 = _packs(module, p, fast9, need_grad, tuple(extras))
+    acc_token = accs.new_token() if acc_mode else None
     x3 = ops.transpose(x.contiguous(), to_nchw=False)                                  # [B,h,w,3]
-    fast9 = _fast9(module, p)
     if fast9:
         z1 = ops.conv9_c3_fwd(x3, p["conv1.0.weight"], 0, bias=p["conv1.0.bias"], wp=w9["conv1"])
     else:
         z1, _, _, _ = ops.conv_fwd(x3, wp["conv1.0.weight"], C, 9, 1, bias=p["conv1.0.bias"])
     a1 = p["conv1.1.weight"]
-    sv["x3"], sv["z1"] = x3, z1
+    n_px = float(B * H * W)
 
-    def bn_affine(bn, pre, stats, cnt):
-        if training:
-            mean, rstd, scale, shift = ops.bn_finalize(stats, cnt, p[pre + ".weight"], p[pre + ".bias"],
-                                                       bn.running_mean, bn.running_var)
-            return mean, rstd, scale, shift
-        scale, shift = ops.bn_eval_affine(p[pre + ".weight"], p[pre + ".bias"], bn.running_mean, bn.running_var)
-        return None, None, scale, shift
+    def link(mod, name, k):          # the k-th BatchNorm of the trunk
+        return _BN(mod, name, p[name + ".weight"], p[name + ".bias"], accs.fwd[k] if acc_mode else None)
 
-    h = z1
-    blocks = []
-    n_px = float(B_ * H_ * W_)
-    if use_acc:
-        # ---- accumulator mode: no BatchNorm finalize launches - each conv adds its output statistics into fp64 accumulators and
-        # the NEXT conv derives the affine of its input from them in its prologue (csrc/conv_epilogue.h: BandAcc)
-        nbn = 2 * len(module.trunk) + 1
-        acc, _ = _bn_accumulators(module, len(module.trunk), C, z1.device, zero=None)       # cleared by the pack launch above
-        sv["acc_token"] = state(module).bn_acc_token = object()      # backward: its accumulators are still clear
-
-        def stat_tensors():
-            return tuple(ops._f32(C, like=z1) for _ in range(4))
-
-        pend = None       # (x, y2, acc2, bn2 module, prefix, (m2, r2, s2, t2)): residual sum formed by the next conv
-        for i, blk in enumerate(module.trunk):
-            pre = f"trunk.{i}.rcb"
-            first = i == 0
-            a_k1, a_k2 = acc[2 * i], acc[2 * i + 1]
-            if pend is None:
-                y1, _ = ops.conv_fwd_acc(h, wp[pre + ".0.weight"], C, 3, in_slope=a1 if first else None,
-                                         in_act=ACT_SLOPE if first else 0, st_acc=a_k1)
-            else:
-                px, py2, pacc, pbn, ppre, pst = pend
-                y1, h = ops.conv_fwd_acc(px, wp[pre + ".0.weight"], C, 3, in2=py2, in_acc=pacc, in_bn=(p[ppre + ".weight"], p[ppre + ".bias"]),
-                                         n=n_px, out_stats=pst, run_stats=(pbn.running_mean, pbn.running_var), st_acc=a_k1)
-            st1 = stat_tensors()
-            y2, _ = ops.conv_fwd_acc(y1, wp[pre + ".3.weight"], C, 3, in_slope=p[pre + ".2.weight"], in_act=ACT_SLOPE, in_acc=a_k1,
-                                     in_bn=(p[pre + ".1.weight"], p[pre + ".1.bias"]), n=n_px, out_stats=st1,
-                                     run_stats=(blk.rcb[1].running_mean, blk.rcb[1].running_var), st_acc=a_k2)
-            if first:     # the skip term is PReLU(z1): stand-alone finalize + residual kernel for this one block
-                st2 = ops.bn_finalize_acc(a_k2, n_px, p[pre + ".4.weight"], p[pre + ".4.bias"], blk.rcb[4].running_mean,
-                                          blk.rcb[4].running_var)
-                blocks.append((h, y1, *st1, y2, *st2))
-                h, pend = ops.bn_residual(y2, st2[2], st2[3], h, a1), None
-            else:
-                st2 = stat_tensors()
-                blocks.append((h, y1, *st1, y2, *st2))
-                pend = (h, y2, a_k2, blk.rcb[4], pre + ".4", st2)
-        a_k3 = acc[nbn - 1]
-        if pend is None:
-            y3, _ = ops.conv_fwd_acc(h, wp["conv2.0.weight"], C, 3, st_acc=a_k3)
+    def conv(t, w, out_bn, in_bn=None, slope=None, pend=None):
+        """One trunk conv, its output statistics going to out_bn.  Input: PReLU_slope(in_bn(t)), or - pend, a _Block - that
+        block's output pend.h + bn2(pend.y2), formed while staging.  -> (y, the input: t, or the sum just formed)."""
+        src = pend.bn2 if pend else in_bn
+        if acc_mode:
+            kw = dict(in_acc=src.acc, in_bn=(src.gamma, src.beta), n=n_px, out_stats=src.stats(), run_stats=src.running()) if src else {}
+            y, h = ops.conv_fwd_acc(pend.h if pend else t, w, C, 3, in2=pend.y2 if pend else None, in_slope=slope, in_act=_act(slope),
+                                    st_acc=out_bn.acc, **kw)
         else:
-            px, py2, pacc, pbn, ppre, pst = pend
-            y3, h = ops.conv_fwd_acc(px, wp["conv2.0.weight"], C, 3, in2=py2, in_acc=pacc, in_bn=(p[ppre + ".weight"], p[ppre + ".bias"]),
-                                     n=n_px, out_stats=pst, run_stats=(pbn.running_mean, pbn.running_var), st_acc=a_k3)
-        m3, r3, s3, t3 = ops.bn_finalize_acc(a_k3, n_px, p["conv2.1.weight"], p["conv2.1.bias"], module.conv2[1].running_mean,
-                                             module.conv2[1].running_var)
-    else:
-        h = z1
-        blocks = []
-        pend = None       # (x, y2, scale2, shift2): the previous block's output h = x + BN2(y2), not materialised yet - the next
-                          # conv forms it while staging its input and hands it back (one bn_residual launch less per block)
-        for i, blk in enumerate(module.trunk):
-            pre = f"trunk.{i}.rcb"
-            first = i == 0
-            if pend is None:
-                y1, _, st, cnt = ops.conv_fwd(h, wp[pre + ".0.weight"], C, 3, 1,
-                                              in_slope=a1 if first else None, in_act=ACT_SLOPE if first else 0,
-                                              want_stats=training)
+            if pend:
+                y, h, st, cnt = ops.conv_fwd_resin(pend.h, pend.y2, src.scale, src.shift, w, C, 3, want_stats=training)
             else:
-                y1, h, st, cnt = ops.conv_fwd_resin(*pend, wp[pre + ".0.weight"], C, 3, want_stats=training)
-            m1, r1, s1, t1 = bn_affine(blk.rcb[1], pre + ".1", st, cnt)
-            y2, _, st, cnt = ops.conv_fwd(y1, wp[pre + ".3.weight"], C, 3, 1, in_scale=s1, in_shift=t1,
-                                          in_slope=p[pre + ".2.weight"], in_act=ACT_SLOPE, want_stats=training)
-            m2, r2, s2, t2 = bn_affine(blk.rcb[4], pre + ".4", st, cnt)
-            blocks.append((h, y1, m1, r1, s1, t1, y2, m2, r2, s2, t2))
-            if first:     # the skip term is PReLU(z1) here: keep the stand-alone residual kernel
-                h, pend = ops.bn_residual(y2, s2, t2, h, a1), None
+                y, h, st, cnt = ops.conv_fwd(t, w, C, 3, 1, in_scale=src.scale if src else None, in_shift=src.shift if src else None,
+                                             in_slope=slope, in_act=_act(slope), want_stats=training)
+            if training:
+                out_bn.mean, out_bn.rstd, out_bn.scale, out_bn.shift = ops.bn_finalize(st, cnt, out_bn.gamma, out_bn.beta, *out_bn.running())
             else:
-                pend = (h, y2, s2, t2)
-        if pend is None:
-            y3, _, st, cnt = ops.conv_fwd(h, wp["conv2.0.weight"], C, 3, 1, want_stats=training)
+                out_bn.scale, out_bn.shift = ops.bn_eval_affine(out_bn.gamma, out_bn.beta, *out_bn.running())
+        return y, h if pend else t
+
+    def materialise(bn):             # ahead of a stand-alone consumer (tile / eval mode: done right after the producer)
+        if acc_mode:
+            bn.mean, bn.rstd, bn.scale, bn.shift = ops.bn_finalize_acc(bn.acc, n_px, bn.gamma, bn.beta, *bn.running())
+
+    h, slope = z1, a1     # slope: h is a pre-activation whose PReLU the consumer applies on load (z1 only)
+    pend = None           # the previous block while its output h + bn2(y2) is not materialised yet: the next conv forms it while
+    blocks = []           # staging its input and hands it back (one bn_residual launch less per block)
+    for i, blk in enumerate(module.trunk):
+        pre = f"trunk.{i}.rcb"
+        bn1, bn2 = link(blk.rcb[1], pre + ".1", 2 * i), link(blk.rcb[4], pre + ".4", 2 * i + 1)
+        y1, h = conv(h, wp[pre + ".0.weight"], bn1, slope=slope, pend=pend)
+        y2, _ = conv(y1, wp[pre + ".3.weight"], bn2, in_bn=bn1, slope=p[pre + ".2.weight"])
+        blocks.append(_Block(h, y1, bn1, y2, bn2))
+        if i == 0:        # the skip term is PReLU(z1): stand-alone residual kernel for this one block
+            materialise(bn2)
+            h, slope = ops.bn_residual(y2, bn2.scale, bn2.shift, h, a1), None
         else:
-            y3, h, st, cnt = ops.conv_fwd_resin(*pend, wp["conv2.0.weight"], C, 3, want_stats=training)
-        m3, r3, s3, t3 = bn_affine(module.conv2[1], "conv2.1", st, cnt)
-    u = ops.bn_residual(y3, s3, t3, z1, a1)
-    sv["blocks"], sv["h_last"], sv["conv2"] = blocks, h, (y3, m3, r3, s3, t3)
+            pend = blocks[-1]
+    bn3 = link(module.conv2[1], "conv2.1", 2 * nb)
+    y3, h = conv(h, wp["conv2.0.weight"], bn3, slope=slope, pend=pend)
+    materialise(bn3)
+    u = ops.bn_residual(y3, bn3.scale, bn3.shift, z1, a1)
     ups = []
     slope = None
     for j, _ in enumerate(module.upsampling):
         pre = f"upsampling.{j}.upsample_block"
         us, _, _, _ = ops.conv_fwd(u, wp[pre + ".0.weight"], 4 * C, 3, 1, bias=p[pre + ".0.bias"],
-                                   in_slope=slope, in_act=ACT_SLOPE if slope is not None else 0, out_mode=OUT_SHUFFLE)
-        ups.append((u, slope, us))
+                                   in_slope=slope, in_act=_act(slope), out_mode=OUT_SHUFFLE)
+        ups.append(_Up(u, slope, us))
         u, slope = us, p[pre + ".2.weight"]
-    sv["ups"] = ups
-    cout = p["conv3.weight"].shape[0]
     if fast9:
-        sr, sr_pre = ops.conv9_to3_fwd(u, p["conv3.weight"], bias=p["conv3.bias"], in_slope=slope,
-                                       in_act=ACT_SLOPE if slope is not None else 0, want_pre=need_grad, wp=w9["conv3"])
+        sr, sr_pre = ops.conv9_to3_fwd(u, p["conv3.weight"], bias=p["conv3.bias"], in_slope=slope, in_act=_act(slope),
+                                       want_pre=need_grad, wp=w9["conv3"])
     else:
-        sr, sr_pre, _, _ = ops.conv_fwd(u, wp["conv3.weight"], cout, 9, 1, bias=p["conv3.bias"], in_slope=slope,
-                                        in_act=ACT_SLOPE if slope is not None else 0, out_mode=OUT_NCHW_CLAMP,
-                                        want_pre=need_grad)
-    sv["last"] = (u, slope, sr_pre)
-    return sr, sv
+        sr, sr_pre, _, _ = ops.conv_fwd(u, wp["conv3.weight"], p["conv3.weight"].shape[0], 9, 1, bias=p["conv3.bias"], in_slope=slope,
+                                        in_act=_act(slope), out_mode=OUT_NCHW_CLAMP, want_pre=need_grad)
+    return sr, _Saved(x3, z1, blocks, h, y3, bn3, ups, _Up(u, slope, sr_pre), wd, w9, fast9, acc_mode, acc_token)
 
 
 def backward(module, params, sv, dsr, need_dx=False):
     """-> list of gradients in module._names order."""
-    p = _P(module, params)
+    p = dict(zip(module._names, params))
     grads = ops.flat_grads(module, module._names, params)      # views of ONE flat buffer (single RCCL message)
     C = p["conv1.0.weight"].shape[0]
     a1 = p["conv1.1.weight"]
-    wd, w9 = sv["wd"], sv["w9"]                  # packed by the forward's multi-tensor launch
+    wd, w9, fast9 = sv.wd, sv.w9, sv.fast9
     wg = ops.WgradGroup()            # the trunk-shaped weight gradients go out as ONE launch at the end
 
-    def leaf(launch, *tensors):      # a weight gradient: a leaf of the backward chain
-        with ops.SideStream(*tensors):
-            launch()
-
-    def rows(t):
-        return t.numel() // t.shape[-1]
-
     # ---- conv3 + clamp
-    u, slope, sr_pre = sv["last"]
-    g3 = ops.clamp_bwd(dsr.contiguous(), sr_pre, dbias=grads["conv3.bias"])
-    fast9 = _fast9(module, p)
-    def w_conv3(u=u, g3=g3, slope=slope):
+    u, slope = sv.last.u, sv.last.slope
+    g3 = ops.clamp_bwd(dsr.contiguous(), sv.last.us, dbias=grads["conv3.bias"])
+    with ops.SideStream(u, g3, grads["conv3.weight"]):      # a weight gradient: a leaf of the backward chain
         if fast9:
-            ops.wgrad_c3(u, g3, grads["conv3.weight"], 0, in_slope=slope, in_act=ACT_SLOPE if slope is not None else 0)
+            ops.wgrad_c3(u, g3, grads["conv3.weight"], 0, in_slope=slope, in_act=_act(slope))
         else:
-            ops.conv_wgrad(u, g3, grads["conv3.weight"], 9, 1, in_slope=slope, in_act=ACT_SLOPE if slope is not None else 0)
-    leaf(w_conv3, u, g3, grads["conv3.weight"])
+            ops.conv_wgrad(u, g3, grads["conv3.weight"], 9, 1, in_slope=slope, in_act=_act(slope))
     if fast9:
         g = ops.conv9_c3_fwd(g3, p["conv3.weight"], 1, wp=w9["conv3.dgrad"])              # d PReLU(u)
     else:
         g = ops.conv_fwd(g3, wd["conv3.weight"], C, 9, 1)[0]
     # ---- up-sampling blocks, last to first
-    for j in reversed(range(len(sv["ups"]))):
+    for j, up in reversed(list(enumerate(sv.ups))):
         pre = f"upsampling.{j}.upsample_block"
-        u_in, slope_in, us = sv["ups"][j]
-        sl = p[pre + ".2.weight"]
         # PReLU backward + inverse PixelShuffle + the partial sums of (conv bias, slope) gradients in ONE pass, one finalize
-        du = ops.act_bwd(g, us, slope=sl, dbias=grads[pre + ".0.bias"], dslope=grads[pre + ".2.weight"],
+        du = ops.act_bwd(g, up.us, slope=p[pre + ".2.weight"], dbias=grads[pre + ".0.bias"], dslope=grads[pre + ".2.weight"],
                          unshuffle=True)                                             # [B,h,w,4C] pre-shuffle grad
-        def w_up(u_in=u_in, du=du, pre=pre, slope_in=slope_in):
-            ops.conv_wgrad(u_in, du, grads[pre + ".0.weight"], 3, 1, in_slope=slope_in,
-                           in_act=ACT_SLOPE if slope_in is not None else 0)
-        leaf(w_up, u_in, du, grads[pre + ".0.weight"])
+        with ops.SideStream(up.u, du, grads[pre + ".0.weight"]):
+            ops.conv_wgrad(up.u, du, grads[pre + ".0.weight"], 3, 1, in_slope=up.slope, in_act=_act(up.slope))
         g = ops.conv_fwd(du, wd[pre + ".0.weight"], C, 3, 1)[0]    # d (input of the up-conv)
     # ---- u = BN(conv2(h_last)) + PReLU(z1)
-    y3, m3, r3, s3, t3 = sv["conv2"]
-    n = rows(y3)
-    dy3 = ops.bwd_reduce_apply(g, y3, n, scale=s3, shift=t3, mean=m3, rstd=r3, gamma=p["conv2.1.weight"],
+    y3, bn3, blocks = sv.y3, sv.bn3, sv.blocks
+    nb = len(blocks)
+    n = y3.numel() // y3.shape[-1]
+    dy3 = ops.bwd_reduce_apply(g, y3, n, scale=bn3.scale, shift=bn3.shift, mean=bn3.mean, rstd=bn3.rstd, gamma=bn3.gamma,
                                dgamma=grads["conv2.1.weight"], dbeta=grads["conv2.1.bias"])
-    wg.add(sv["h_last"], dy3, grads["conv2.0.weight"], 3, 1,
-           in_slope=a1 if not sv["blocks"] else None, in_act=ACT_SLOPE if not sv["blocks"] else 0)
+    wg.add(sv.h_last, dy3, grads["conv2.0.weight"], 3, 1, in_slope=None if nb else a1, in_act=0 if nb else ACT_SLOPE)
     dskip = g
-    nb = len(sv["blocks"])
-    Bq, Hq, Wq, _ = y3.shape
-    if nb and ops.conv_acc_supported(Bq, Hq, Wq, C, C):
-        # ---- accumulator mode: every data-gradient conv adds the BatchNorm-backward sums of its result into fp64 accumulators,
-        # the next stage derives its coefficients from them in its prologue (no finalize launches between the stages)
-        _, bacc = _bn_accumulators(module, nb, C, y3.device, zero="bwd" if sv.get("acc_token") is None or
-                                   state(module).bn_acc_token is not sv.get("acc_token") else None)
-        state(module).bn_acc_token = None          # the backward accumulators are dirty from here on
-        dh, _ = ops.conv_dgrad_fused_acc(dy3, wd["conv2.0.weight"], C, 3, epi_y=sv["blocks"][-1][6], bw_st_acc=bacc[2 * nb - 1])
-        for i in reversed(range(nb)):
-            pre = f"trunk.{i}.rcb"
-            first = i == 0
-            h, y1, m1, r1, s1, t1, y2, m2, r2, s2, t2 = sv["blocks"][i]
-            sl = p[pre + ".2.weight"]
-            # stage 2 (BN2, no activation): [coefficients + apply + dgrad conv_b + sums for stage 1] in one launch
-            dp1, dy2 = ops.conv_dgrad_fused_acc(dh, wd[pre + ".3.weight"], C, 3, y2=y2, epi_y=y1, epi_scale=s1, epi_shift=t1, epi_slope=sl,
-                                                epi_act=1, bw_in_acc=bacc[2 * i + 1], bn=(m2, r2, p[pre + ".4.weight"]), n=n,
-                                                dgamma=grads[pre + ".4.weight"], dbeta=grads[pre + ".4.bias"], bw_st_acc=bacc[2 * i])
-            wg.add(y1, dy2, grads[pre + ".3.weight"], 3, 1, in_scale=s1, in_shift=t1, in_slope=sl, in_act=ACT_SLOPE)
-            # stage 1 (BN1 + PReLU)
-            prev_y2 = None if first else sv["blocks"][i - 1][6]
-            dh, dy1 = ops.conv_dgrad_fused_acc(dp1, wd[pre + ".0.weight"], C, 3, y2=y1, in_scale=s1, in_shift=t1, in_slope=sl,
-                                               in_act=ACT_SLOPE, residual=dh, epi_y=prev_y2, bw_in_acc=bacc[2 * i],
-                                               bn=(m1, r1, p[pre + ".1.weight"]), n=n, dgamma=grads[pre + ".1.weight"],
-                                               dbeta=grads[pre + ".1.bias"], dslope=grads[pre + ".2.weight"],
-                                               bw_st_acc=None if first else bacc[2 * i - 1])
-            wg.add(h, dy1, grads[pre + ".0.weight"], 3, 1, in_slope=a1 if first else None, in_act=ACT_SLOPE if first else 0)
+    # Every trunk data-gradient conv also emits the BatchNorm-backward sums of its result against the conv output the NEXT stage
+    # differentiates through.  Tile mode: per-tile partials (`part`), a bwd_finalize launch ahead of each stage.  Accumulator mode:
+    # fp64 accumulator rows (bacc), each stage derives its coefficients from them in its prologue.
+    bacc = _Accumulators(module, nb, C, y3.device).backward_rows(sv.acc_token) if sv.acc_mode else None
+    part = None
+    if not nb:
+        dh = ops.conv_fwd(dy3, wd["conv2.0.weight"], C, 3, 1)[0]
+    elif sv.acc_mode:
+        dh, _ = ops.conv_dgrad_fused_acc(dy3, wd["conv2.0.weight"], C, 3, epi_y=blocks[-1].y2, bw_st_acc=bacc[2 * nb - 1])
     else:
-        # every stride-1 data-gradient conv below also emits the BatchNorm-backward partial sums of its result against the
-        # conv output the NEXT backward stage differentiates through (saves one reduction pass per stage)
-        if nb:
-            dh, part = ops.conv_dgrad_bwdstats(dy3, wd["conv2.0.weight"], C, 3, sv["blocks"][-1][6])        # vs y2 of the last block
-        else:
-            dh, part = ops.conv_fwd(dy3, wd["conv2.0.weight"], C, 3, 1)[0], None
-        # ---- residual blocks, last to first
-        for i in reversed(range(nb)):
-            pre = f"trunk.{i}.rcb"
-            first = i == 0
-            h, y1, m1, r1, s1, t1, y2, m2, r2, s2, t2 = sv["blocks"][i]
-            sl = p[pre + ".2.weight"]
-            # stage 2 (BN2, no activation): finalize -> [apply + dgrad conv_b + partials for stage 1] in one launch
-            cA, cB, cC = ops.bwd_finalize(part, n, m2, r2, p[pre + ".4.weight"], grads[pre + ".4.weight"], grads[pre + ".4.bias"])
-            dp1, dy2, part = ops.conv_dgrad_fused(dh, y2, wd[pre + ".3.weight"], C, 3, cA, cB, cC, epi_y=y1, epi_scale=s1,
-                                                  epi_shift=t1, epi_slope=sl, epi_act=1)
-            wg.add(y1, dy2, grads[pre + ".3.weight"], 3, 1, in_scale=s1, in_shift=t1, in_slope=sl, in_act=ACT_SLOPE)
-            # stage 1 (BN1 + PReLU)
-            cA, cB, cC = ops.bwd_finalize(part, n, m1, r1, p[pre + ".1.weight"], grads[pre + ".1.weight"], grads[pre + ".1.bias"],
-                                          dslope=grads[pre + ".2.weight"])
-            prev_y2 = None if first else sv["blocks"][i - 1][6]
-            dh, dy1, part = ops.conv_dgrad_fused(dp1, y1, wd[pre + ".0.weight"], C, 3, cA, cB, cC, in_scale=s1, in_shift=t1,
-                                                 in_slope=sl, in_act=ACT_SLOPE, residual=dh, epi_y=prev_y2)
-            wg.add(h, dy1, grads[pre + ".0.weight"], 3, 1, in_slope=a1 if first else None, in_act=ACT_SLOPE if first else 0)
+        dh, part = ops.conv_dgrad_bwdstats(dy3, wd["conv2.0.weight"], C, 3, blocks[-1].y2)
+
+    def stage(g, y, bn, k, w, part, epi_y, dslope=None, **kw):
+        """One BatchNorm-backward stage: dy = g through bn (the k-th of the trunk) against its input y, out = data-gradient conv
+        of dy, with the sums of `out` against epi_y (if any) for the next stage, BatchNorm k - 1.  -> (out, dy, part)."""
+        dgamma, dbeta = grads[bn.name + ".weight"], grads[bn.name + ".bias"]
+        if sv.acc_mode:
+            out, dy = ops.conv_dgrad_fused_acc(g, w, C, 3, y2=y, epi_y=epi_y, bw_in_acc=bacc[k], bn=(bn.mean, bn.rstd, bn.gamma), n=n,
+                                               dgamma=dgamma, dbeta=dbeta, dslope=dslope,
+                                               bw_st_acc=None if epi_y is None else bacc[k - 1], **kw)
+            return out, dy, None
+        cA, cB, cC = ops.bwd_finalize(part, n, bn.mean, bn.rstd, bn.gamma, dgamma, dbeta, dslope=dslope)
+        return ops.conv_dgrad_fused(g, y, w, C, 3, cA, cB, cC, epi_y=epi_y, **kw)
+
+    # ---- residual blocks, last to first
+    for i, b in reversed(list(enumerate(blocks))):
+        pre = f"trunk.{i}.rcb"
+        s1, t1, sl = b.bn1.scale, b.bn1.shift, p[pre + ".2.weight"]
+        # stage 2 (BN2, no activation)
+        dp1, dy2, part = stage(dh, b.y2, b.bn2, 2 * i + 1, wd[pre + ".3.weight"], part, b.y1,
+                               epi_scale=s1, epi_shift=t1, epi_slope=sl, epi_act=1)
+        wg.add(b.y1, dy2, grads[pre + ".3.weight"], 3, 1, in_scale=s1, in_shift=t1, in_slope=sl, in_act=ACT_SLOPE)
+        # stage 1 (BN1 + PReLU); its sums are against y2 of the block before
+        dh, dy1, part = stage(dp1, b.y1, b.bn1, 2 * i, wd[pre + ".0.weight"], part, blocks[i - 1].y2 if i else None,
+                              dslope=grads[pre + ".2.weight"], in_scale=s1, in_shift=t1, in_slope=sl, in_act=ACT_SLOPE, residual=dh)
+        wg.add(b.h, dy1, grads[pre + ".0.weight"], 3, 1, in_slope=None if i else a1, in_act=0 if i else ACT_SLOPE)
     # ---- c1 = PReLU(z1): gradient = trunk path (dh) + global skip (dskip)
-    z1 = sv["z1"]
-    dz1 = ops.act_bwd(dh, z1, g2=dskip, slope=a1, dbias=grads["conv1.0.bias"], dslope=grads["conv1.1.weight"])
-    def w_conv1(dz1=dz1, x3=sv["x3"]):
+    dz1 = ops.act_bwd(dh, sv.z1, g2=dskip, slope=a1, dbias=grads["conv1.0.bias"], dslope=grads["conv1.1.weight"])
+    with ops.SideStream(dz1, sv.x3, grads["conv1.0.weight"]):
         if fast9:
-            ops.wgrad_c3(dz1, x3, grads["conv1.0.weight"], 1)
+            ops.wgrad_c3(dz1, sv.x3, grads["conv1.0.weight"], 1)
         else:
-            ops.conv_wgrad(x3, dz1, grads["conv1.0.weight"], 9, 1)
-    leaf(w_conv1, dz1, sv["x3"], grads["conv1.0.weight"])
+            ops.conv_wgrad(sv.x3, dz1, grads["conv1.0.weight"], 9, 1)
     wg.run()
     ops.join_side()
     dx = None
     if need_dx:
         wd1 = ops.pack_conv(p["conv1.0.weight"], 1) if fast9 else wd["conv1.0.weight"]
-        dx3 = ops.conv_fwd(dz1, wd1, sv["x3"].shape[-1], 9, 1)[0]
+        dx3 = ops.conv_fwd(dz1, wd1, sv.x3.shape[-1], 9, 1)[0]
         dx = ops.transpose(dx3, to_nchw=True)
     return [grads[n] for n in module._names], dx
 

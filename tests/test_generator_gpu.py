@@ -263,3 +263,46 @@ def test_accumulator_mode_run_to_run(capsys):
     with capsys.disabled():
         print(f"\\n[accumulator mode, 3 runs] worst run-to-run difference {worst:.2e}; {identical} of {2 * len(runs[0])} tensor pairs bit-identical")
     assert worst < 1e-6
+
+
+@pytest.mark.parametrize("ch,size,acc", [(64, 12, True), (64, 20, False), (8, 12, False)])
+@pytest.mark.parametrize("n_rcb", [0, 1, 2])
+def test_generator_few_blocks_vs_oracle(n_rcb, ch, size, acc):
+    """The edges of the pending-residual logic of gen_graph's trunk walk: no block (conv2 consumes PReLU(z1), its weight
+    gradient takes the slope of conv1's PReLU), the special first block alone (nothing ever pending, conv2 gets a materialised
+    h), two blocks (the first pending residual sum is formed by conv2) - in accumulator mode (64 channels, W = 12: 4-row bands)
+    and in tile mode (W = 20 divides neither 48 nor 144; 8 channels).  SR, loss, every gradient and the BatchNorm running
+    statistics after the step against the CPU oracle."""
+    from oracle import model as om
+    from oracle import st as ost
+    from srganst import ops
+    from srganst.model import Generator
+    from srganst.loss import MSELoss, StructureTensorLoss
+    assert bool(ops.conv_acc_supported(2, size, size, ch, ch)) == acc
+    torch.manual_seed(21 + n_rcb)
+    G = Generator(make_cfg(ch, n_rcb))
+    gen = torch.Generator().manual_seed(22)
+    lr = torch.rand(2, 3, size, size, generator=gen)
+    gt = torch.rand(2, 3, 4 * size, 4 * size, generator=gen)
+    sd = {k: v.clone() for k, v in G.state_dict().items()}
+    bufs = {}
+
+    def fl(sdx, lr_, gt_):
+        sr_ = om.generator_forward(sdx, lr_, True, bufs, n_rcb=n_rcb)        # bufs: of the later (fp64) run in the end
+        return torch.nn.functional.mse_loss(sr_, gt_) + ost.st_loss(sr_, gt_) / 3, sr_
+    ins = ((lr, False), (gt, False))
+    l_ref, g32, _, (sr_ref,) = oracle_grads(fl, sd, torch.float32, ins)
+    _, g64, _, _ = oracle_grads(fl, sd, torch.float64, ins)
+    G.cuda().train()
+    sr = G(lr.cuda())
+    loss = MSELoss()(sr, gt.cuda()) + StructureTensorLoss()(sr, gt.cuda()) * (1 / 3)
+    loss.backward()
+    assert sr.shape == gt.shape
+    assert rel_err(sr.detach().cpu(), sr_ref) < 1e-3
+    assert abs(loss.item() - l_ref.item()) < 1e-3 * abs(l_ref.item())
+    for n, p in G.named_parameters():
+        assert_fp64_truth(n, p.grad.cpu(), g32[n], g64[n])
+    running = {k: v.cpu() for k, v in G.state_dict().items() if "running" in k}
+    assert len(running) == 2 * (2 * n_rcb + 1) and set(running) <= set(bufs)
+    for k, v in running.items():
+        assert torch.allclose(v, bufs[k].detach().float(), rtol=1e-3, atol=1e-4), k

@@ -49,7 +49,7 @@ params = [p.detach() for p in G.parameters()]
 names = [n for n, _ in G.named_parameters()]
 with torch.no_grad():
     sr, sv = gen_graph.forward(G, lr.cuda(), params, True)
-    u, slope, sr_pre = sv["last"]
+    sr_pre = sv.last.us
     n = sr.numel()
     dsr = (2.0 / n) * (sr - gt.cuda())
     grads, _ = gen_graph.backward(G, params, sv, dsr)
