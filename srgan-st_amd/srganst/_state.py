@@ -58,7 +58,7 @@ class HipState:
         # D(sr) in the generator step, D(gt) and D(sr) in its own step).  An owner controls those updates (engine.TrainEngine: D's
         # packed weights are made once per iteration, by the D(sr) of the generator step, and re-used by the passes of the
         # discriminator step) and clears packs_fresh after every optimizer step; while there is an owner and the packs are fresh
-        # (and no parameter was rebound or modified through torch, see _version) disc_graph._packs hands the packed buffers out again
+        # (and no parameter was rebound or modified through torch, see _version) disc_graph.packs hands the packed buffers out again
         # without a launch.  Without an owner every call packs.
         self.owner = None
         self.packs_fresh = False

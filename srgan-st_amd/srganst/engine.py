@@ -369,7 +369,7 @@ class TrainEngine:
                 main, side = torch.cuda.current_stream(), self._side_stream()
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    disc_graph._packs(self.D, disc_graph.param_dict(self.D)[1], True, counter_add=counter_add)
+                    disc_graph.packs(self.D, disc_graph.param_dict(self.D)[1], True, counter_add=counter_add)
             sr = self.G(self.lr)
             if early_pack:
                 main.wait_stream(side)               # D(sr) below reads the packed weights
@@ -478,7 +478,7 @@ class TrainEngine:
                 pred_gt, sv_gt = disc_graph.forward(D, self.gt, pd, True, True, arena=(kept.arena, 0))
                 disc_graph.replay_running_stats(D, pd, kept.sv)
                 self.d_sr_reused = True
-                return self._d_cls_batched(pd, names, pred_gt, kept.out.detach(), disc_graph.batched_saved(kept.arena, sv_gt))
+                return self._d_cls_batched(pd, names, pred_gt, kept.out.detach(), kept.arena.all_slots(sv_gt))
         pred_gt, sv_gt = disc_graph.forward(D, self.gt, pd, True, True)
         loss_real, dl_gt = ops.bce_logits(pred_gt, self.real, want_loss=True, want_grad=True)
         # D(sr.detach()) (train.py:158) repeats the generator step's D(sr) (train.py:136): same input, same weights (D's Adam comes
@@ -495,10 +495,9 @@ class TrainEngine:
             pred_sr, sv_sr = disc_graph.forward(D, self.sr, pd, True, True)
         loss_fake, dl_sr = ops.bce_logits(pred_sr, self.fake, want_loss=True, want_grad=True)
         self.d_loss, self.pred_gt, self.pred_sr = loss_real + loss_fake, pred_gt, pred_sr
-        with ds.accumulating_grads():
-            st_sr = disc_graph.backward_classifier(D, pd, sv_sr, dl_sr, True)
-            st_gt = disc_graph.backward_classifier(D, pd, sv_gt, dl_gt, True)
-        self._d_state = (pd, sv_sr, st_sr, sv_gt, st_gt)
+        with ds.accumulating_grads():      # backward order: the D(sr) pass first, the D(gt) pass adds into its buffer
+            passes = [(sv, disc_graph.backward_classifier(D, pd, sv, dl, True)) for sv, dl in ((sv_sr, dl_sr), (sv_gt, dl_gt))]
+        self._d_state = (pd, passes)
         self._cut_d_buckets(pd, names)
         return self.d_loss
 
@@ -511,8 +510,7 @@ class TrainEngine:
         loss_real, _ = ops.bce_logits(pred_gt, self.real, want_loss=True, want_grad=True, grad_out=dl[:B])
         loss_fake, _ = ops.bce_logits(pred_sr, self.fake, want_loss=True, want_grad=True, grad_out=dl[B:])
         self.d_loss, self.pred_gt, self.pred_sr = loss_real + loss_fake, pred_gt, pred_sr
-        st = disc_graph.backward_classifier(self.D, pd, sv, dl, True)
-        self._d_state = (pd, None, None, sv, st)
+        self._d_state = (pd, [(sv, disc_graph.backward_classifier(self.D, pd, sv, dl, True))])
         self.d_batched = True
         self._cut_d_buckets(pd, names)
         return self.d_loss
@@ -526,16 +524,17 @@ class TrainEngine:
         self._d_buckets = (flat[cut:total], flat[:cut])
 
     def _d_features(self, defer_gt_wgrad=None):
-        """defer_gt_wgrad (a list; passes run one by one only): the conv weight gradients of the D(gt) pass are handed back instead of
+        """The feature-stack backward of the passes _d_fwd_cls left in self._d_state = (parameters, [(saved pass, its gradient sink)] in
+        backward order): both passes as one batch, or D(sr) and then D(gt).  The first pass's gradients become p.grad.
+        defer_gt_wgrad (a list; passes run one by one only): the conv weight gradients of the D(gt) pass are handed back instead of
         launched (disc_graph.backward_features); they ADD into what the D(sr) pass wrote, which is complete by then on this stream."""
         from . import disc_graph
-        pd, sv_sr, st_sr, sv_gt, st_gt = self._d_state
-        if sv_sr is None:               # both passes as one batch (_d_fwd_cls): one backward
-            grads, _ = disc_graph.backward_features(self.D, pd, sv_gt, st_gt, True, False)
-        else:
-            grads, _ = disc_graph.backward_features(self.D, pd, sv_sr, st_sr, True, False)
-            disc_graph.backward_features(self.D, pd, sv_gt, st_gt, True, False, defer_wgrad=defer_gt_wgrad,
-                                         defer_below=int(self.config.KERNEL.DEFER_D_WGRAD))
+        pd, passes = self._d_state
+        for i, (sv, sink) in enumerate(passes):
+            out, _ = disc_graph.backward_features(self.D, pd, sv, sink, True, False, defer_wgrad=defer_gt_wgrad if i else None,
+                                                  defer_below=int(self.config.KERNEL.DEFER_D_WGRAD))
+            if i == 0:
+                grads = out
         for n, p in self.D.named_parameters():
             p.grad = grads[n]
 

@@ -156,6 +156,11 @@ def conv_pipe_groups_ok(B, H, W, cin, cout, ksize, stride, grp):
         bool(_abi.lib().sst_conv_pipe_groups_ok(B, H, W, cin, cout, ksize, stride, int(grp)))
 
 
+def conv_wgrad_groups_ok(B, H, W, cin, cout, ksize, stride, grp):
+    """The all-taps weight-gradient kernel takes this shape with passes of `grp` images (conv_wgrad's grp)."""
+    return bool(_abi.lib().sst_conv_wgrad_groups_ok(B, H, W, cin, cout, ksize, stride, int(grp)))
+
+
 CONV_NS = os.environ.get("SST_CONV_NS", "1") != "0"      # the N-split form of the pipelined conv where it applies (0: dev A/B)
 
 

@@ -152,7 +152,7 @@ def test_discriminator_two_passes_as_one_batch(same_kernels, monkeypatch):
             assert disc_graph.groups_supported(D, pd, B, 2, 96, 96)
             pred, sv = disc_graph.forward(D, [a, b], pd, True, True)
             grads, _ = disc_graph.backward(D, pd, sv, dl, True, False)
-            rows = [(r["scale"], r["shift"]) for r in sv["layers"] if r["bi"] is not None]
+            rows = [(r.scale, r.shift) for r in sv.layers if r.bi is not None]
         else:
             pa, sva = disc_graph.forward(D, a, pd, True, True)
             pb, svb = disc_graph.forward(D, b, pd, True, True)
@@ -160,8 +160,8 @@ def test_discriminator_two_passes_as_one_batch(same_kernels, monkeypatch):
             with state(D).accumulating_grads():
                 grads, _ = disc_graph.backward(D, pd, sva, dl[:B].contiguous(), True, False)
                 disc_graph.backward(D, pd, svb, dl[B:].contiguous(), True, False)
-            rows = [(torch.stack([ra["scale"], rb["scale"]]), torch.stack([ra["shift"], rb["shift"]]))
-                    for ra, rb in zip(sva["layers"], svb["layers"]) if ra["bi"] is not None]
+            rows = [(torch.stack([ra.scale, rb.scale]), torch.stack([ra.shift, rb.shift]))
+                    for ra, rb in zip(sva.layers, svb.layers) if ra.bi is not None]
         torch.cuda.synchronize()
         outs[mode] = (pred.clone(), {n: g.clone() for n, g in grads.items()}, {k: v.clone() for k, v in D.state_dict().items()}, rows)
     ps, gs, sds, rs = outs["seq"]
@@ -176,6 +176,54 @@ def test_discriminator_two_passes_as_one_batch(same_kernels, monkeypatch):
     worst = max((rel_err(gb[n], gs[n]), n) for n in gs)
     print("worst gradient difference batched vs sequential:", worst)
     assert worst[0] < (2e-4 if same_kernels else 2e-3), worst
+
+
+def test_arena_record_matches_stand_alone_passes():
+    """Two passes written into a PassArena(2) in the engine's order (slot 1, then slot 0) against stand-alone forwards of the same
+    inputs (train-mode outputs do not depend on the running statistics, so one module serves): the all-slots record holds every
+    pass's tensors bit for bit in its slot, derives each layer's input from the record below, and takes its packs from the pass
+    handed in.  Single-pass kernels only, so the narrow network suffices."""
+    from srganst import disc_graph
+    from srganst.config import Config
+    from srganst.model import Discriminator
+    cfg = Config()
+    cfg.MODEL.D_N_CHANNEL = 8
+    torch.manual_seed(3)
+    D = Discriminator(cfg).cuda().train()
+    _, pd = disc_graph.param_dict(D)
+    B = 2
+    gen = torch.Generator().manual_seed(11)
+    xs = [torch.rand(B, 3, 96, 96, generator=gen).cuda() for _ in range(2)]
+    arena = disc_graph.PassArena(2)
+    out1, sv1 = disc_graph.forward(D, xs[1], pd, True, True, arena=(arena, 1))
+    with pytest.raises(AssertionError):
+        arena.all_slots(sv1)                        # slot 0 has not run
+    out0, sv0 = disc_graph.forward(D, xs[0], pd, True, True, arena=(arena, 0))
+    rec = arena.all_slots(sv0)
+    alone = [disc_graph.forward(D, x, pd, True, True) for x in xs]
+    torch.cuda.synchronize()
+    assert rec.groups == 2 and rec.gB == B
+    assert rec.wd is sv0.wd and rec.ws2 is sv0.ws2 and rec.wd is not None and rec.ws2 is not None
+    assert len(rec.layers) == len(disc_graph.PLAN)
+    for s, (out, (out_a, sv_a)) in enumerate(zip((out0, out1), alone)):
+        sl = slice(s * B, (s + 1) * B)
+        assert torch.equal(out, out_a)
+        assert torch.equal(rec.x3[sl], sv_a.x3) and torch.equal(rec.flat[sl], sv_a.flat) and torch.equal(rec.h1[sl], sv_a.h1)
+        for r, ra, plan in zip(rec.layers, sv_a.layers, disc_graph.PLAN):
+            assert (r.ci, r.bi, r.stride) == (ra.ci, ra.bi, ra.stride) == plan
+            assert torch.equal(r.y[sl], ra.y), r.ci
+            for k in ("mean", "rstd", "scale", "shift"):
+                if r.bi is None:
+                    assert getattr(r, k) is None and getattr(ra, k) is None
+                else:
+                    assert getattr(r, k).shape == (2, ra.y.shape[-1]) and torch.equal(getattr(r, k)[s], getattr(ra, k)), (r.ci, k)
+    x, kw = rec.input_of(0)
+    assert x is rec.x3 and kw["in_scale"] is None and kw["in_shift"] is None and kw["in_act"] == 0
+    for li in range(1, len(rec.layers)):
+        x, kw = rec.input_of(li)
+        below = rec.layers[li - 1]
+        assert x.data_ptr() == below.y.data_ptr() and x.shape == below.y.shape
+        assert kw["in_scale"] is below.scale and kw["in_shift"] is below.shift and kw["in_act"] != 0
 
 
 @pytest.mark.parametrize("reuse", [False, True])

@@ -282,7 +282,7 @@ def test_discriminator_hr192_vs_oracle():
 
 @pytest.mark.parametrize("interval", [1, 2])
 def test_train_engine_pack_reuse_equals_repacking(interval):
-    """The engine lets the discriminator step re-use the weight packs made by the generator step's D(sr) (disc_graph._packs).
+    """The engine lets the discriminator step re-use the weight packs made by the generator step's D(sr) (disc_graph.packs).
     Same run with the re-use switched off (every pass packs, as outside an engine): parameters, BatchNorm buffers and losses
     must be bit-identical, with D updated every step and every second step, under hipGraph replay."""
     from srganst._state import state
