@@ -467,6 +467,16 @@ int sst_flatten_act_grp(const float* y, const float* scale, const float* shift, 
 int sst_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, const float* lr, float* steps,
                   int nsteps, double beta1, double beta2, double eps, double weight_decay, void* stream);
 
+/* sst_adam_flat plus, in the same pass, an exponential moving average of the parameters: with t = steps[0] after the tick,
+ * d = ema_warmup ? min(ema_decay, (1 + t) / (10 + t)) : ema_decay and ema = (float)(d * ema + (1 - d) * p_new), evaluated
+ * in double.  ema: n floats in p's layout.  p / m / v come out bit-identical to sst_adam_flat's. */
+int sst_adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* lr, float* steps,
+                      int nsteps, double beta1, double beta2, double eps, double weight_decay, double ema_decay,
+                      int ema_warmup, void* stream);
+
+/* The average's update alone (no tick, no Adam) with t = steps[0] as it stands: for steps whose Adam update ran elsewhere. */
+int sst_ema_flat(float* ema, const float* p, int64_t n, const float* steps, double ema_decay, int ema_warmup, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

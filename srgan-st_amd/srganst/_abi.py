@@ -36,6 +36,9 @@ SIGNATURES = {
     "sst_debug_big_tile_launches": (ctypes.c_long, []),
     "sst_adam_flat": (c_int, [P, P, P, P, c_int64, P, P, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                             ctypes.c_double, P]),
+    "sst_adam_flat_ema": (c_int, [P, P, P, P, P, c_int64, P, P, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                ctypes.c_double, ctypes.c_double, c_int, P]),
+    "sst_ema_flat": (c_int, [P, P, c_int64, P, ctypes.c_double, c_int, P]),
     "sst_debug_band_launches": (ctypes.c_long, []),
     "sst_debug_wgrad_band_launches": (ctypes.c_long, []),
     "sst_debug_mfma_peak": (c_int, [P, c_int, c_int, P]),

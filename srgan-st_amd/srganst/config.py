@@ -37,6 +37,13 @@ class Config:
         self.EXP.START_EPOCH = 0
         self.EXP.N_EPOCHS = 40
         self.EXP.LABEL_SMOOTHING = 0.1
+        # Resume (checkpoint.py): a path to a training-state file, or "auto" = results/{NAME}/state_last.pth when it exists, else a
+        # fresh start.  The file restores weights, Adam moments and step counters, the LR schedule, the averaged generator, the
+        # best validation values and the RNG streams, and START_EPOCH is taken from it.  "" = off
+        self.EXP.RESUME = ""
+        # the drivers write results/{NAME}/state_last.pth after every epoch (tens of MB for the full model: G, D and their
+        # moments).  False: the files written are exactly g_* / d_* as before
+        self.EXP.SAVE_STATE = True
 
         self.LOG_TRAIN_PERIOD = 100
         self.LOG_VALIDATION_PERIOD = 1
@@ -122,10 +129,18 @@ class Config:
         self.SOLVER.G_BETA2 = 0.999
         self.SOLVER.G_WEIGHT_DECAY = 0
         self.SOLVER.G_EPS = 1e-4
+        # Exponential moving average of the generator's weights, kept by the flat Adam kernel in the same pass (optim.FlatAdam):
+        # 0 = off (the step launches what it launches without the option); 0.999 is the usual value.  WARMUP: the decay at Adam
+        # step t is min(G_EMA_DECAY, (1 + t) / (10 + t)), so a young average is not dominated by the initial weights.  VALIDATE:
+        # the drivers validate, and select "best" on, the averaged generator (engine.g_ema) instead of the last iterate
+        self.SOLVER.G_EMA_DECAY = 0.0
+        self.SOLVER.G_EMA_WARMUP = True
+        self.SOLVER.G_EMA_VALIDATE = True
 
         self.SCHEDULER = dotdict()
         self.SCHEDULER.STEP_SIZE = self.EXP.N_EPOCHS // 2
         self.SCHEDULER.GAMMA = 0.5
+        self.SCHEDULER.MILESTONES = [10]    # reference train.py:80,85 hard-codes MultiStepLR(milestones=[10]) for both optimizers
 
         # --- additions (not in the reference) ---
         self.DIST = dotdict()

@@ -26,11 +26,44 @@ from . import ops as _ops
 from ._state import state
 
 
-def make_adam(module, lr, betas, eps, weight_decay, capturable):
+def make_adam(module, lr, betas, eps, weight_decay, capturable, ema_decay=0.0, ema_warmup=True, ema_buffer=None):
     # torch.optim.Adam semantics and state layout (the reference uses it as-is, train.py:62-75) on flat buffers: one
     # HIP kernel per step, graph-capturable, lr as a device tensor so that LR schedulers keep working under capture.
+    # ema_decay > 0: the same kernel keeps a moving average of the parameters in ema_buffer (optim.FlatAdam).
     from .optim import FlatAdam
-    return FlatAdam(module, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable)
+    return FlatAdam(module, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable,
+                    ema_decay=ema_decay, ema_warmup=ema_warmup, ema_buffer=ema_buffer)
+
+
+def _ema_knobs(config):
+    s = config.SOLVER
+    return float(s.get("G_EMA_DECAY", 0.0)), bool(s.get("G_EMA_WARMUP", True))
+
+
+def make_shadow(config, generator):
+    """The generator the parameter average lives in: a second module of the same class and config in eval mode, its
+    parameters views of ONE flat buffer in the layout of the generator's (ops.flatten_params) - the buffer the flat Adam's
+    kernel writes.  Returns (shadow, flat).  Built without touching the global RNG streams (a run with the average on draws
+    what the same run draws with it off)."""
+    with torch.random.fork_rng(devices=[]):          # the constructor initialises on the host
+        shadow = type(generator)(config)
+    shadow.to(next(generator.parameters()).device)
+    shadow.load_state_dict(generator.state_dict())
+    shadow.eval()
+    for p in shadow.parameters():
+        p.requires_grad_(False)
+    flat, _, _ = _ops.flatten_params(shadow)
+    return shadow, flat
+
+
+def sync_shadow_buffers(generator, shadow):
+    """BatchNorm running statistics and batch counters are running averages already: copied, not averaged again."""
+    if shadow is None:
+        return
+    src = dict(generator.named_buffers())
+    with torch.no_grad():
+        for name, buf in shadow.named_buffers():
+            buf.copy_(src[name])
 
 
 _ONES = {}
@@ -186,9 +219,13 @@ class WarmupEngine:
         self.pg = process_group
         self.world = sdist.world_size(process_group)
         use_graph = config.KERNEL.USE_GRAPH if use_graph is None else use_graph
+        # SOLVER.G_EMA_DECAY > 0: g_ema is the averaged generator (eval mode), its weights written by the optimizer's kernel
+        ema_decay, ema_warmup = _ema_knobs(config)
+        self.g_ema, ema_buf = make_shadow(config, self.G) if ema_decay > 0 else (None, None)
         self.opt = make_adam(self.G, config.SOLVER.G_BASE_LR, (config.SOLVER.G_BETA1, config.SOLVER.G_BETA2),
                              config.SOLVER.G_EPS, config.SOLVER.G_WEIGHT_DECAY,
-                             capturable=use_graph if adam_capturable is None else adam_capturable)
+                             capturable=use_graph if adam_capturable is None else adam_capturable,
+                             ema_decay=ema_decay, ema_warmup=ema_warmup, ema_buffer=ema_buf)
         self.gt = self.lr = None
         self.loss_values = OrderedDict()
         self.sr = None
@@ -205,6 +242,10 @@ class WarmupEngine:
         else:
             self._fb = _GraphedStep(self._full_step, enabled=use_graph, on_fail=self._drop_graphs)
             self._op = None
+
+    def sync_ema_buffers(self):
+        """Copy G's BatchNorm buffers into g_ema; call before the shadow is validated or saved."""
+        sync_shadow_buffers(self.G, self.g_ema)
 
     def _steps(self):
         return [s for s in (self._fb, self._op) if s is not None]
@@ -251,6 +292,7 @@ class WarmupEngine:
         device objects are released right here and not by a later cyclic collection)."""
         self._fb = self._op = None
         self.gt = self.lr = self.sr = None
+        self.g_ema = None
 
     def step(self, gt, lr):
         """One optimisation step on the batch (gt [B,3,H,W], lr [B,3,H/4,W/4], device tensors)."""
@@ -275,7 +317,12 @@ class TrainEngine:
         use_graph = config.KERNEL.USE_GRAPH if use_graph is None else use_graph
         s = config.SOLVER
         cap = use_graph if adam_capturable is None else adam_capturable
-        self.g_opt = make_adam(self.G, s.G_BASE_LR, (s.G_BETA1, s.G_BETA2), s.G_EPS, s.G_WEIGHT_DECAY, cap)
+        # SOLVER.G_EMA_DECAY > 0: g_ema is the averaged generator (eval mode); its weights are written by G's Adam kernel, so the
+        # update rides in whichever graph holds g_opt.step.  D has no average.
+        ema_decay, ema_warmup = _ema_knobs(config)
+        self.g_ema, ema_buf = make_shadow(config, self.G) if ema_decay > 0 else (None, None)
+        self.g_opt = make_adam(self.G, s.G_BASE_LR, (s.G_BETA1, s.G_BETA2), s.G_EPS, s.G_WEIGHT_DECAY, cap,
+                               ema_decay=ema_decay, ema_warmup=ema_warmup, ema_buffer=ema_buf)
         self.d_opt = make_adam(self.D, s.D_BASE_LR, (s.D_BETA1, s.D_BETA2), s.D_EPS, s.D_WEIGHT_DECAY, cap)
         self.adv = BCEWithLogitsLoss()                      # train.py:59
         self.real = 1.0 - config.EXP.LABEL_SMOOTHING        # train.py:113
@@ -327,6 +374,10 @@ class TrainEngine:
             # whole iteration as ONE graph: the discriminator step runs beside the generator's backward (see _iter_gd)
             if bool(getattr(config.KERNEL, "OVERLAP_GD", False)):
                 self._it = _GraphedStep(self._iter_gd, enabled=g, on_fail=f)
+
+    def sync_ema_buffers(self):
+        """Copy G's BatchNorm buffers into g_ema; call before the shadow is validated or saved."""
+        sync_shadow_buffers(self.G, self.g_ema)
 
     def _steps(self):
         if self._it is not None:               # merged iterations; generator-only graph between them when D is updated every n-th step
@@ -616,6 +667,7 @@ class TrainEngine:
         # D is handed back: no owner, so it packs on every call again (a later optimizer step on it would not clear packs_fresh)
         self._ds.owner, self._ds.packs_fresh, self._ds.last_pass = None, False, None
         self.gt = self.lr = self.sr = None
+        self.g_ema = None
 
     def _step_overlapped(self):
         """Data-parallel iteration: collectives hidden behind compute AND the discriminator half beside the generator's backward

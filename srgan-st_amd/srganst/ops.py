@@ -1006,6 +1006,23 @@ def adam_flat(p, g, m, v, lr_dev, steps, beta1, beta2, eps, weight_decay):
     _trace_hbm("adam_flat_kernel", 28.0 * p.numel(), lambda: _abi.lib().sst_adam_flat(*args, stream_ptr()), p, g, m, v, lr_dev, steps)
 
 
+def adam_flat_ema(p, g, m, v, ema, lr_dev, steps, beta1, beta2, eps, weight_decay, ema_decay, ema_warmup):
+    """adam_flat plus, in the same pass, ema <- d * ema + (1 - d) * p_new (csrc/optim.hip): 5 reads + 4 writes per element."""
+    assert p.numel() == g.numel() == m.numel() == v.numel() == ema.numel() and p.numel() % 4 == 0
+    args = (ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), ptr(lr_dev), ptr(steps), steps.numel(), float(beta1), float(beta2),
+            float(eps), float(weight_decay), float(ema_decay), int(bool(ema_warmup)))
+    check(_abi.lib().sst_adam_flat_ema(*args, stream_ptr()), "sst_adam_flat_ema")
+    _trace_hbm("adam_flat_ema_kernel", 36.0 * p.numel(), lambda: _abi.lib().sst_adam_flat_ema(*args, stream_ptr()),
+               p, g, m, v, ema, lr_dev, steps)
+
+
+def ema_flat(ema, p, steps, ema_decay, ema_warmup):
+    """The average's update alone, t = steps[0] as it stands (after an Adam update that did not go through adam_flat_ema)."""
+    assert ema.numel() == p.numel() and p.numel() % 4 == 0 and steps.numel() > 0
+    check(_abi.lib().sst_ema_flat(ptr(ema), ptr(p), p.numel(), ptr(steps), float(ema_decay), int(bool(ema_warmup)), stream_ptr()),
+          "sst_ema_flat")
+
+
 class WgradGroup:
     """Collects weight-gradient jobs of identical shape and issues them as ONE launch (+ one grouped slab reduce).
     The slab is cached per (shape, count); the job table (device pointers of every layer) is a kernel argument."""

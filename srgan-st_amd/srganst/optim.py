@@ -4,7 +4,12 @@ The reference builds ``optim.Adam(params, lr, betas, eps, weight_decay)`` (train
 schedulers on it.  FlatAdam IS a torch.optim.Adam (schedulers, ``param_groups``, ``state_dict()`` / ``load_state_dict()``
 keep working and checkpoints stay interchangeable); what changes is where the numbers live: parameters, gradients and
 both moments are flat fp32 buffers of one layout, so ``step()`` is a single streaming pass (csrc/optim.hip) instead of
-torch's multi-tensor launches (measured 130 us -> ~12 us per generator step on MI355X)."""
+torch's multi-tensor launches (measured 130 us -> ~12 us per generator step on MI355X).
+
+With ``ema_decay > 0`` the same pass also keeps an exponential moving average of the parameters in a flat buffer of the
+parameters' layout (``ema``): ema <- d * ema + (1 - d) * p_new, d = ema_decay or, with ``ema_warmup``,
+min(ema_decay, (1 + t) / (10 + t)) at Adam step t.  The average is NOT part of ``state_dict()`` (that stays torch's
+layout); it travels as the state dict of a module whose parameters are views of the buffer (engine: ``g_ema``)."""
 from __future__ import annotations
 
 import torch
@@ -14,7 +19,10 @@ from ._state import state
 
 
 class FlatAdam(torch.optim.Adam):
-    def __init__(self, module, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
+    def __init__(self, module, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False, ema_decay=0.0,
+                 ema_warmup=True, ema_buffer=None):
+        if not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay}")
         flat, offs, params = ops.flatten_params(module)
         dev = flat.device
         self._lr_dev = torch.tensor(float(lr), device=dev, dtype=torch.float32)
@@ -27,6 +35,22 @@ class FlatAdam(torch.optim.Adam):
         self._v = torch.zeros_like(flat)
         self._steps = torch.zeros(len(params), device=dev, dtype=torch.float32)
         self._adopt_state()
+        # the average: allocated and filled here, so it exists before any graph capture.  ema_buffer: a flat buffer of the same
+        # layout that the caller owns (the flattened parameters of a shadow module) - the ONE buffer the kernel writes
+        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
+        self.ema = None
+        if self.ema_decay > 0.0:
+            if ema_buffer is not None and (ema_buffer.shape != flat.shape or ema_buffer.device != dev or ema_buffer.dtype != flat.dtype
+                                           or not ema_buffer.is_contiguous()):
+                raise ValueError("ema_buffer must be a contiguous fp32 buffer of the flat parameters' size on their device")
+            self.ema = ema_buffer if ema_buffer is not None else torch.empty_like(flat)
+            self.reset_ema()
+
+    @torch.no_grad()
+    def reset_ema(self):
+        """The average starts over from the parameters as they are now (for callers that load weights after construction)."""
+        if self.ema is not None:
+            self.ema.copy_(self._flat_p)
 
     def _adopt_state(self):
         """(Re)build the per-parameter state entries torch's Adam expects, as views of the flat buffers."""
@@ -73,11 +97,18 @@ class FlatAdam(torch.optim.Adam):
         g = self._flat_grad()
         grp = self.param_groups[0]
         if g is None or len(self.param_groups) != 1 or grp.get("amsgrad") or grp.get("maximize"):
-            return super().step(closure)             # not our layout: torch's own update on the same state tensors
+            out = super().step(closure)              # not our layout: torch's own update on the same state tensors
+            if self.ema is not None:                 # ... which has moved the step counters: t = steps[0] as it stands now
+                ops.ema_flat(self.ema, self._flat_p, self._steps, self.ema_decay, self.ema_warmup)
+            return out
         lr = grp["lr"]
         if not isinstance(lr, torch.Tensor):
             self._lr_dev.fill_(float(lr))
             lr = self._lr_dev
         b1, b2 = grp["betas"]
-        ops.adam_flat(self._flat_p, g, self._m, self._v, lr, self._steps, b1, b2, grp["eps"], grp["weight_decay"])
+        if self.ema is not None:
+            ops.adam_flat_ema(self._flat_p, g, self._m, self._v, self.ema, lr, self._steps, b1, b2, grp["eps"], grp["weight_decay"],
+                              self.ema_decay, self.ema_warmup)
+        else:
+            ops.adam_flat(self._flat_p, g, self._m, self._v, lr, self._steps, b1, b2, grp["eps"], grp["weight_decay"])
         return None

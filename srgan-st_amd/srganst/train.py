@@ -1,6 +1,10 @@
 """SRGAN training driver.  Mirrors reference train.py:16-226: seeds, D then G construction, two Adams
 (eps 1e-4), MultiStepLR(milestones=[10], gamma), optional warm weights, the G-then-D iteration
-(engine.TrainEngine = train.py:116-164), per-epoch validation and checkpoints with reference key names."""
+(engine.TrainEngine = train.py:116-164), per-epoch validation and checkpoints with reference key names.
+
+Not in the reference: EXP.RESUME continues a run from its training state (checkpoint.py: weights, Adam state, LR schedule, averaged
+generator, best values, RNG streams), and with SOLVER.G_EMA_DECAY > 0 the averaged generator (engine.g_ema) is validated and
+saved beside the last iterate (g_ema_last / g_ema_best / g_ema_epochN, plain generator state dicts)."""
 from __future__ import annotations
 
 import os
@@ -9,6 +13,7 @@ import torch
 from torch.optim import lr_scheduler
 from torch.utils.data import DataLoader
 
+from . import checkpoint
 from . import device_data
 from . import dist as sdist
 from .bicubic import Bicubic
@@ -25,6 +30,13 @@ def train(config: Config, train_dataset=None, test_dataset=None, max_steps_per_e
     rank, local, world = sdist.init_from_env(config.DIST.BACKEND)
     init_random_seed(config.DATA.SEED)
     best_psnr = best_ssim = 0.0
+    # EXP.RESUME: START_EPOCH comes from the file BEFORE the loaders are built (the on-device loaders key their draws on it)
+    resume = checkpoint.load_resume(config, world)
+    if resume is not None:
+        if resume["discriminator"] is None or resume["d_opt"] is None:
+            raise ValueError("EXP.RESUME: the training state holds no discriminator (a warmup() state?); "
+                             "continue from warm-up weights with MODEL.G_CONTINUE_FROM_WARMUP instead")
+        best_psnr, best_ssim = resume["best_psnr"], resume["best_ssim"]
     train_ds = train_dataset or TrainImageDataset(config.DATA.TRAIN_GT_IMAGES_DIR, config.DATA.UPSCALE_FACTOR)
     test_ds = test_dataset or TestImageDataset(config.DATA.TEST_GT_IMAGES_DIR, config.DATA.TEST_LR_IMAGES_DIR)
     on_device = device_data.on_device(config)    # DATA.ON_DEVICE or DATA.ON_DEVICE_WHOLE_IMAGES
@@ -41,17 +53,33 @@ def train(config: Config, train_dataset=None, test_dataset=None, max_steps_per_e
     start_workers(train_loader)                  # fork the loader workers with the collector frozen (see utils.start_workers)
     discriminator = Discriminator(config).to(config.DEVICE)     # train.py:52-53: D is constructed before G
     generator = Generator(config).to(config.DEVICE)
-    if config.MODEL.G_CONTINUE_FROM_WARMUP:
+    # weights go in before the engine is built (D's packs and G's flat buffer see them); a resumed state wins over warm-up weights
+    if resume is not None:
+        generator.load_state_dict(resume["generator"])
+        discriminator.load_state_dict(resume["discriminator"])
+    if config.MODEL.G_CONTINUE_FROM_WARMUP and resume is None:
         generator = load_state_dict(generator, torch.load(config.MODEL.G_WARMUP_WEIGHTS, map_location=config.DEVICE, weights_only=True))
-    if config.MODEL.D_CONTINUE_FROM_WARMUP:
+    if config.MODEL.D_CONTINUE_FROM_WARMUP and resume is None:
         discriminator = load_state_dict(discriminator, torch.load(config.MODEL.D_WARMUP_WEIGHTS, map_location=config.DEVICE, weights_only=True))
     sdist.broadcast_module(generator)
     sdist.broadcast_module(discriminator)
     engine = TrainEngine(config, generator, discriminator)
-    d_scheduler = lr_scheduler.MultiStepLR(engine.d_opt, milestones=[10], gamma=config.SCHEDULER.GAMMA)
-    g_scheduler = lr_scheduler.MultiStepLR(engine.g_opt, milestones=[10], gamma=config.SCHEDULER.GAMMA)
+    milestones = list(config.SCHEDULER.get("MILESTONES", [10]))
+    d_scheduler = lr_scheduler.MultiStepLR(engine.d_opt, milestones=milestones, gamma=config.SCHEDULER.GAMMA)
+    g_scheduler = lr_scheduler.MultiStepLR(engine.g_opt, milestones=milestones, gamma=config.SCHEDULER.GAMMA)
+    if resume is not None:
+        engine.g_opt.load_state_dict(resume["g_opt"])
+        engine.d_opt.load_state_dict(resume["d_opt"])
+        checkpoint.load_scheduler_state(g_scheduler, resume["g_sched"])
+        checkpoint.load_scheduler_state(d_scheduler, resume["d_sched"])
+        if engine.g_ema is not None:
+            engine.g_ema.load_state_dict(resume["g_ema"])
+    ema_validate = engine.g_ema is not None and bool(config.SOLVER.get("G_EMA_VALIDATE", True))
     writer = _writer(config.EXP.NAME) if rank == 0 else _NullWriter()
     writer.add_text("Config/Params", config.get_all_params())
+    if resume is not None:      # last: model construction and start_workers have drawn from the streams by now
+        checkpoint.restore_rng(resume["rng"], config.DEVICE)
+    resume = None
     for epoch in range(config.EXP.START_EPOCH, config.EXP.N_EPOCHS):
         if rank == 0:
             print(f"Beginning train epoch: {epoch+1}")
@@ -94,7 +122,9 @@ def train(config: Config, train_dataset=None, test_dataset=None, max_steps_per_e
         d_scheduler.step()
         generator.eval()
         if rank == 0:
-            psnr, ssim, *st = _validate(generator, test_loader, config)      # (psnr, ssim, st) with DATA.VALIDATE_ST
+            engine.sync_ema_buffers()             # the averaged generator takes G's BatchNorm buffers before it is run or saved
+            # (psnr, ssim, st) with DATA.VALIDATE_ST; with the average on (and G_EMA_VALIDATE) it is the averaged generator's
+            psnr, ssim, *st = _validate(engine.g_ema if ema_validate else generator, test_loader, config)
             if epoch % config.LOG_VALIDATION_PERIOD == 0:
                 print(f"[Test: {epoch+1}/{config.EXP.N_EPOCHS}] [PSNR: {psnr}] [SSIM: {ssim}]")
             writer.add_scalar("Test/PSNR", psnr, epoch + 1)
@@ -105,14 +135,25 @@ def train(config: Config, train_dataset=None, test_dataset=None, max_steps_per_e
             os.makedirs(results_dir, exist_ok=True)
             torch.save(generator.state_dict(), results_dir + "/g_last.pth")
             torch.save(discriminator.state_dict(), results_dir + "/d_last.pth")
+            if engine.g_ema is not None:
+                torch.save(engine.g_ema.state_dict(), results_dir + "/g_ema_last.pth")
             if best_psnr < psnr and best_ssim < ssim:
                 torch.save(generator.state_dict(), results_dir + "/g_best.pth")
                 torch.save(discriminator.state_dict(), results_dir + "/d_best.pth")
+                if engine.g_ema is not None:
+                    torch.save(engine.g_ema.state_dict(), results_dir + "/g_ema_best.pth")
                 best_psnr, best_ssim = psnr, ssim
             if 0 < epoch and epoch % config.G_CHECKPOINT_INTERVAL == 0:
                 torch.save(generator.state_dict(), results_dir + f"/g_epoch{epoch}.pth")
+                if engine.g_ema is not None:
+                    torch.save(engine.g_ema.state_dict(), results_dir + f"/g_ema_epoch{epoch}.pth")
             if 0 < epoch and epoch % config.D_CHECKPOINT_INTERVAL == 0:
                 torch.save(discriminator.state_dict(), results_dir + f"/d_epoch{epoch}.pth")
+            if config.EXP.get("SAVE_STATE", True):       # last in the epoch: the RNG streams go in as the next epoch will find them
+                checkpoint.save_training_state(results_dir + "/" + checkpoint.STATE_FILE, epoch=epoch + 1, generator=generator,
+                                               g_opt=engine.g_opt, g_sched=g_scheduler, discriminator=discriminator,
+                                               d_opt=engine.d_opt, d_sched=d_scheduler, g_ema=engine.g_ema,
+                                               best=(best_psnr, best_ssim), config=config, world_size=world)
     engine.close()
     return generator, discriminator
 

@@ -150,8 +150,10 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
 
 def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_gt: bool = False, dataset=None, on_device=None,
          with_st=None, tile=None):
-    if not g_path:
-        g_path = f"results/{config.EXP.NAME}/g_best.pth"
+    if not g_path:                # the averaged generator's best when the run kept one (SOLVER.G_EMA_DECAY), else the last iterate's
+        g_path = f"results/{config.EXP.NAME}/g_ema_best.pth"
+        if not os.path.exists(g_path):
+            g_path = f"results/{config.EXP.NAME}/g_best.pth"
     ds = dataset if dataset is not None else TestImageDataset(config.DATA.TEST_GT_IMAGES_DIR, config.DATA.TEST_LR_IMAGES_DIR)
     loader = DataLoader(ds, batch_size=1, shuffle=False, num_workers=0, drop_last=False)
     if config.EXP.NAME == "bicubic":

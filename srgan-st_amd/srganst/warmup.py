@@ -1,6 +1,7 @@
 """SRResNet pre-training driver.  Mirrors reference warmup.py:14-147: seed, Generator, Adam(eps 1e-4),
 loaders, per-epoch step loop, validation, checkpoints (g_last / g_best / g_epochN with the reference's
-state-dict keys).  The step itself is srganst.engine.WarmupEngine (HIP kernels, hipGraph, RCCL)."""
+state-dict keys).  The step itself is srganst.engine.WarmupEngine (HIP kernels, hipGraph, RCCL).
+EXP.RESUME / SOLVER.G_EMA_DECAY: as in train.py (training state and averaged generator, checkpoint.py)."""
 from __future__ import annotations
 
 import os
@@ -8,6 +9,7 @@ import os
 import torch
 from torch.utils.data import DataLoader
 
+from . import checkpoint
 from . import device_data
 from . import dist as sdist
 from .bicubic import Bicubic
@@ -36,9 +38,21 @@ def warmup(config: Config, train_dataset=None, test_dataset=None, max_steps_per_
     rank, local, world = sdist.init_from_env(config.DIST.BACKEND)
     init_random_seed(config.DATA.SEED)
     best_psnr = best_ssim = 0.0
+    batches_done = 0
+    # EXP.RESUME: START_EPOCH comes from the file BEFORE the loaders are built (the on-device loaders key their draws on it)
+    resume = checkpoint.load_resume(config, world)
+    if resume is not None:
+        best_psnr, best_ssim, batches_done = resume["best_psnr"], resume["best_ssim"], resume["batches_done"]
     generator = Generator(config).to(config.DEVICE)
+    if resume is not None:                       # before the engine is built: its flat parameter buffer sees the weights
+        generator.load_state_dict(resume["generator"])
     sdist.broadcast_module(generator)
     engine = WarmupEngine(config, generator)
+    if resume is not None:
+        engine.opt.load_state_dict(resume["g_opt"])
+        if engine.g_ema is not None:
+            engine.g_ema.load_state_dict(resume["g_ema"])
+    ema_validate = engine.g_ema is not None and bool(config.SOLVER.get("G_EMA_VALIDATE", True))
     train_ds = train_dataset or TrainImageDataset(config.DATA.TRAIN_GT_IMAGES_DIR, config.DATA.UPSCALE_FACTOR)
     test_ds = test_dataset or TestImageDataset(config.DATA.TEST_GT_IMAGES_DIR, config.DATA.TEST_LR_IMAGES_DIR)
     on_device = device_data.on_device(config)    # DATA.ON_DEVICE or DATA.ON_DEVICE_WHOLE_IMAGES
@@ -55,7 +69,9 @@ def warmup(config: Config, train_dataset=None, test_dataset=None, max_steps_per_
     start_workers(train_loader)                  # fork the loader workers with the collector frozen (see utils.start_workers)
     writer = _writer(config.EXP.NAME) if rank == 0 else _NullWriter()
     writer.add_text("Config/Params", config.get_all_params())
-    batches_done = 0
+    if resume is not None:      # last: model construction and start_workers have drawn from the streams by now
+        checkpoint.restore_rng(resume["rng"], config.DEVICE)
+    resume = None
     for epoch in range(config.EXP.START_EPOCH, config.EXP.N_EPOCHS):
         if rank == 0:
             print(f"Beginning warmup epoch: {epoch+1}")
@@ -88,7 +104,9 @@ def warmup(config: Config, train_dataset=None, test_dataset=None, max_steps_per_
             print(f"[Epoch {epoch+1}/{config.EXP.N_EPOCHS}] [Batch {batch_num}/{len(train_loader)}] [G losses: {vals}]")
         generator.eval()
         if rank == 0:
-            psnr, ssim, *st = _validate(generator, test_loader, config)      # (psnr, ssim, st) with DATA.VALIDATE_ST
+            engine.sync_ema_buffers()             # the averaged generator takes G's BatchNorm buffers before it is run or saved
+            # (psnr, ssim, st) with DATA.VALIDATE_ST; with the average on (and G_EMA_VALIDATE) it is the averaged generator's
+            psnr, ssim, *st = _validate(engine.g_ema if ema_validate else generator, test_loader, config)
             if epoch % config.LOG_VALIDATION_PERIOD == 0:
                 print(f"[Test: {epoch+1}/{config.EXP.N_EPOCHS}] [PSNR: {psnr}] [SSIM: {ssim}]")
             writer.add_scalar("Test/PSNR", psnr, epoch + 1)
@@ -98,11 +116,21 @@ def warmup(config: Config, train_dataset=None, test_dataset=None, max_steps_per_
             results_dir = f"results/{config.EXP.NAME}"
             os.makedirs(results_dir, exist_ok=True)
             torch.save(generator.state_dict(), results_dir + "/g_last.pth")
+            if engine.g_ema is not None:
+                torch.save(engine.g_ema.state_dict(), results_dir + "/g_ema_last.pth")
             if best_psnr < psnr and best_ssim < ssim:
                 torch.save(generator.state_dict(), results_dir + "/g_best.pth")
+                if engine.g_ema is not None:
+                    torch.save(engine.g_ema.state_dict(), results_dir + "/g_ema_best.pth")
                 best_psnr, best_ssim = psnr, ssim
             if 0 < epoch and epoch % config.G_CHECKPOINT_INTERVAL == 0:
                 torch.save(generator.state_dict(), results_dir + f"/g_epoch{epoch}.pth")
+                if engine.g_ema is not None:
+                    torch.save(engine.g_ema.state_dict(), results_dir + f"/g_ema_epoch{epoch}.pth")
+            if config.EXP.get("SAVE_STATE", True):       # last in the epoch: the RNG streams go in as the next epoch will find them
+                checkpoint.save_training_state(results_dir + "/" + checkpoint.STATE_FILE, epoch=epoch + 1, generator=generator,
+                                               g_opt=engine.opt, g_sched=None, g_ema=engine.g_ema, best=(best_psnr, best_ssim),
+                                               batches_done=batches_done, config=config, world_size=world)
     engine.close()
     return generator
 
