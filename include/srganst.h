@@ -114,17 +114,12 @@ int sst_conv_fwd(const float* x, const float* wp, float* y, float* y_pre, const 
 int sst_conv_pipe_supported(int B, int H, int W, int Cin, int Cout, int ksize, int stride);
 int sst_conv_pipe_stat_tiles(int B, int H, int W, int Cin, int Cout, int ksize, int stride);
 int64_t sst_conv_pipe_ws_floats(int B, int H, int W, int Cin, int Cout, int ksize, int stride);
-int sst_conv_pipe_fwd(const float* x, const float* wp, float* y, const float* bias, const float* in_scale,
-                      const float* in_shift, const float* in_slope, float in_slope_const, int in_act, float* stats,
-                      float* stats_cnt, const float* epi_y, const float* epi_scale, const float* epi_shift,
-                      const float* epi_slope, float epi_slope_const, int epi_act, float* epi_partial, float* ws, int B,
-                      int H, int W, int Cin, int Cout, int ksize, int stride, void* stream);
-/* ... with COEFFICIENT GROUPS: several passes of the network over different inputs with the same weights - the discriminator step's
+/* COEFFICIENT GROUPS: several passes of the network over different inputs with the same weights - the discriminator step's
  * D(gt) and D(sr.detach()), train.py:155-158 - run as ONE batch of B images in which every grp_images consecutive images form a
  * pass with its own train-mode BatchNorm statistics.  The per-channel arrays in_scale / in_shift / epi_scale / epi_shift are then
  * [B / grp_images][channels] (row = pass); stats / epi_partial tiles never straddle a pass (sst_conv_pipe_groups_ok: the pass
  * boundary falls on a tile boundary of the tall image), so the tile rows of pass p are the p-th of B / grp_images equal consecutive
- * ranges.  grp_images = 0 (or B): one row, the call above. */
+ * ranges.  grp_images = 0 (or B): one row for the whole batch. */
 int sst_conv_pipe_groups_ok(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int grp_images);
 int sst_conv_pipe_fwd_grp(const float* x, const float* wp, float* y, const float* bias, const float* in_scale,
                           const float* in_shift, const float* in_slope, float in_slope_const, int in_act, float* stats,
@@ -149,16 +144,10 @@ int sst_conv_ns_fwd(const float* x, const float* wp, float* y, const float* bias
  * sst_conv_s2_dgrad_pipe_supported: tile width when the shape is taken, else 0. */
 int sst_conv_s2_dgrad_pipe_supported(int B, int H, int W, int Cin, int Cout);
 int64_t sst_conv_s2_dgrad_pipe_ws_floats(int B, int H, int W, int Cin, int Cout);
-int sst_conv_s2_dgrad_pipe(const float* dy, const float* wp, float* dx, float* ws, int B, int H, int W, int Cin, int Cout,
-                           void* stream);
-/* ... with the BatchNorm / activation backward partials of dx against epi_y (the saved output of the layer below, [B,H,W,Cin]) written by
- * the epilogue: epi_partial [sst_conv_s2_dgrad_pipe_stat_tiles()][3][Cin], the layout sst_bwd_finalize consumes (null: none). */
+/* The epilogue can write the BatchNorm / activation backward partials of dx against epi_y (the saved output of the layer below,
+ * [B,H,W,Cin]): epi_partial [sst_conv_s2_dgrad_pipe_stat_tiles()][3][Cin], the layout sst_bwd_finalize consumes (null: none; the
+ * epi_* arguments are then unused).  Coefficient groups (sst_conv_pipe_fwd_grp): epi_scale / epi_shift [B / grp_images][Cin]. */
 int sst_conv_s2_dgrad_pipe_stat_tiles(int B, int H, int W, int Cin, int Cout);
-int sst_conv_s2_dgrad_pipe_bwdstats(const float* dy, const float* wp, float* dx, float* ws, const float* epi_y,
-                                    const float* epi_scale, const float* epi_shift, const float* epi_slope,
-                                    float epi_slope_const, int epi_act, float* epi_partial, int B, int H, int W, int Cin,
-                                    int Cout, void* stream);
-/* ... with coefficient groups (sst_conv_pipe_fwd_grp): epi_scale / epi_shift [B / grp_images][Cin] */
 int sst_conv_s2_dgrad_pipe_groups_ok(int B, int H, int W, int Cin, int Cout, int grp_images);
 int sst_conv_s2_dgrad_pipe_bwdstats_grp(const float* dy, const float* wp, float* dx, float* ws, const float* epi_y,
                                     const float* epi_scale, const float* epi_shift, const float* epi_slope,
@@ -166,7 +155,7 @@ int sst_conv_s2_dgrad_pipe_bwdstats_grp(const float* dy, const float* wp, float*
                                     int Cout, int grp_images, void* stream);
 /* stride-1 data-gradient (mode 1 weights) whose epilogue also emits the BatchNorm/activation BACKWARD partial sums of
  * its result g against the saved conv output epi_y: epi_partial [sst_conv_stat_tiles][3][Cout] = per-tile sums of
- * (gz, gz*epi_y, g*min(z,0)) - the layout sst_bwd_finalize consumes (replaces a separate sst_bwd_reduce pass). */
+ * (gz, gz*epi_y, g*min(z,0)) - the layout sst_bwd_finalize consumes (replaces a separate sst_bwd_reduce_grp pass). */
 int sst_conv_dgrad_bwdstats(const float* x, const float* wp, float* y, const float* residual, const float* epi_y,
                             const float* epi_scale, const float* epi_shift, const float* epi_slope,
                             float epi_slope_const, int epi_act, float* epi_partial, int B, int H, int W, int Cin,
@@ -174,7 +163,7 @@ int sst_conv_dgrad_bwdstats(const float* x, const float* wp, float* y, const flo
 /* ---- accumulator mode of the BatchNorm statistics (trunk shape only: sst_conv_acc_supported): the producer conv adds its
  * per-band (sum, Chan-form sum of squares) into fp64 accumulators acc[nrep][C][2] (zero before the launch) with hardware
  * atomics; the consumer conv derives batch statistics + affine of its input from them in its prologue and publishes
- * mean / rstd / scale / shift (+ running statistics) once.  Replaces sst_bn_finalize launches of model.py:174-177's BatchNorms.
+ * mean / rstd / scale / shift (+ running statistics) once.  Replaces sst_bn_finalize_grp launches of model.py:174-177's BatchNorms.
  * in2 == null: staged = act(x*scale+shift); in2 != null: staged = x + in2*scale + shift, also written to side_out. */
 int sst_conv_acc_supported(int B, int H, int W, int Cin, int Cout, int ksize, int stride);
 int sst_conv_fwd_acc(const float* x, const float* in2, float* side_out, const float* ones, const float* wp, float* y,
@@ -208,16 +197,12 @@ int sst_conv_dgrad_fused(const float* g, const float* y2, const float* cA, const
                          const float* epi_y, const float* epi_scale, const float* epi_shift, const float* epi_slope,
                          float epi_slope_const, int epi_act, float* epi_partial, int B, int H, int W, int Cin, int Cout,
                          int ksize, void* stream);
-/* dW[Cout][Cin][k][k] (+)= sum_pixels X'(shifted) * dY ; slab = sst_conv_wgrad_chunks*k*k*Cout*Cin floats */
-int sst_conv_wgrad_chunks(int B, int Ho, int Wo, int Cin, int Cout, int ksize);   /* general (per-tap) kernel only */
-/* chunk count to size the slab of sst_conv_wgrad (njobs = 1) / sst_conv_wgrad_grouped (njobs layers) with; H, W = input size.
+/* dW[Cout][Cin][k][k] (+)= sum_pixels X'(shifted) * dY ; slab = sst_conv_wgrad_chunks2*k*k*Cout*Cin floats.
+ * sst_conv_wgrad_chunks2: chunk count to size the slab of sst_conv_wgrad_grp (njobs = 1) / sst_conv_wgrad_grouped (njobs layers)
+ * with; H, W = input size.
  * It is the launcher's own plan (wgrad_plan, csrc/conv_wgrad.hip): the chunks its kernel writes, or - where input affine, activation
  * or a dev switch decide between kernels of different chunk counts - the largest of them. */
 int sst_conv_wgrad_chunks2(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int njobs);
-int sst_conv_wgrad(const float* x, const float* dy, float* slab, float* dw, const float* in_scale,
-                   const float* in_shift, const float* in_slope, float in_slope_const, int in_act,
-                   int B, int H, int W, int Cin, int Cout, int stride, int ksize, int accumulate,
-                   void* stream);
 /* in_scale / in_shift [B / grp_images][Cin]: the images are grp_images-sized passes with their own BatchNorm coefficients (see
  * sst_conv_pipe_fwd_grp), dW sums over all of them.  Taken by the all-taps tile kernel only (sst_conv_wgrad_groups_ok). */
 int sst_conv_wgrad_groups_ok(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int grp_images);
@@ -279,9 +264,6 @@ int sst_conv_wgrad_grouped(const void* jobs, int njobs, int B, int H, int W, int
 /* ---- BatchNorm (train mode) + elementwise glue, tensors viewed as [R rows, C channels] -----------
  * nn.BatchNorm2d model.py:36-57,114,174,177 (eps 1e-5, momentum .1); PReLU/LeakyReLU backward;
  * residual adds model.py:146,183. */
-int sst_bn_finalize(const float* stats, const float* cnt, int ntiles, int C, const float* gamma,
-                    const float* beta, float* run_mean, float* run_var, float* mean, float* rstd,
-                    float* scale, float* shift, float eps, float momentum, void* stream);
 /* `groups` passes batched as one tall image (see sst_conv_pipe_fwd_grp): stats / cnt hold ntiles tiles = groups equal consecutive
  * ranges; mean / rstd / scale / shift are [groups][C]; the running statistics take one momentum step per group, in group order. */
 int sst_bn_finalize_grp(const float* stats, const float* cnt, int ntiles, int C, int groups, const float* gamma,
@@ -292,9 +274,6 @@ int sst_bn_eval_affine(const float* gamma, const float* beta, const float* run_m
 int sst_bn_residual(const float* y, const float* scale, const float* shift, const float* res,
                     const float* res_slope, float* out, int64_t R, int C, void* stream);
 int sst_bwd_reduce_blocks(int64_t R, int C);
-int sst_bwd_reduce(const float* g, const float* g2, const float* y, const float* scale,
-                   const float* shift, const float* slope, float slope_const, int act, float* partial,
-                   int64_t R, int C, void* stream);
 int sst_bwd_finalize(const float* partial, int nblk, int C, float n, const float* mean,
                      const float* rstd, const float* gamma, float* dgamma, float* dbeta, float* cA,
                      float* cB, float* cC, float* dslope, int accumulate, void* stream);
@@ -408,7 +387,7 @@ int sst_canvas_to_u8(const float* canvas, int H, int W, float scale, uint8_t* ou
 /* ---- best-buddy losses (loss.py:78-142 BestBuddyLoss, loss.py:145-228 GramLoss, loss.py:292-375
  * PatchwiseStructureTensorLoss; ksize 3, stride 3, pad 0, squared-L2 matching):
  * sst_bb_patches cuts an image [B,3,H,W] into 27-vectors (unfold order) + squared norms inside the candidate table
- * cand [B,ncand,27] / cnrm [B,ncand]; sst_bb_match pairs every SR patch with its best candidate (first minimum of
+ * cand [B,ncand,27] / cnrm [B,ncand]; sst_bb_match_dist pairs every SR patch with its best candidate (first minimum of
  * alpha*d(sr_i,c_j) + beta*d(gt_i,c_j), d = clamped expanded squared distance of utils.py:173-187) and produces the selected
  * indices, d(loss)/d(sr) and per-workgroup partial sums of the L1 / L2 criterion (loss = sum of partials) */
 int sst_bb_blocks(int B, int H, int W);
@@ -418,10 +397,7 @@ int sst_bb_blocks(int B, int H, int W);
 int sst_bb_feature_dim(int mode);
 int sst_bb_patches(const float* img, float* cand, float* cnrm, int B, int H, int W, int ncand_total, int cand_off,
                    int mode, const float* st_mats, void* stream);
-int sst_bb_match(const float* sr, const float* cand, const float* cnrm, int* ind, float* dsr, float* partials, int B,
-                 int H, int W, int ncand, float alpha, float beta, int criterion_l2, int mode, const float* st_mats,
-                 void* stream);
-/* ... with the matching distance of utils.py:157-191 selectable (dist_l1 = 1: sum |x - y|; 0: the clamped expanded squared L2) */
+/* the matching distance of utils.py:157-191 selectable (dist_l1 = 1: sum |x - y|; 0: the clamped expanded squared L2) */
 int sst_bb_match_dist(const float* sr, const float* cand, const float* cnrm, int* ind, float* dsr, float* partials, int B,
                  int H, int W, int ncand, float alpha, float beta, int criterion_l2, int mode, const float* st_mats, int dist_l1,
                       void* stream);
@@ -455,8 +431,6 @@ int sst_head_fwd(const float* h, const float* w, const float* b, float* y, int M
                  void* stream);
 int sst_head_bwd(const float* h, const float* w, const float* dy, float* dh, float* dw, float* db, int M,
                  int N, int K, float slope, int accumulate, void* stream);
-int sst_flatten_act(const float* y, const float* scale, const float* shift, float slope, int act,
-                    float* flat, int B, int HW, int C, void* stream);
 /* scale / shift [B / grp_images][C] (passes batched as one tensor); grp_images = 0: one row */
 int sst_flatten_act_grp(const float* y, const float* scale, const float* shift, float slope, int act,
                         float* flat, int B, int HW, int C, int grp_images, void* stream);

@@ -553,17 +553,9 @@ SST_API int sst_bb_patches(const float* img, float* cand, float* cnrm, int B, in
   return SST_OK;
 }
 
-SST_API int sst_bb_match_dist(const float* sr, const float* cand, const float* cnrm, int* ind, float* dsr, float* partials, int B, int H,
-                              int W, int ncand, float alpha, float beta, int criterion_l2, int gram, const float* st_mats, int dist_l1,
-                              void* stream);
 // sr [B,3,H,W]; cand / cnrm: candidate table whose first (H/3)(W/3) rows are the full-resolution GT features.
 // ind [B, nP] int32; dsr [B,3,H,W] = d(loss)/d(sr) for loss = sum(partials) (criterion mean over B*nP*D elements);
-// partials [sst_bb_blocks(B,H,W)].
-SST_API int sst_bb_match(const float* sr, const float* cand, const float* cnrm, int* ind, float* dsr, float* partials, int B, int H,
-                         int W, int ncand, float alpha, float beta, int criterion_l2, int gram, const float* st_mats, void* stream) {
-  return sst_bb_match_dist(sr, cand, cnrm, ind, dsr, partials, B, H, W, ncand, alpha, beta, criterion_l2, gram, st_mats, 0, stream);
-}
-// ... with the matching distance of utils.py:157-191 selectable: dist_l1 = 0 the (clamped, expanded) squared L2, 1 the L1 distance
+// partials [sst_bb_blocks(B,H,W)].  Matching distance of utils.py:157-191: dist_l1 = 0 the (clamped, expanded) squared L2, 1 the L1 distance
 SST_API int sst_bb_match_dist(const float* sr, const float* cand, const float* cnrm, int* ind, float* dsr, float* partials, int B, int H,
                               int W, int ncand, float alpha, float beta, int criterion_l2, int gram, const float* st_mats, int dist_l1,
                               void* stream) {

@@ -552,21 +552,9 @@ inline int grid_for(int64_t work_items) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ C ABI
-SST_API int sst_bn_finalize_grp(const float* stats, const float* cnt, int ntiles, int C, int groups, const float* gamma,
-                                const float* beta, float* run_mean, float* run_var, float* mean, float* rstd, float* scale,
-                                float* shift, float eps, float momentum, void* stream);
-SST_API int sst_bn_finalize(const float* stats, const float* cnt, int ntiles, int C, const float* gamma, const float* beta,
-                            float* run_mean, float* run_var, float* mean, float* rstd, float* scale, float* shift,
-                            float eps, float momentum, void* stream) {
-  SST_REQUIRE(stats && cnt && gamma && beta && mean && rstd && scale && shift && ntiles > 0 && C > 0,
-              "sst_bn_finalize: bad argument");
-  SST_REQUIRE((run_mean == nullptr) == (run_var == nullptr), "sst_bn_finalize: running stats must come together");
-  return sst_bn_finalize_grp(stats, cnt, ntiles, C, 1, gamma, beta, run_mean, run_var, mean, rstd, scale, shift, eps, momentum, stream);
-}
-
-// The same for `groups` passes batched as one tall image: stats / cnt hold ntiles tiles = groups equal consecutive ranges; mean / rstd /
-// scale / shift are [groups][C]; the running statistics take one momentum step per group, in group order (the order the reference runs
-// the passes in, train.py:155-158).
+// `groups` passes batched as one tall image (1: a plain batch): stats / cnt hold ntiles tiles = groups equal consecutive ranges; mean /
+// rstd / scale / shift are [groups][C]; the running statistics take one momentum step per group, in group order (the order the
+// reference runs the passes in, train.py:155-158).
 SST_API int sst_bn_finalize_grp(const float* stats, const float* cnt, int ntiles, int C, int groups, const float* gamma,
                                 const float* beta, float* run_mean, float* run_var, float* mean, float* rstd, float* scale,
                                 float* shift, float eps, float momentum, void* stream) {
@@ -630,12 +618,6 @@ static int launch_bwd_reduce(const float* g, const float* g2, const float* y, co
   bwd_reduce_kernel<<<dim3(nblk, groups), NT, smem, sst_stream(stream)>>>(g, g2, y, scale, shift, slope, slope_const, act, partial, R, C, rpb);
   SST_LAUNCH_CHECK("bwd_reduce_kernel");
   return SST_OK;
-}
-
-SST_API int sst_bwd_reduce(const float* g, const float* g2, const float* y, const float* scale, const float* shift,
-                           const float* slope, float slope_const, int act, float* partial, int64_t R, int C,
-                           void* stream) {
-  return launch_bwd_reduce(g, g2, y, scale, shift, slope, slope_const, act, partial, R, C, stream);
 }
 
 // ---- the same three steps for `groups` passes batched as one tall tensor [groups * R rows][C] (R rows per group): scale / shift / mean /

@@ -587,23 +587,10 @@ SST_API int sst_conv_pipe_fwd_grp(const float* x, const float* wp, float* y, con
   return SST_OK;
 }
 
-SST_API int sst_conv_pipe_fwd(const float* x, const float* wp, float* y, const float* bias, const float* in_scale,
-                              const float* in_shift, const float* in_slope, float in_slope_const, int in_act, float* stats,
-                              float* stats_cnt, const float* epi_y, const float* epi_scale, const float* epi_shift,
-                              const float* epi_slope, float epi_slope_const, int epi_act, float* epi_partial, float* ws, int B,
-                              int H, int W, int Cin, int Cout, int ksize, int stride, void* stream) {
-  return sst_conv_pipe_fwd_grp(x, wp, y, bias, in_scale, in_shift, in_slope, in_slope_const, in_act, stats, stats_cnt, epi_y, epi_scale,
-                               epi_shift, epi_slope, epi_slope_const, epi_act, epi_partial, ws, B, H, W, Cin, Cout, ksize, stride, 0, stream);
-}
-
 // ---- stride-2 data-gradient on the pipelined kernel (MODE 1).  dx [B,H,W,Cin] = conv_transpose(dy [B,H/2,W/2,Cout]) for
 // y = conv3x3(x, stride 2, pad 1); wp = the buffer of sst_conv_s2_dgrad_pack (its 5th section).  Even H, W; Cout % 64 == 0
 // (K blocks), Cin % 32 == 0.
 int64_t sst_conv_s2_dgrad_pipe_section(int Cout, int Cin);      // conv_fwd.hip
-SST_API int sst_conv_s2_dgrad_pipe_bwdstats_grp(const float* dy, const float* wp, float* dx, float* ws, const float* epi_y,
-                                                const float* epi_scale, const float* epi_shift, const float* epi_slope,
-                                                float epi_slope_const, int epi_act, float* epi_partial, int B, int H, int W, int Cin,
-                                                int Cout, int grp_images, void* stream);
 
 namespace {
 PipePlan pipe_plan_s2d(int B, int H, int W, int Cin, int Cout) {
@@ -642,16 +629,9 @@ SST_API int64_t sst_conv_s2_dgrad_pipe_ws_floats(int B, int H, int W, int Cin, i
   return (pl.tw && pl.ksplit > 1) ? (int64_t)pl.ksplit * pl.n_mt * pl.nfc * 4 * 1024 : 0;
 }
 SST_API int sst_conv_s2_dgrad_pipe_stat_tiles(int B, int H, int W, int Cin, int Cout) { return pipe_plan_s2d(B, H, W, Cin, Cout).n_mt * 4; }
-// ... with the BatchNorm / activation backward partials of dx against epi_y (the saved output of the layer below, [B,H,W,Cin]) in
-// the epilogue: epi_partial [sst_conv_s2_dgrad_pipe_stat_tiles()][3][Cin], the layout sst_bwd_finalize consumes (null: none).
-SST_API int sst_conv_s2_dgrad_pipe_bwdstats(const float* dy, const float* wp, float* dx, float* ws, const float* epi_y,
-                                            const float* epi_scale, const float* epi_shift, const float* epi_slope,
-                                            float epi_slope_const, int epi_act, float* epi_partial, int B, int H, int W, int Cin,
-                                            int Cout, void* stream) {
-  return sst_conv_s2_dgrad_pipe_bwdstats_grp(dy, wp, dx, ws, epi_y, epi_scale, epi_shift, epi_slope, epi_slope_const, epi_act, epi_partial,
-                                             B, H, W, Cin, Cout, 0, stream);
-}
-// ... with coefficient groups (see sst_conv_pipe_fwd_grp): epi_scale / epi_shift [B / grp_images][Cin], the partial rows of a pass are
+// The data-gradient can leave the BatchNorm / activation backward partials of dx against epi_y (the saved output of the layer below,
+// [B,H,W,Cin]) in its epilogue: epi_partial [sst_conv_s2_dgrad_pipe_stat_tiles()][3][Cin], the layout sst_bwd_finalize consumes (null:
+// none).  With coefficient groups (see sst_conv_pipe_fwd_grp): epi_scale / epi_shift [B / grp_images][Cin], the partial rows of a pass are
 // the p-th of B / grp_images equal consecutive ranges (a tile of the class grid never straddles a pass: sst_conv_s2_dgrad_pipe_groups_ok)
 SST_API int sst_conv_s2_dgrad_pipe_groups_ok(int B, int H, int W, int Cin, int Cout, int grp_images) {
   const PipePlan pl = pipe_plan_s2d(B, H, W, Cin, Cout);
@@ -699,9 +679,5 @@ SST_API int sst_conv_s2_dgrad_pipe_bwdstats_grp(const float* dy, const float* wp
   if (pl.tw == 8) SST_S2D_LAUNCH(8); else if (pl.tw == 4) SST_S2D_LAUNCH(4); else SST_S2D_LAUNCH(2);
 #undef SST_S2D_LAUNCH
   return SST_OK;
-}
-SST_API int sst_conv_s2_dgrad_pipe(const float* dy, const float* wp, float* dx, float* ws, int B, int H, int W, int Cin, int Cout,
-                                   void* stream) {
-  return sst_conv_s2_dgrad_pipe_bwdstats(dy, wp, dx, ws, nullptr, nullptr, nullptr, nullptr, 0.f, 0, nullptr, B, H, W, Cin, Cout, stream);
 }
 

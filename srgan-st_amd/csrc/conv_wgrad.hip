@@ -695,9 +695,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 
 }  // namespace
 
-// ------------------------------------------------------------------------------------------ C ABI
-// Number of pixel chunks the wgrad kernel will use for this shape (slab floats = chunks*KS*KS*Cout*Cin).
-SST_API int sst_conv_wgrad_chunks(int B, int Ho, int Wo, int Cin, int Cout, int ksize) {
+// Number of pixel chunks the general (per-tap) wgrad kernel will use for this shape (slab floats = chunks*KS*KS*Cout*Cin).
+static int sst_conv_wgrad_chunks(int B, int Ho, int Wo, int Cin, int Cout, int ksize) {
   const int64_t M = (int64_t)B * Ho * Wo;
   const int nblk = ((Cout + 63) / 64) * ((Cin + 63) / 64);
   // Measured on MI355X (tools/ablate_wgrad.py): ~4 co-resident workgroups per CU hide the staging latency best, as long
@@ -1187,13 +1186,13 @@ void wgrad_shape_args(WgradArgs& a, const WgradPlan& pl, int B, int H, int W, in
 }
 }  // namespace
 
-// Chunk count to size a layer's slab with (slab floats = chunks*k*k*Cout*Cin) for sst_conv_wgrad (njobs = 1) / sst_conv_wgrad_grouped
+// Chunk count to size a layer's slab with (slab floats = chunks*k*k*Cout*Cin) for sst_conv_wgrad_grp (njobs = 1) / sst_conv_wgrad_grouped
 // launches of this shape; H, W are the INPUT size.
 SST_API int sst_conv_wgrad_chunks2(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int njobs) {
   return wgrad_plan(B, H, W, Cin, Cout, ksize, stride, njobs, false, ACT_NONE, njobs > 1).slab_chunks;
 }
 
-// Name of the main kernel sst_conv_wgrad (njobs = 1) / sst_conv_wgrad_grouped launch for this shape when called plain: no input
+// Name of the main kernel sst_conv_wgrad_grp (njobs = 1) / sst_conv_wgrad_grouped launch for this shape when called plain: no input
 // affine, no activation (rocprofv3 spelling).
 SST_API const char* sst_conv_wgrad_kernel_name(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int njobs) {
   return wgrad_plan(B, H, W, Cin, Cout, ksize, stride, njobs, false, ACT_NONE, njobs > 1).name;
@@ -1282,13 +1281,6 @@ SST_API int sst_conv_wgrad_grp(const float* x, const float* dy, float* slab, flo
   launch_wgrad_reduce(slab, dw, pl.nchunk, KK, Cout, Cin, accumulate, nullptr, 1, st);
   SST_LAUNCH_CHECK("wgrad_reduce_kernel");
   return SST_OK;
-}
-
-SST_API int sst_conv_wgrad(const float* x, const float* dy, float* slab, float* dw, const float* in_scale,
-                           const float* in_shift, const float* in_slope, float in_slope_const, int in_act, int B, int H,
-                           int W, int Cin, int Cout, int stride, int ksize, int accumulate, void* stream) {
-  return sst_conv_wgrad_grp(x, dy, slab, dw, in_scale, in_shift, in_slope, in_slope_const, in_act, B, H, W, Cin, Cout, stride, ksize,
-                            accumulate, 0, stream);
 }
 
 // jobs: HOST array of njobs <= 24 records {slab, dw, nchunk, k*k, Cout, Cin, accumulate, 0} (two pointers + six ints = 40 bytes):

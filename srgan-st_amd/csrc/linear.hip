@@ -444,7 +444,3 @@ SST_API int sst_flatten_act_grp(const float* y, const float* scale, const float*
   SST_LAUNCH_CHECK("flatten_act_kernel");
   return SST_OK;
 }
-SST_API int sst_flatten_act(const float* y, const float* scale, const float* shift, float slope, int act, float* flat,
-                            int B, int HW, int C, void* stream) {
-  return sst_flatten_act_grp(y, scale, shift, slope, act, flat, B, HW, C, 0, stream);
-}

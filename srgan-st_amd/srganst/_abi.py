@@ -51,8 +51,6 @@ SIGNATURES = {
     "sst_conv_pipe_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "sst_conv_pipe_stat_tiles": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "sst_conv_pipe_ws_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "sst_conv_pipe_fwd": (c_int, [P, P, P, P, P, P, P, c_float, c_int, P, P, P, P, P, P, c_float, c_int, P, P,
-                                  c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_conv_pipe_groups_ok": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "sst_conv_pipe_fwd_grp": (c_int, [P, P, P, P, P, P, P, c_float, c_int, P, P, P, P, P, P, c_float, c_int, P, P,
                                       c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
@@ -61,9 +59,7 @@ SIGNATURES = {
                                 c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_conv_s2_dgrad_pipe_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "sst_conv_s2_dgrad_pipe_ws_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
-    "sst_conv_s2_dgrad_pipe": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_conv_s2_dgrad_pipe_stat_tiles": (c_int, [c_int, c_int, c_int, c_int, c_int]),
-    "sst_conv_s2_dgrad_pipe_bwdstats": (c_int, [P, P, P, P, P, P, P, P, c_float, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_conv_s2_dgrad_pipe_groups_ok": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "sst_conv_s2_dgrad_pipe_bwdstats_grp": (c_int, [P, P, P, P, P, P, P, P, c_float, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_conv_acc_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
@@ -76,22 +72,17 @@ SIGNATURES = {
     "sst_conv_dgrad_bwdstats": (c_int, [P, P, P, P, P, P, P, P, c_float, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_conv_dgrad_fused": (c_int, [P, P, P, P, P, P, P, P, c_float, c_int, P, P, P, P, P, P, P, P, c_float, c_int, P,
                                      c_int, c_int, c_int, c_int, c_int, c_int, P]),
-    "sst_conv_wgrad_chunks": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "sst_conv_wgrad_chunks2": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
-    "sst_conv_wgrad": (c_int, [P, P, P, P, P, P, P, c_float, c_int, c_int, c_int, c_int, c_int, c_int,
-                               c_int, c_int, c_int, P]),
     "sst_conv_wgrad_groups_ok": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "sst_conv_wgrad_grp": (c_int, [P, P, P, P, P, P, P, c_float, c_int, c_int, c_int, c_int, c_int, c_int,
                                    c_int, c_int, c_int, c_int, P]),
     "sst_conv_wgrad_grouped": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_conv_wgrad_pending_reduce": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "sst_wgrad_reduce_multi": (c_int, [P, c_int, P]),
-    "sst_bn_finalize": (c_int, [P, P, c_int, c_int, P, P, P, P, P, P, P, P, c_float, c_float, P]),
     "sst_bn_finalize_grp": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_float, c_float, P]),
     "sst_bn_eval_affine": (c_int, [P, P, P, P, P, P, c_int, c_float, P]),
     "sst_bn_residual": (c_int, [P, P, P, P, P, P, c_int64, c_int, P]),
     "sst_bwd_reduce_blocks": (c_int, [c_int64, c_int]),
-    "sst_bwd_reduce": (c_int, [P, P, P, P, P, P, c_float, c_int, P, c_int64, c_int, P]),
     "sst_bwd_finalize": (c_int, [P, c_int, c_int, c_float, P, P, P, P, P, P, P, P, P, c_int, P]),
     "sst_bwd_reduce_grp": (c_int, [P, P, P, P, P, P, c_float, c_int, P, c_int64, c_int, c_int, P]),
     "sst_bwd_finalize_grp": (c_int, [P, c_int, c_int, c_float, c_int, P, P, P, P, P, P, P, P, c_int, P]),
@@ -124,7 +115,6 @@ SIGNATURES = {
     "sst_bb_blocks": (c_int, [c_int, c_int, c_int]),
     "sst_bb_feature_dim": (c_int, [c_int]),
     "sst_bb_patches": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
-    "sst_bb_match": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, P, P]),
     "sst_bb_match_dist": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, P, c_int, P]),
     "sst_bbg_patches": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "sst_bbg_blocks": (c_int, [c_int, c_int]),
@@ -154,7 +144,6 @@ SIGNATURES = {
     "sst_linear_wgrad": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "sst_head_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, P]),
     "sst_head_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_int, P]),
-    "sst_flatten_act": (c_int, [P, P, P, c_float, c_int, P, c_int, c_int, c_int, P]),
     "sst_flatten_act_grp": (c_int, [P, P, P, c_float, c_int, P, c_int, c_int, c_int, c_int, P]),
 }
 

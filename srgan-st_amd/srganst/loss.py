@@ -16,32 +16,36 @@ from torch import nn
 from . import _abi
 
 
+def _st_workspace(x, gt, ws):
+    """Checks a structure-tensor input pair and (re)builds the kernels' partials / last-arriver counter in the criterion's cache `ws`
+    when device or shape changed -> the workspace size in floats."""
+    if x.dtype != torch.float32 or gt.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.shape != gt.shape:
+        raise _abi.HipPathError(f"StructureTensorLoss: expected fp32 [B,3,H,W] pairs, got {tuple(x.shape)} / {tuple(gt.shape)}")
+    B, _, H, W = x.shape
+    n = ctypes.c_int64()
+    _abi.check(_abi.lib().sst_st_loss_workspace(B, H, W, ctypes.byref(n)), "sst_st_loss_workspace")
+    key = (x.device, B, H, W)
+    if ws.get("key") != key:
+        ws["key"] = key
+        ws["partials"] = torch.empty(n.value, device=x.device, dtype=torch.float32)
+        ws["counter"] = torch.zeros(1, device=x.device, dtype=torch.int32)
+    return n.value
+
+
 class _StLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gt, sigma, rho, normalize, ws):
-        if x.dtype != torch.float32 or gt.dtype != torch.float32:
-            raise _abi.HipPathError("StructureTensorLoss: fp32 only")
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape != gt.shape:
-            raise _abi.HipPathError(f"StructureTensorLoss: expected [B,3,H,W] pairs, got {tuple(x.shape)} / {tuple(gt.shape)}")
+        from . import ops
+        _st_workspace(x, gt, ws)
         x = x.contiguous()
         gt = gt.contiguous()
         B, _, H, W = x.shape
-        lib = _abi.lib()
-        n = ctypes.c_int64()
-        _abi.check(lib.sst_st_loss_workspace(B, H, W, ctypes.byref(n)), "sst_st_loss_workspace")
-        key = (x.device, B, H, W)
-        if ws.get("key") != key:
-            ws["key"] = key
-            ws["partials"] = torch.empty(n.value, device=x.device, dtype=torch.float32)
-            ws["counter"] = torch.zeros(1, device=x.device, dtype=torch.int32)
         gS = torch.empty_like(x)
         loss = torch.empty((), device=x.device, dtype=torch.float32)
-        from . import ops
         args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(gS), _abi.ptr(ws["partials"]), _abi.ptr(ws["counter"]), B, H, W,
                 sigma, rho, int(normalize))
-        _abi.check(lib.sst_st_loss_fwd(*args, _abi.stream_ptr()), "sst_st_loss_fwd")
         # algorithmic bytes (SURVEY 8d): forward reads sr + gt, backward writes d(sr): 3 x 3*H*W*4 B per image in all
-        ops._trace_hbm("st_loss_fwd_kernel", 2.0 * x.numel() * 4, lambda: lib.sst_st_loss_fwd(*args, _abi.stream_ptr()), x, gt, loss, gS, ws)
+        ops._launch_hbm(_abi.lib().sst_st_loss_fwd, args, "sst_st_loss_fwd", "st_loss_fwd_kernel", 2.0 * x.numel() * 4, (x, gt, loss, gS, ws))
         ctx.save_for_backward(x, gS)
         ctx.cfg = (sigma, rho)
         return loss
@@ -123,26 +127,17 @@ FUSE_PIXEL_INTO_ST = os.environ.get("SST_FUSE_PIXEL_ST", "1") != "0"
 def _st_pixel_fwd(x, gt, sigma, rho, normalize, ws, mode):
     """Structure-tensor loss and pixel criterion (mode 0 MSE / 1 L1) of (x, gt) in one launch -> (st_loss, pixel_loss, gS)."""
     from . import ops
-    if x.dtype != torch.float32 or gt.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.shape != gt.shape:
-        raise _abi.HipPathError(f"StructureTensorLoss: expected fp32 [B,3,H,W] pairs, got {tuple(x.shape)} / {tuple(gt.shape)}")
+    n = _st_workspace(x, gt, ws)
     B, _, H, W = x.shape
-    lib = _abi.lib()
-    n = ctypes.c_int64()
-    _abi.check(lib.sst_st_loss_workspace(B, H, W, ctypes.byref(n)), "sst_st_loss_workspace")
-    key = (x.device, B, H, W)
-    if ws.get("key") != key:
-        ws["key"] = key
-        ws["partials"] = torch.empty(n.value, device=x.device, dtype=torch.float32)
-        ws["counter"] = torch.zeros(1, device=x.device, dtype=torch.int32)
-    if ws.get("pix_partials") is None or ws["pix_partials"].numel() != n.value or ws["pix_partials"].device != x.device:
-        ws["pix_partials"] = torch.empty(n.value, device=x.device, dtype=torch.float32)
+    if ws.get("pix_partials") is None or ws["pix_partials"].numel() != n or ws["pix_partials"].device != x.device:
+        ws["pix_partials"] = torch.empty(n, device=x.device, dtype=torch.float32)
     gS = torch.empty_like(x)
     loss = torch.empty((), device=x.device, dtype=torch.float32)
     pix = torch.empty((), device=x.device, dtype=torch.float32)
     args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(gS), _abi.ptr(ws["partials"]), _abi.ptr(ws["counter"]), _abi.ptr(pix),
             _abi.ptr(ws["pix_partials"]), int(mode), B, H, W, sigma, rho, int(normalize))
-    _abi.check(lib.sst_st_pixel_loss_fwd(*args, _abi.stream_ptr()), "sst_st_pixel_loss_fwd")
-    ops._trace_hbm("st_loss_fwd_kernel", 2.0 * x.numel() * 4, lambda: lib.sst_st_pixel_loss_fwd(*args, _abi.stream_ptr()), x, gt, loss, gS, ws, pix)
+    ops._launch_hbm(_abi.lib().sst_st_pixel_loss_fwd, args, "sst_st_pixel_loss_fwd", "st_loss_fwd_kernel", 2.0 * x.numel() * 4,
+                    (x, gt, loss, gS, ws, pix))
     return loss, pix, gS
 
 
@@ -205,16 +200,14 @@ class _CriterionSumFn(torch.autograd.Function):
             t = ctx.terms[si]
             bargs = (_abi.ptr(sr), _abi.ptr(gt), _abi.ptr(ctx.gS[si]), _abi.ptr(dsr), _abi.ptr(g), ctx.weights[si], ctx.weights[pi], mode, 0,
                      B, H, W, float(t.sigma), float(t.rho))
-            _abi.check(_abi.lib().sst_st_pixel_loss_bwd(*bargs, _abi.stream_ptr()), "sst_st_pixel_loss_bwd")
-            ops._trace_hbm("st_loss_bwd_kernel", 1.0 * sr.numel() * 4, lambda: _abi.lib().sst_st_pixel_loss_bwd(*bargs, _abi.stream_ptr()),
-                           sr, gt, ctx.gS[si], dsr, g)
+            ops._launch_hbm(_abi.lib().sst_st_pixel_loss_bwd, bargs, "sst_st_pixel_loss_bwd", "st_loss_bwd_kernel", 1.0 * sr.numel() * 4,
+                            (sr, gt, ctx.gS[si], dsr, g))
             return dsr, None, None, None, None
         for i, (t, w) in enumerate(zip(ctx.terms, ctx.weights)):
             if isinstance(t, StructureTensorLoss):
                 bargs = (_abi.ptr(sr), _abi.ptr(ctx.gS[i]), _abi.ptr(dsr), _abi.ptr(g), w, int(i > 0), B, H, W, float(t.sigma), float(t.rho))
-                _abi.check(_abi.lib().sst_st_loss_bwd(*bargs, _abi.stream_ptr()), "sst_st_loss_bwd")
-                ops._trace_hbm("st_loss_bwd_kernel", 1.0 * sr.numel() * 4, lambda bargs=bargs: _abi.lib().sst_st_loss_bwd(*bargs, _abi.stream_ptr()),
-                               sr, ctx.gS[i], dsr, g)
+                ops._launch_hbm(_abi.lib().sst_st_loss_bwd, bargs, "sst_st_loss_bwd", "st_loss_bwd_kernel", 1.0 * sr.numel() * 4,
+                                (sr, ctx.gS[i], dsr, g))
             else:
                 ops.pixel_loss_bwd(sr, gt, 0 if isinstance(t, MSELoss) else 1, scale_dev=g, scale_host=w, out=dsr, accumulate=i > 0)
         return dsr, None, None, None, None

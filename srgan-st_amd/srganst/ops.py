@@ -19,54 +19,39 @@ ACT_NONE, ACT_SLOPE = 0, 1
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
 
 
-# --- optional per-launch timing of the MFMA kernels (bench.py roofline leg): list of (kernel, flops, ev0, ev1)
-PROFILE = None
-
-
-# --- optional launch trace (bench.py roofline leg): kernel name -> list of (relaunch closure, flops).  The closures
+# --- optional launch trace (bench.py roofline leg): kernel name -> list of (relaunch closure, flops, keep-alive).  The closures
 # hold their tensors alive and re-issue exactly the same launch, so a kernel family can be replayed back-to-back
 # from a hipGraph (GPU-bound timing, no host gaps).
 TRACE = None
-
-
-def _trace(name, flops, fn, *keep):
-    if TRACE is not None:
-        TRACE.setdefault(name, []).append((fn, flops, keep))
-
 
 # --- the same for the HBM-bound kernels (structure-tensor loss, classifier GEMMs, Adam): name -> [(relaunch closure, ALGORITHMIC
 # bytes of the launch, keep-alive)]
 TRACE_HBM = None
 
 
-def _trace_hbm(name, nbytes, fn, *keep):
-    if TRACE_HBM is not None:
-        TRACE_HBM.setdefault(name, []).append((fn, float(nbytes), keep))
-
-
-def _prof_begin():
-    if PROFILE is None:
-        return None
-    e = torch.cuda.Event(enable_timing=True)
-    e.record()
-    return e
-
-
-def _prof_end(e0, name, flops):
-    if e0 is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        PROFILE.append((name, flops, e0, e1))
-
-
 def _launch(fn, args, what, flops, name_fn, keep):
-    """One conv launch fn(*args, stream): checked, timed into PROFILE and registered in TRACE (with a closure that re-issues the
-    identical launch and holds `keep` alive) under name_fn(), which is evaluated only when one of the two is on."""
-    e0 = _prof_begin()
+    """One MFMA launch fn(*args, stream): checked and, when TRACE is on, registered (with a closure that re-issues the identical
+    launch and holds `keep` alive) under name_fn(), which is evaluated only then."""
     check(fn(*args, stream_ptr()), what)
-    name = name_fn() if (PROFILE is not None or TRACE is not None) else ""
-    _prof_end(e0, name, flops)
-    _trace(name, flops, lambda: fn(*args, stream_ptr()), *keep)
+    if TRACE is not None:
+        TRACE.setdefault(name_fn(), []).append((lambda: fn(*args, stream_ptr()), flops, keep))
+
+
+def _launch_hbm(fn, args, what, name, nbytes, keep):
+    """The same for an HBM-bound launch: registered in TRACE_HBM under `name` with its algorithmic bytes."""
+    check(fn(*args, stream_ptr()), what)
+    if TRACE_HBM is not None:
+        TRACE_HBM.setdefault(name, []).append((lambda: fn(*args, stream_ptr()), float(nbytes), keep))
+
+
+def _in_args(scale=None, shift=None, slope=None, slope_const=0.0, act=ACT_NONE):
+    """The input-side coefficients as the library takes them -> (five arguments, tensors to keep alive)."""
+    return (ptr(scale), ptr(shift), ptr(slope), float(slope_const), int(act)), (scale, shift, slope)
+
+
+def _epi_args(y=None, scale=None, shift=None, slope=None, slope_const=0.0, act=0):
+    """The epilogue (backward partials against y) as the library takes it -> (six arguments, tensors to keep alive)."""
+    return (ptr(y), ptr(scale), ptr(shift), ptr(slope), float(slope_const), int(act)), (y, scale, shift, slope)
 
 
 def _conv_name(B, H, W, cin, cout, ksize, stride, out_mode=0, fused_in=0):
@@ -97,14 +82,55 @@ def conv_out_hw(h, w, k, stride):
     return (h + 2 * p - k) // stride + 1, (w + 2 * p - k) // stride + 1
 
 
+CONV_NS = os.environ.get("SST_CONV_NS", "1") != "0"      # the N-split form of the pipelined conv where it applies (0: dev A/B)
+
+
+def _pipe_on():
+    """SST_CONV_PIPE=0 (dev switch, read per call) keeps every shape off the persistent pipelined kernels (csrc/conv_pipe.hip)."""
+    return os.environ.get("SST_CONV_PIPE", "1") != "0"
+
+
+class _ConvRoute:
+    """Which entry takes a forward-form conv - "general" (sst_conv_fwd / sst_conv_dgrad_bwdstats), "pipe" (sst_conv_pipe_fwd_grp) or
+    "ns" (sst_conv_ns_fwd: same tiling, statistics rows and packed weights, no split-K workspace) - and what follows from the choice.
+    plain: no residual and no pre-activation copy.  The NHWC store goes to the pipelined plan where that takes the shape, and within
+    it to the N-split kernel where that does; the PixelShuffle store without statistics (the up-sampling blocks' convs,
+    model.py:157-161) goes to the N-split kernel whatever SST_CONV_PIPE says; everything else is general."""
+
+    def __init__(self, shp, out_mode=OUT_NHWC, plain=True, want_stats=False):
+        L = _abi.lib()
+        self.shp, self.out_mode = shp, int(out_mode)
+        pipe_tw = L.sst_conv_pipe_supported(*shp) if plain and out_mode == OUT_NHWC and _pipe_on() else 0
+        shuffle = plain and out_mode == OUT_SHUFFLE and not want_stats
+        ns_tw = L.sst_conv_ns_supported(*shp, self.out_mode) if CONV_NS and (pipe_tw or shuffle) else 0
+        self.kind, self.tw = ("ns", ns_tw) if ns_tw else ("pipe", pipe_tw) if pipe_tw else ("general", 0)       # tw: tile width
+
+    def rows(self):
+        """Rows of the statistics / backward-partial tensors the launch fills."""
+        return (_abi.lib().sst_conv_stat_tiles if self.kind == "general" else _abi.lib().sst_conv_pipe_stat_tiles)(*self.shp)
+
+    def ws_floats(self):
+        return _abi.lib().sst_conv_pipe_ws_floats(*self.shp) if self.kind == "pipe" else 0
+
+    def name(self):
+        stride = self.shp[6]
+        if self.kind == "general":
+            return _conv_name(*self.shp, self.out_mode)
+        return f"conv_ns_kernel<{stride}, {self.tw}>" if self.kind == "ns" else f"conv_pipe_kernel<{stride}, {self.tw}, 0>"
+
+    def groups_ok(self, grp):
+        """Passes of `grp` images end on the tile boundaries of the pipelined plan (which must have taken the shape)."""
+        return self.kind != "general" and self.out_mode == OUT_NHWC and bool(_abi.lib().sst_conv_pipe_groups_ok(*self.shp, int(grp)))
+
+
 def conv_fwd(x, wp, cout, ksize=3, stride=1, bias=None, in_scale=None, in_shift=None, in_slope=None,
              in_slope_const=0.0, in_act=ACT_NONE, residual=None, want_stats=False, out_mode=OUT_NHWC,
              want_pre=False, grp=0, out=None):
     """x [B,H,W,Cin] NHWC -> y (layout per out_mode); returns (y, y_pre|None, stats|None, cnt|None).
     grp > 0: the batch is B / grp passes of grp images each, in_scale / in_shift are [B / grp, Cin] (pipelined kernel only)."""
     B, H, W, cin = x.shape
-    if grp and grp < B and in_scale is not None and not (out_mode == OUT_NHWC and residual is None and not want_pre
-                                                         and conv_pipe_groups_ok(B, H, W, cin, cout, ksize, stride, grp)):
+    route = _ConvRoute((B, H, W, cin, cout, ksize, stride), out_mode, residual is None and not want_pre, want_stats)
+    if grp and grp < B and in_scale is not None and not route.groups_ok(grp):
         raise _abi.HipPathError(f"conv_fwd: coefficient groups of {grp} images are not supported for this shape")
     ho, wo = conv_out_hw(H, W, ksize, stride)
     if out is not None:
@@ -118,42 +144,25 @@ def conv_fwd(x, wp, cout, ksize=3, stride=1, bias=None, in_scale=None, in_shift=
         y = _f32(B, cout, ho, wo, like=x)
     else:
         y = _f32(B, ho // 2, wo // 2, cout * 4, like=x)
-    if out_mode == OUT_NHWC and residual is None and not want_pre and conv_pipe_tw(B, H, W, cin, cout, ksize, stride):
-        y, stats, cnt, _ = _conv_pipe(x, wp, y, cout, ksize, stride, bias, in_scale, in_shift, in_slope, in_slope_const, in_act,
-                                      want_stats, grp=grp)
+    inp, ikeep = _in_args(in_scale, in_shift, in_slope, in_slope_const, in_act)
+    if route.kind != "general":
+        stats, cnt, _ = _conv_tile(route, x, wp, y, bias, (inp, ikeep), want_stats, grp=grp if out_mode == OUT_NHWC else 0)
         return y, None, stats, cnt
-    if (out_mode == OUT_SHUFFLE and residual is None and not want_pre and not want_stats and CONV_NS
-            and _abi.lib().sst_conv_ns_supported(B, H, W, cin, cout, ksize, stride, OUT_SHUFFLE)):
-        # the up-sampling blocks' convs (model.py:157-161): N-split kernel with the PixelShuffle store
-        y, _, _, _ = _conv_pipe(x, wp, y, cout, ksize, stride, bias, in_scale, in_shift, in_slope, in_slope_const, in_act, False,
-                                out_mode=OUT_SHUFFLE)
-        return y, None, None, None
     y_pre = torch.empty_like(y) if want_pre else None
     stats = cnt = None
     if want_stats:
-        mt = _abi.lib().sst_conv_stat_tiles(B, H, W, cin, cout, ksize, stride)
+        mt = route.rows()
         stats = _f32(mt, 2, cout, like=x)
         cnt = _f32(mt, like=x)
-    args = (ptr(x), ptr(wp), ptr(y), ptr(y_pre), ptr(bias), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const),
-            int(in_act), ptr(residual), ptr(stats), ptr(cnt), int(out_mode), B, H, W, cin, cout, ksize, stride)
-    _launch(_abi.lib().sst_conv_fwd, args, "sst_conv_fwd", 2.0 * B * ho * wo * cout * cin * ksize * ksize,
-            lambda: _conv_name(B, H, W, cin, cout, ksize, stride, out_mode),
-            (x, wp, y, y_pre, bias, in_scale, in_shift, in_slope, residual, stats, cnt))
+    args = (ptr(x), ptr(wp), ptr(y), ptr(y_pre), ptr(bias), *inp, ptr(residual), ptr(stats), ptr(cnt), int(out_mode), *route.shp)
+    _launch(_abi.lib().sst_conv_fwd, args, "sst_conv_fwd", 2.0 * B * ho * wo * cout * cin * ksize * ksize, route.name,
+            (x, wp, y, y_pre, bias, *ikeep, residual, stats, cnt))
     return y, y_pre, stats, cnt
-
-
-def conv_pipe_tw(B, H, W, cin, cout, ksize, stride):
-    """Tile width of the persistent pipelined conv kernel (csrc/conv_pipe.hip) when it takes this NHWC-store shape, else 0.
-    SST_CONV_PIPE=0 (dev switch) keeps every shape on the general kernel."""
-    if os.environ.get("SST_CONV_PIPE", "1") == "0":
-        return 0
-    return _abi.lib().sst_conv_pipe_supported(B, H, W, cin, cout, ksize, stride)
 
 
 def conv_pipe_groups_ok(B, H, W, cin, cout, ksize, stride, grp):
     """The pipelined conv kernel takes this shape AND passes of `grp` images end on its tile boundaries."""
-    return bool(conv_pipe_tw(B, H, W, cin, cout, ksize, stride)) and \
-        bool(_abi.lib().sst_conv_pipe_groups_ok(B, H, W, cin, cout, ksize, stride, int(grp)))
+    return _ConvRoute((B, H, W, cin, cout, ksize, stride)).groups_ok(grp)
 
 
 def conv_wgrad_groups_ok(B, H, W, cin, cout, ksize, stride, grp):
@@ -161,43 +170,27 @@ def conv_wgrad_groups_ok(B, H, W, cin, cout, ksize, stride, grp):
     return bool(_abi.lib().sst_conv_wgrad_groups_ok(B, H, W, cin, cout, ksize, stride, int(grp)))
 
 
-CONV_NS = os.environ.get("SST_CONV_NS", "1") != "0"      # the N-split form of the pipelined conv where it applies (0: dev A/B)
-
-
-def _conv_pipe(x, wp, y, cout, ksize, stride, bias=None, in_scale=None, in_shift=None, in_slope=None, in_slope_const=0.0,
-               in_act=ACT_NONE, want_stats=False, epi=None, grp=0, out_mode=OUT_NHWC):
-    """sst_conv_pipe_fwd: forward statistics (want_stats) or backward partials (epi = dict(y, scale, shift, slope, slope_const,
-    act)); returns (y, stats, cnt, partial)."""
-    B, H, W, cin = x.shape
+def _conv_tile(route, x, wp, y, bias, inp, want_stats=False, epi=None, grp=0):
+    """The launch of a conv its route gave to the pipelined or the N-split kernel: forward statistics (want_stats) or backward
+    partials (epi); inp / epi as _in_args / _epi_args return them.  Returns (stats, cnt, partial)."""
     L = _abi.lib()
-    shp = (B, H, W, cin, cout, ksize, stride)
+    B, H, W, cin, cout, ksize, stride = route.shp
     stats = cnt = partial = None
     if want_stats:
-        mt = L.sst_conv_pipe_stat_tiles(*shp)
+        mt = route.rows()
         stats, cnt = _f32(mt, 2, cout, like=x), _f32(mt, like=x)
-    e = epi or {}
     if epi is not None:
-        partial = _f32(L.sst_conv_pipe_stat_tiles(*shp), 3, cout, like=x)
-    ho, wo = conv_out_hw(H, W, ksize, stride)
-    flops = 2.0 * B * ho * wo * cout * cin * ksize * ksize
-    if CONV_NS and L.sst_conv_ns_supported(*shp, int(out_mode)):
-        # the N-split form (csrc/conv_nsplit.hip): same tiling, statistics rows and packed weights, no split-K workspace
-        nargs = (ptr(x), ptr(wp), ptr(y), ptr(bias), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const), int(in_act),
-                 ptr(stats), ptr(cnt), ptr(e.get("y")), ptr(e.get("scale")), ptr(e.get("shift")), ptr(e.get("slope")),
-                 float(e.get("slope_const", 0.0)), int(e.get("act", 0)), ptr(partial), *shp, int(out_mode), int(grp))
-        _launch(L.sst_conv_ns_fwd, nargs, "sst_conv_ns_fwd", flops,
-                lambda: f"conv_ns_kernel<{stride}, {L.sst_conv_ns_supported(*shp, int(out_mode))}>",
-                (x, wp, y, bias, in_scale, in_shift, in_slope, stats, cnt, partial, *[v for v in e.values() if torch.is_tensor(v)]))
-        return y, stats, cnt, partial
-    assert out_mode == OUT_NHWC
-    nws = L.sst_conv_pipe_ws_floats(*shp)
+        partial = _f32(route.rows(), 3, cout, like=x)
+    nws = route.ws_floats()
     ws = _f32(nws, like=x) if nws else None
-    args = (ptr(x), ptr(wp), ptr(y), ptr(bias), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const), int(in_act),
-            ptr(stats), ptr(cnt), ptr(e.get("y")), ptr(e.get("scale")), ptr(e.get("shift")), ptr(e.get("slope")),
-            float(e.get("slope_const", 0.0)), int(e.get("act", 0)), ptr(partial), ptr(ws), *shp, int(grp))
-    _launch(L.sst_conv_pipe_fwd_grp, args, "sst_conv_pipe_fwd", flops, lambda: f"conv_pipe_kernel<{stride}, {L.sst_conv_pipe_supported(*shp)}, 0>",
-            (x, wp, y, bias, in_scale, in_shift, in_slope, stats, cnt, partial, ws, *[v for v in e.values() if torch.is_tensor(v)]))
-    return y, stats, cnt, partial
+    (ia, ikeep), (ea, ekeep) = inp, epi or _epi_args()
+    ho, wo = conv_out_hw(H, W, ksize, stride)
+    ns = route.kind == "ns"
+    args = (ptr(x), ptr(wp), ptr(y), ptr(bias), *ia, ptr(stats), ptr(cnt), *ea, ptr(partial), *(() if ns else (ptr(ws),)), *route.shp,
+            *((route.out_mode,) if ns else ()), int(grp))
+    _launch(L.sst_conv_ns_fwd if ns else L.sst_conv_pipe_fwd_grp, args, "sst_conv_ns_fwd" if ns else "sst_conv_pipe_fwd",
+            2.0 * B * ho * wo * cout * cin * ksize * ksize, route.name, (x, wp, y, bias, *ikeep, stats, cnt, partial, ws, *ekeep))
+    return stats, cnt, partial
 
 
 _ONES = {}
@@ -266,14 +259,13 @@ def conv_dgrad_fused_acc(g, wd, cout, ksize=3, y2=None, in_scale=None, in_shift=
     out = _f32(B, H, W, cout, like=g)
     dy = torch.empty_like(g) if y2 is not None else None
     mean, rstd, gamma = bn if bn is not None else (None, None, None)
-    args = (ptr(g), ptr(y2), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const), int(in_act), ptr(dy), ptr(wd), ptr(out),
-            ptr(residual), ptr(epi_y), ptr(epi_scale), ptr(epi_shift), ptr(epi_slope), float(epi_slope_const), int(epi_act),
-            _dptr(bw_in_acc), ptr(mean), ptr(rstd), ptr(gamma), float(n), ptr(dgamma), ptr(dbeta), ptr(dslope), _dptr(bw_st_acc),
-            ACC_NREP, B, H, W, cin, cout, ksize)
+    inp, ikeep = _in_args(in_scale, in_shift, in_slope, in_slope_const, in_act)
+    epi, ekeep = _epi_args(epi_y, epi_scale, epi_shift, epi_slope, epi_slope_const, epi_act)
+    args = (ptr(g), ptr(y2), *inp, ptr(dy), ptr(wd), ptr(out), ptr(residual), *epi, _dptr(bw_in_acc), ptr(mean), ptr(rstd), ptr(gamma),
+            float(n), ptr(dgamma), ptr(dbeta), ptr(dslope), _dptr(bw_st_acc), ACC_NREP, B, H, W, cin, cout, ksize)
     _launch(_abi.lib().sst_conv_dgrad_fused_acc, args, "sst_conv_dgrad_fused_acc", 2.0 * B * H * W * cout * cin * ksize * ksize,
             lambda: _conv_name(B, H, W, cin, cout, ksize, 1, 0, 1),
-            (g, y2, in_scale, in_shift, in_slope, dy, wd, out, residual, epi_y, epi_scale, epi_shift, epi_slope, bw_in_acc, mean, rstd, gamma,
-             dgamma, dbeta, dslope, bw_st_acc))
+            (g, y2, *ikeep, dy, wd, out, residual, *ekeep, bw_in_acc, mean, rstd, gamma, dgamma, dbeta, dslope, bw_st_acc))
     return out, dy
 
 
@@ -308,19 +300,20 @@ def conv_wgrad(x, dy, dw_out, ksize=3, stride=1, in_scale=None, in_shift=None, i
     nch = _abi.lib().sst_conv_wgrad_chunks2(B, H, W, cin, cout, ksize, stride, 1)
     slab = _f32(nch * ksize * ksize * cout * cin, like=x)
     pend = 0
-    if defer_reduce is not None and PROFILE is None and TRACE is None:
+    if defer_reduce is not None and TRACE is None:
         pend = _abi.lib().sst_conv_wgrad_pending_reduce(B, H, W, cin, cout, ksize, stride, int(in_scale is not None), int(in_act))
         if pend:
             assert dw_out.is_contiguous()
             defer_reduce.append((slab, dw_out, pend, ksize * ksize, cout, cin, int(bool(accumulate))))
-    args = (ptr(x), ptr(dy), ptr(slab), ptr(dw_out), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const),
-            int(in_act), B, H, W, cin, cout, stride, ksize, int(bool(accumulate)) | (4 if pend else 0), int(grp))
+    inp, ikeep = _in_args(in_scale, in_shift, in_slope, in_slope_const, in_act)
+    args = (ptr(x), ptr(dy), ptr(slab), ptr(dw_out), *inp, B, H, W, cin, cout, stride, ksize, int(bool(accumulate)) | (4 if pend else 0),
+            int(grp))
 
     def name():
         n = _wgrad_name(B, H, W, cin, cout, ksize, stride, 1)
         return n + ("+c3m_reduce_kernel" if n == "wgrad_k3c3_mfma_kernel" else "+wgrad_reduce_kernel")
     _launch(_abi.lib().sst_conv_wgrad_grp, args, "sst_conv_wgrad", 2.0 * B * ho * wo * cout * cin * ksize * ksize, name,
-            (x, dy, slab, dw_out, in_scale, in_shift, in_slope))
+            (x, dy, slab, dw_out, *ikeep))
     return dw_out
 
 
@@ -529,6 +522,23 @@ S2D_EPI = os.environ.get("SST_S2D_EPI", "0") != "0"
 S2D_EPI_GRP = os.environ.get("SST_S2D_EPI_GRP", "0") != "0"      # ... for passes batched as one tall image (grp > 0)
 
 
+def _s2_dgrad_route(B, H, W, cin, cout, want_epi, grp):
+    """Which entry takes a stride-2 data-gradient and what follows: (tile width of the pipelined kernel or 0 = the merged-classes
+    kernel, workspace floats, rows of the epilogue's partials or 0 = none come out of it, trace name).
+    Measured on the G + D + ST step: 5.34 ms with the partials in the epilogue against 5.30 ms with the separate reduce pass (four
+    scattered epilogues per unit cost more than the three reduce launches they replace) - off unless SST_S2D_EPI=1 (ungrouped calls) /
+    SST_S2D_EPI_GRP=1 (passes batched as one tall image, which must end on tile boundaries)."""
+    L = _abi.lib()
+    shp = (B, H, W, cin, cout)
+    tw = L.sst_conv_s2_dgrad_pipe_supported(*shp) if _pipe_on() else 0
+    if not tw:
+        return 0, 0, 0, lambda: L.sst_conv_s2_dgrad_kernel_name(*shp, 0).decode()
+    grouped = bool(grp) and grp < B
+    epi = want_epi and (S2D_EPI_GRP and bool(L.sst_conv_s2_dgrad_pipe_groups_ok(*shp, int(grp))) if grouped else S2D_EPI)
+    return (tw, L.sst_conv_s2_dgrad_pipe_ws_floats(*shp), L.sst_conv_s2_dgrad_pipe_stat_tiles(*shp) if epi else 0,
+            lambda: f"conv_pipe_kernel<1, {tw}, 1>")
+
+
 def conv_s2_dgrad(dy, wp, H, W, cin, epi=None, grp=0):
     """dy [B,Ho,Wo,Cout] -> dx [B,H,W,Cin] for y = conv3x3(x, stride 2, pad 1).
     epi = dict(y, scale, shift, slope, slope_const, act): also the BatchNorm / activation backward partials of dx against epi["y"]
@@ -536,28 +546,20 @@ def conv_s2_dgrad(dy, wp, H, W, cin, epi=None, grp=0):
     B, ho, wo, cout = dy.shape
     dx = _f32(B, H, W, cin, like=dy)
     L = _abi.lib()
-    if os.environ.get("SST_CONV_PIPE", "1") != "0" and L.sst_conv_s2_dgrad_pipe_supported(B, H, W, cin, cout):
-        nws = L.sst_conv_s2_dgrad_pipe_ws_floats(B, H, W, cin, cout)
+    tw, nws, rows, name = _s2_dgrad_route(B, H, W, cin, cout, epi is not None, grp)
+    flops, partial = 2.0 * B * ho * wo * cout * cin * 9, None
+    if tw:
         ws = _f32(nws, like=dy) if nws else None
-        partial = None
-        # measured on the G + D + ST step: 5.34 ms with the partials in the epilogue against 5.30 ms with the separate reduce pass (four
-        # scattered epilogues per unit cost more than the three reduce launches they replace) - off unless SST_S2D_EPI=1
-        grouped = bool(grp) and grp < B
-        if epi is not None and ((S2D_EPI and not grouped) or
-                                (grouped and S2D_EPI_GRP and L.sst_conv_s2_dgrad_pipe_groups_ok(B, H, W, cin, cout, int(grp)))):
-            partial = _f32(L.sst_conv_s2_dgrad_pipe_stat_tiles(B, H, W, cin, cout), 3, cin, like=dy)
-        e = epi or {}
-        args = (ptr(dy), ptr(wp), ptr(dx), ptr(ws), ptr(e.get("y")) if partial is not None else None,
-                ptr(e.get("scale")) if partial is not None else None, ptr(e.get("shift")) if partial is not None else None,
-                ptr(e.get("slope")) if partial is not None else None, float(e.get("slope_const", 0.0)), int(e.get("act", 0)),
-                ptr(partial), B, H, W, cin, cout, int(grp) if partial is not None else 0)
-        _launch(L.sst_conv_s2_dgrad_pipe_bwdstats_grp, args, "sst_conv_s2_dgrad_pipe", 2.0 * B * ho * wo * cout * cin * 9,
-                lambda: f"conv_pipe_kernel<1, {L.sst_conv_s2_dgrad_pipe_supported(B, H, W, cin, cout)}, 1>",
-                (dy, wp, dx, ws, partial, e.get("y"), e.get("scale"), e.get("shift"), e.get("slope")))
-        return (dx, partial) if epi is not None else dx
-    _launch(L.sst_conv_s2_dgrad, (ptr(dy), ptr(wp), ptr(dx), B, H, W, cin, cout), "sst_conv_s2_dgrad", 2.0 * B * ho * wo * cout * cin * 9,
-            lambda: L.sst_conv_s2_dgrad_kernel_name(B, H, W, cin, cout, 0).decode(), (dy, wp, dx))
-    return (dx, None) if epi is not None else dx
+        ea, ekeep = _epi_args(**(epi or {}))
+        if rows:
+            partial = _f32(rows, 3, cin, like=dy)
+        else:               # no partials: neither the epilogue's tensors nor grp reach the library
+            ea, grp = (None,) * 4 + ea[4:], 0
+        _launch(L.sst_conv_s2_dgrad_pipe_bwdstats_grp, (ptr(dy), ptr(wp), ptr(dx), ptr(ws), *ea, ptr(partial), B, H, W, cin, cout, int(grp)),
+                "sst_conv_s2_dgrad_pipe", flops, name, (dy, wp, dx, ws, partial, *ekeep))
+    else:
+        _launch(L.sst_conv_s2_dgrad, (ptr(dy), ptr(wp), ptr(dx), B, H, W, cin, cout), "sst_conv_s2_dgrad", flops, name, (dy, wp, dx))
+    return (dx, partial) if epi is not None else dx
 
 
 def conv_s2_dgrad_fused(g, y2, wp, H, W, cin, cA=None, cB=None, cC=None, in_scale=None, in_shift=None, in_slope=None,
@@ -568,12 +570,12 @@ def conv_s2_dgrad_fused(g, y2, wp, H, W, cin, cA=None, cB=None, cC=None, in_scal
     dx = _f32(B, H, W, cin, like=g)
     dy = torch.empty_like(g)
     partial = _f32(_abi.lib().sst_conv_s2_dgrad_tiles(B, H, W), 3, cin, like=g) if epi_y is not None else None
-    args = (ptr(g), ptr(y2), ptr(cA), ptr(cB), ptr(cC), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const), int(in_act),
-            ptr(dy), ptr(wp), ptr(dx), ptr(epi_y), ptr(epi_scale), ptr(epi_shift), ptr(epi_slope), float(epi_slope_const), int(epi_act),
-            ptr(partial), B, H, W, cin, cout)
+    inp, ikeep = _in_args(in_scale, in_shift, in_slope, in_slope_const, in_act)
+    epi, ekeep = _epi_args(epi_y, epi_scale, epi_shift, epi_slope, epi_slope_const, epi_act)
+    args = (ptr(g), ptr(y2), ptr(cA), ptr(cB), ptr(cC), *inp, ptr(dy), ptr(wp), ptr(dx), *epi, ptr(partial), B, H, W, cin, cout)
     _launch(_abi.lib().sst_conv_s2_dgrad_fused, args, "sst_conv_s2_dgrad_fused", 2.0 * B * ho * wo * cout * cin * 9,
             lambda: _abi.lib().sst_conv_s2_dgrad_kernel_name(B, H, W, cin, cout, 1).decode(),
-            (g, y2, cA, cB, cC, in_scale, in_shift, in_slope, dy, wp, dx, epi_y, epi_scale, epi_shift, epi_slope, partial))
+            (g, y2, cA, cB, cC, *ikeep, dy, wp, dx, *ekeep, partial))
     return dx, dy, partial
 
 
@@ -583,9 +585,8 @@ def linear_fwd(x, w, bias, out=None):
     y = out if out is not None else _f32(M, N, like=x)
     assert tuple(y.shape) == (M, N) and y.is_contiguous()
     slab = _f32(_abi.lib().sst_linear_ksplit(M, N, K) * M * N, like=x)
-    args = (ptr(x), ptr(w), ptr(bias), ptr(y), ptr(slab), M, N, K)
-    check(_abi.lib().sst_linear_fwd(*args, stream_ptr()), "sst_linear_fwd")
-    _trace_hbm("linear_fwd_kernel", 4.0 * (N * K + M * K + M * N), lambda: _abi.lib().sst_linear_fwd(*args, stream_ptr()), x, w, bias, y, slab)
+    _launch_hbm(_abi.lib().sst_linear_fwd, (ptr(x), ptr(w), ptr(bias), ptr(y), ptr(slab), M, N, K), "sst_linear_fwd", "linear_fwd_kernel",
+                4.0 * (N * K + M * K + M * N), (x, w, bias, y, slab))
     return y
 
 
@@ -595,19 +596,16 @@ def linear_dgrad(dy, w, nhwc=None):
     K = w.shape[1]
     dx = _f32(M, K, like=dy)
     c, hw = nhwc if nhwc else (0, 0)
-    args = (ptr(dy), ptr(w), ptr(dx), M, N, K, c, hw)
-    check(_abi.lib().sst_linear_dgrad(*args, stream_ptr()), "sst_linear_dgrad")
-    _trace_hbm("linear_dgrad_kernel", 4.0 * (N * K + M * K + M * N), lambda: _abi.lib().sst_linear_dgrad(*args, stream_ptr()), dy, w, dx)
+    _launch_hbm(_abi.lib().sst_linear_dgrad, (ptr(dy), ptr(w), ptr(dx), M, N, K, c, hw), "sst_linear_dgrad", "linear_dgrad_kernel",
+                4.0 * (N * K + M * K + M * N), (dy, w, dx))
     return dx
 
 
 def linear_wgrad(dy, x, dw, db=None, accumulate=False):
     M, N = dy.shape
     K = x.shape[1]
-    args = (ptr(dy), ptr(x), ptr(dw), ptr(db), M, N, K, int(accumulate))
-    check(_abi.lib().sst_linear_wgrad(*args, stream_ptr()), "sst_linear_wgrad")
-    _trace_hbm("linear_wgrad_kernel", 4.0 * (N * K * (2 if accumulate else 1) + M * K + M * N),
-               lambda: _abi.lib().sst_linear_wgrad(*args, stream_ptr()), dy, x, dw, db)
+    _launch_hbm(_abi.lib().sst_linear_wgrad, (ptr(dy), ptr(x), ptr(dw), ptr(db), M, N, K, int(accumulate)), "sst_linear_wgrad",
+                "linear_wgrad_kernel", 4.0 * (N * K * (2 if accumulate else 1) + M * K + M * N), (dy, x, dw, db))
 
 
 def head_fwd(h, w, b, slope):
@@ -644,10 +642,8 @@ def wgrad_c3(big, small, dw_out, kind, in_slope=None, in_slope_const=0.0, in_act
     assert tuple(small.shape) == (B, H, W, 3)
     assert tuple(dw_out.shape) == ((3, C, 9, 9) if kind == 0 else (C, 3, 9, 9))
     slab = _f32(_abi.lib().sst_wgrad_c3_slab_floats(B, H, W, C), like=big)
-    e0 = _prof_begin()
     check(_abi.lib().sst_wgrad_c3(ptr(big), ptr(small), ptr(slab), ptr(dw_out), ptr(in_slope), float(in_slope_const), int(in_act),
                                   kind, B, H, W, C, int(accumulate), stream_ptr()), "sst_wgrad_c3")
-    _prof_end(e0, "wgrad_c3_kernel+reduce", 2.0 * B * H * W * C * 3 * 81)
     return dw_out
 
 
@@ -833,9 +829,7 @@ def conv9_c3_fwd(x3, w, mode, bias=None, wp=None):
         wp = _f32(_abi.lib().sst_conv9_c3_packed_floats(cout), like=w)
         check(_abi.lib().sst_conv9_c3_pack(ptr(w), ptr(wp), w.shape[0], w.shape[1], mode, stream_ptr()), "sst_conv9_c3_pack")
     y = _f32(B, H, W, cout, like=x3)
-    e0 = _prof_begin()
     check(_abi.lib().sst_conv9_c3_fwd(ptr(x3), ptr(wp), ptr(y), ptr(bias), B, H, W, cout, stream_ptr()), "sst_conv9_c3_fwd")
-    _prof_end(e0, "conv9_c3_fwd_kernel", 2.0 * B * H * W * cout * 3 * 81)
     return y
 
 
@@ -849,10 +843,8 @@ def conv9_to3_fwd(x, w, bias=None, in_slope=None, in_slope_const=0.0, in_act=ACT
         check(_abi.lib().sst_conv9_to3_pack(ptr(w), ptr(wp), C, stream_ptr()), "sst_conv9_to3_pack")
     y = _f32(B, 3, H, W, like=x)
     y_pre = torch.empty_like(y) if want_pre else None
-    e0 = _prof_begin()
     check(_abi.lib().sst_conv9_to3_fwd(ptr(x), ptr(wp), ptr(y), ptr(y_pre), ptr(bias), ptr(in_slope), float(in_slope_const),
                                        int(in_act), B, H, W, C, stream_ptr()), "sst_conv9_to3_fwd")
-    _prof_end(e0, "conv9_to3_fwd_kernel", 2.0 * B * H * W * C * 3 * 81)
     return y, y_pre
 
 
@@ -899,18 +891,16 @@ def conv_dgrad_bwdstats(dy, wd, cout, ksize, epi_y, residual=None, epi_scale=Non
     against epi_y ([mtiles,3,cout], the layout bwd_finalize consumes)."""
     B, H, W, cin = dy.shape
     g = _f32(B, H, W, cout, like=dy)
-    if residual is None and conv_pipe_tw(B, H, W, cin, cout, ksize, 1):
-        _, _, _, partial = _conv_pipe(dy, wd, g, cout, ksize, 1, epi=dict(y=epi_y, scale=epi_scale, shift=epi_shift, slope=epi_slope,
-                                                                         slope_const=epi_slope_const, act=epi_act), grp=grp)
-        return g, partial
+    route = _ConvRoute((B, H, W, cin, cout, ksize, 1), plain=residual is None)
+    epi, ekeep = _epi_args(epi_y, epi_scale, epi_shift, epi_slope, epi_slope_const, epi_act)
+    if route.kind != "general":
+        return g, _conv_tile(route, dy, wd, g, None, _in_args(), epi=(epi, ekeep), grp=grp)[2]
     if grp and grp < B and epi_scale is not None:
         raise _abi.HipPathError("conv_dgrad_bwdstats: coefficient groups need the pipelined kernel")
-    mt = _abi.lib().sst_conv_stat_tiles(B, H, W, cin, cout, ksize, 1)
-    partial = _f32(mt, 3, cout, like=dy)
-    args = (ptr(dy), ptr(wd), ptr(g), ptr(residual), ptr(epi_y), ptr(epi_scale), ptr(epi_shift), ptr(epi_slope),
-            float(epi_slope_const), int(epi_act), ptr(partial), B, H, W, cin, cout, ksize)
+    partial = _f32(route.rows(), 3, cout, like=dy)
+    args = (ptr(dy), ptr(wd), ptr(g), ptr(residual), *epi, ptr(partial), B, H, W, cin, cout, ksize)
     _launch(_abi.lib().sst_conv_dgrad_bwdstats, args, "sst_conv_dgrad_bwdstats", 2.0 * B * H * W * cout * cin * ksize * ksize,
-            lambda: _conv_name(B, H, W, cin, cout, ksize, 1), (dy, wd, g, residual, epi_y, epi_scale, epi_shift, epi_slope, partial))
+            route.name, (dy, wd, g, residual, *ekeep, partial))
     return g, partial
 
 
@@ -934,12 +924,13 @@ def conv_dgrad_fused(g, y2, wd, cout, ksize, cA=None, cB=None, cC=None, in_scale
     partial = None
     if epi_y is not None:
         partial = _f32(_abi.lib().sst_conv_stat_tiles(B, H, W, cin, cout, ksize, 1), 3, cout, like=g)
-    args = (ptr(g), ptr(y2), ptr(cA), ptr(cB), ptr(cC), ptr(in_scale), ptr(in_shift), ptr(in_slope), float(in_slope_const),
-            int(in_act), ptr(dy), ptr(wd), ptr(out), ptr(residual), ptr(epi_y), ptr(epi_scale), ptr(epi_shift), ptr(epi_slope),
-            float(epi_slope_const), int(epi_act), ptr(partial), B, H, W, cin, cout, ksize)
+    inp, ikeep = _in_args(in_scale, in_shift, in_slope, in_slope_const, in_act)
+    epi, ekeep = _epi_args(epi_y, epi_scale, epi_shift, epi_slope, epi_slope_const, epi_act)
+    args = (ptr(g), ptr(y2), ptr(cA), ptr(cB), ptr(cC), *inp, ptr(dy), ptr(wd), ptr(out), ptr(residual), *epi, ptr(partial),
+            B, H, W, cin, cout, ksize)
     _launch(_abi.lib().sst_conv_dgrad_fused, args, "sst_conv_dgrad_fused", 2.0 * B * H * W * cout * cin * ksize * ksize,
             lambda: _conv_name(B, H, W, cin, cout, ksize, 1, 0, 1),
-            (g, y2, cA, cB, cC, in_scale, in_shift, in_slope, dy, wd, out, residual, epi_y, epi_scale, epi_shift, epi_slope, partial))
+            (g, y2, cA, cB, cC, *ikeep, dy, wd, out, residual, *ekeep, partial))
     return out, dy, partial
 
 
@@ -1002,8 +993,7 @@ def adam_flat(p, g, m, v, lr_dev, steps, beta1, beta2, eps, weight_decay):
     assert p.numel() == g.numel() == m.numel() == v.numel() and p.numel() % 4 == 0
     args = (ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), ptr(lr_dev), ptr(steps), steps.numel(), float(beta1), float(beta2), float(eps),
             float(weight_decay))
-    check(_abi.lib().sst_adam_flat(*args, stream_ptr()), "sst_adam_flat")
-    _trace_hbm("adam_flat_kernel", 28.0 * p.numel(), lambda: _abi.lib().sst_adam_flat(*args, stream_ptr()), p, g, m, v, lr_dev, steps)
+    _launch_hbm(_abi.lib().sst_adam_flat, args, "sst_adam_flat", "adam_flat_kernel", 28.0 * p.numel(), (p, g, m, v, lr_dev, steps))
 
 
 def adam_flat_ema(p, g, m, v, ema, lr_dev, steps, beta1, beta2, eps, weight_decay, ema_decay, ema_warmup):
@@ -1011,9 +1001,8 @@ def adam_flat_ema(p, g, m, v, ema, lr_dev, steps, beta1, beta2, eps, weight_deca
     assert p.numel() == g.numel() == m.numel() == v.numel() == ema.numel() and p.numel() % 4 == 0
     args = (ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), ptr(lr_dev), ptr(steps), steps.numel(), float(beta1), float(beta2),
             float(eps), float(weight_decay), float(ema_decay), int(bool(ema_warmup)))
-    check(_abi.lib().sst_adam_flat_ema(*args, stream_ptr()), "sst_adam_flat_ema")
-    _trace_hbm("adam_flat_ema_kernel", 36.0 * p.numel(), lambda: _abi.lib().sst_adam_flat_ema(*args, stream_ptr()),
-               p, g, m, v, ema, lr_dev, steps)
+    _launch_hbm(_abi.lib().sst_adam_flat_ema, args, "sst_adam_flat_ema", "adam_flat_ema_kernel", 36.0 * p.numel(),
+                (p, g, m, v, ema, lr_dev, steps))
 
 
 def ema_flat(ema, p, steps, ema_decay, ema_warmup):

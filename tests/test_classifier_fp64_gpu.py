@@ -564,8 +564,8 @@ def test_rejected_arguments(ops):
         lambda: L.sst_head_fwd(ptr(a), ptr(w), None, ptr(y), 4, 0, 32, 0.2, stream_ptr()),
         lambda: L.sst_head_bwd(ptr(a), ptr(w), ptr(y), None, None, None, 4, 16, 32, 0.2, 0, stream_ptr()),
         lambda: L.sst_head_bwd(ptr(a), ptr(w), ptr(y), ptr(a), None, None, 0, 16, 32, 0.2, 0, stream_ptr()),
-        lambda: L.sst_flatten_act(ptr(a), None, None, 0.2, 1, None, 4, 4, 8, stream_ptr()),
-        lambda: L.sst_flatten_act(ptr(a), None, None, 0.2, 1, ptr(a), 4, 0, 8, stream_ptr()),
+        lambda: L.sst_flatten_act_grp(ptr(a), None, None, 0.2, 1, None, 4, 4, 8, 0, stream_ptr()),
+        lambda: L.sst_flatten_act_grp(ptr(a), None, None, 0.2, 1, ptr(a), 4, 0, 8, 0, stream_ptr()),
     ]
     for i, call in enumerate(bad):
         assert call() != 0, f"bad call {i} was accepted"
