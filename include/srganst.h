@@ -451,6 +451,27 @@ int sst_adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, 
 /* The average's update alone (no tick, no Adam) with t = steps[0] as it stands: for steps whose Adam update ran elsewhere. */
 int sst_ema_flat(float* ema, const float* p, int64_t n, const float* steps, double ema_decay, int ema_warmup, void* stream);
 
+/* ---- global gradient-norm clipping and the non-finite step guard on the same flat buffers.
+ * sst_grad_sumsq: fp64 sum of squares of the PARAMETER elements of a flat gradient buffer g (n floats, 16-byte aligned).  The
+ * pad words between parameter slots are never read: the kernel is driven by a job table of njobs (start, count) int64 pairs,
+ * one workgroup per job, partials[j] = sum of g[start .. start + count)^2 with every value widened to double before it is
+ * squared.  jobs is the table in device memory, jobs_host the same table in host memory; the host copy is checked (count > 0,
+ * 0 <= start, start + count <= n) before anything is launched.  Fixed order, no atomics: bit-reproducible. */
+int sst_grad_sumsq(const float* g, int64_t n, const int64_t* jobs, const int64_t* jobs_host, int njobs, double* partials,
+                   void* stream);
+
+/* sst_adam_flat (ema == NULL) or sst_adam_flat_ema with the clip rule, two launches.  The first sums partials[0 .. npartials)
+ * (sst_grad_sumsq's output for g) in a fixed order and writes the record rec[6] (doubles): norm = sqrt(sum); coef =
+ * (float)min(1, max_norm / (norm + 1e-6)) evaluated in double (max_norm == 0: no clipping, coef = 1; a NaN norm gives a NaN
+ * coef, as torch.nn.utils.clip_grad_norm_ does); skipped_now = skip_nonfinite && the sum is not finite; and the cumulative
+ * n_skipped, n_clipped, n_steps_seen (rec is zeroed once by the caller).  The step counters tick only when not skipping.  The
+ * second is the update: on skip p / m / v / ema are not touched, otherwise each gradient element is g * coef (one fp32
+ * multiply) and the rest is sst_adam_flat's arithmetic - with coef == 1 its bits. */
+int sst_adam_flat_clip(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* lr, float* steps,
+                       int nsteps, double beta1, double beta2, double eps, double weight_decay, double ema_decay,
+                       int ema_warmup, const double* partials, int npartials, double max_norm, int skip_nonfinite,
+                       double* rec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

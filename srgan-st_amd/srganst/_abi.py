@@ -39,6 +39,9 @@ SIGNATURES = {
     "sst_adam_flat_ema": (c_int, [P, P, P, P, P, c_int64, P, P, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                 ctypes.c_double, ctypes.c_double, c_int, P]),
     "sst_ema_flat": (c_int, [P, P, c_int64, P, ctypes.c_double, c_int, P]),
+    "sst_grad_sumsq": (c_int, [P, c_int64, P, P, c_int, P, P]),
+    "sst_adam_flat_clip": (c_int, [P, P, P, P, P, c_int64, P, P, c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                 ctypes.c_double, ctypes.c_double, c_int, P, c_int, ctypes.c_double, c_int, P, P]),
     "sst_debug_band_launches": (ctypes.c_long, []),
     "sst_debug_wgrad_band_launches": (ctypes.c_long, []),
     "sst_debug_mfma_peak": (c_int, [P, c_int, c_int, P]),

@@ -3,7 +3,9 @@
 ``g_last.pth`` / ``d_last.pth`` hold weights only.  ``state_last.pth`` (written by the drivers after every epoch unless
 ``EXP.SAVE_STATE`` is off) adds what a continued run needs to be the SAME run: both optimizers' state (Adam moments and step
 counters, i.e. the bias correction), both LR schedulers, the averaged generator (``SOLVER.G_EMA_DECAY``), the best validation
-values, warmup's batch counter and the CPU / device RNG streams - plus a fingerprint of the settings that must agree.
+values, warmup's batch counter and the CPU / device RNG streams - plus a fingerprint of the settings that must agree.  With
+gradient clipping or the non-finite guard on (``SOLVER.G_GRAD_CLIP`` / ``D_GRAD_CLIP`` / ``SKIP_NONFINITE``) a ``"clip"`` entry
+carries their cumulative counters per network; a file without it resumes with the counters at zero.
 
 The file is one ``torch.save`` of tensors and plain Python values (loads with ``weights_only=True`` like every checkpoint of the
 project), written to a temporary name in the target's directory and moved into place with ``os.replace``: a run killed mid-write
@@ -109,8 +111,9 @@ def atomic_save(obj, path):
 
 
 def save_training_state(path, *, epoch, generator, g_opt, g_sched, discriminator=None, d_opt=None, d_sched=None, g_ema=None,
-                        best=(0.0, 0.0), batches_done=0, config, world_size=None):
-    """epoch: the NEXT epoch to run.  g_ema: the averaged generator (a module) or None."""
+                        best=(0.0, 0.0), batches_done=0, config, world_size=None, clip=None):
+    """epoch: the NEXT epoch to run.  g_ema: the averaged generator (a module) or None.  clip: engine.clip_state() - the counters
+    of gradient clipping / the non-finite guard per network, {"G": {...}, "D": {...}} - or None (feature off: no entry)."""
     device = next(generator.parameters()).device
     state = {
         "format_version": FORMAT_VERSION,
@@ -128,6 +131,8 @@ def save_training_state(path, *, epoch, generator, g_opt, g_sched, discriminator
         "rng": rng_state(device),
         "fingerprint": fingerprint(config, world_size),
     }
+    if clip:
+        state["clip"] = {str(net): {str(k): int(v) for k, v in c.items()} for net, c in clip.items() if c is not None}
     atomic_save(state, path)
 
 

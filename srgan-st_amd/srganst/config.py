@@ -136,6 +136,16 @@ class Config:
         self.SOLVER.G_EMA_DECAY = 0.0
         self.SOLVER.G_EMA_WARMUP = True
         self.SOLVER.G_EMA_VALIDATE = True
+        # Global gradient-norm clipping and the non-finite step guard, decided on the device inside the flat Adam step
+        # (optim.FlatAdam: one fp64 reduction of the flat gradient, then the update on g * min(1, max_norm / (norm + 1e-6))), so they
+        # ride in the captured graph without a host sync.  GRAD_CLIP: the maximal global L2 norm per network, 0 = off.
+        # SKIP_NONFINITE: an update whose gradient holds a NaN or an infinity is dropped for that network - weights, Adam moments,
+        # step counters and the average stay as they were (BatchNorm running statistics do not: the forward pass has moved them
+        # already).  All off (default): the step launches what it launches without the options.  Under data parallelism the norm is
+        # the averaged gradient's, so every rank decides alike
+        self.SOLVER.G_GRAD_CLIP = 0.0
+        self.SOLVER.D_GRAD_CLIP = 0.0
+        self.SOLVER.SKIP_NONFINITE = False
 
         self.SCHEDULER = dotdict()
         self.SCHEDULER.STEP_SIZE = self.EXP.N_EPOCHS // 2

@@ -26,18 +26,39 @@ from . import ops as _ops
 from ._state import state
 
 
-def make_adam(module, lr, betas, eps, weight_decay, capturable, ema_decay=0.0, ema_warmup=True, ema_buffer=None):
+def make_adam(module, lr, betas, eps, weight_decay, capturable, ema_decay=0.0, ema_warmup=True, ema_buffer=None,
+              max_grad_norm=0.0, skip_nonfinite=False):
     # torch.optim.Adam semantics and state layout (the reference uses it as-is, train.py:62-75) on flat buffers: one
     # HIP kernel per step, graph-capturable, lr as a device tensor so that LR schedulers keep working under capture.
     # ema_decay > 0: the same kernel keeps a moving average of the parameters in ema_buffer (optim.FlatAdam).
+    # max_grad_norm > 0 / skip_nonfinite: global gradient-norm clipping and the non-finite guard, decided on the device.
     from .optim import FlatAdam
     return FlatAdam(module, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable,
-                    ema_decay=ema_decay, ema_warmup=ema_warmup, ema_buffer=ema_buffer)
+                    ema_decay=ema_decay, ema_warmup=ema_warmup, ema_buffer=ema_buffer, max_grad_norm=max_grad_norm,
+                    skip_nonfinite=skip_nonfinite)
 
 
 def _ema_knobs(config):
     s = config.SOLVER
     return float(s.get("G_EMA_DECAY", 0.0)), bool(s.get("G_EMA_WARMUP", True))
+
+
+def _clip_knobs(config, net):
+    """(max_grad_norm, skip_nonfinite) of SOLVER.{G,D}_GRAD_CLIP / SOLVER.SKIP_NONFINITE for network "G" or "D"."""
+    s = config.SOLVER
+    return float(s.get(net + "_GRAD_CLIP", 0.0)), bool(s.get("SKIP_NONFINITE", False))
+
+
+def _clip_state(opts):
+    """{"G": counters, "D": counters} of the optimizers that clip or guard, or None when none does (checkpoint.py: "clip")."""
+    out = {k: o.clip_counters() for k, o in opts.items() if o is not None and o.clip_on}
+    return out or None
+
+
+def _load_clip_state(opts, clip):
+    for k, o in opts.items():
+        if o is not None and clip:
+            o.load_clip_counters(clip.get(k))
 
 
 def make_shadow(config, generator):
@@ -222,10 +243,12 @@ class WarmupEngine:
         # SOLVER.G_EMA_DECAY > 0: g_ema is the averaged generator (eval mode), its weights written by the optimizer's kernel
         ema_decay, ema_warmup = _ema_knobs(config)
         self.g_ema, ema_buf = make_shadow(config, self.G) if ema_decay > 0 else (None, None)
+        g_clip, guard = _clip_knobs(config, "G")
         self.opt = make_adam(self.G, config.SOLVER.G_BASE_LR, (config.SOLVER.G_BETA1, config.SOLVER.G_BETA2),
                              config.SOLVER.G_EPS, config.SOLVER.G_WEIGHT_DECAY,
                              capturable=use_graph if adam_capturable is None else adam_capturable,
-                             ema_decay=ema_decay, ema_warmup=ema_warmup, ema_buffer=ema_buf)
+                             ema_decay=ema_decay, ema_warmup=ema_warmup, ema_buffer=ema_buf, max_grad_norm=g_clip,
+                             skip_nonfinite=guard)
         self.gt = self.lr = None
         self.loss_values = OrderedDict()
         self.sr = None
@@ -246,6 +269,16 @@ class WarmupEngine:
     def sync_ema_buffers(self):
         """Copy G's BatchNorm buffers into g_ema; call before the shadow is validated or saved."""
         sync_shadow_buffers(self.G, self.g_ema)
+
+    def grad_stats(self):
+        """{"G": the optimizer's gradient record as Python numbers or None (feature off), "D": None}; one host copy."""
+        return {"G": self.opt.grad_stats(), "D": None}
+
+    def clip_state(self):
+        return _clip_state({"G": self.opt})
+
+    def load_clip_state(self, clip):
+        _load_clip_state({"G": self.opt}, clip)
 
     def _steps(self):
         return [s for s in (self._fb, self._op) if s is not None]
@@ -321,9 +354,12 @@ class TrainEngine:
         # update rides in whichever graph holds g_opt.step.  D has no average.
         ema_decay, ema_warmup = _ema_knobs(config)
         self.g_ema, ema_buf = make_shadow(config, self.G) if ema_decay > 0 else (None, None)
+        (g_clip, guard), (d_clip, _) = _clip_knobs(config, "G"), _clip_knobs(config, "D")
         self.g_opt = make_adam(self.G, s.G_BASE_LR, (s.G_BETA1, s.G_BETA2), s.G_EPS, s.G_WEIGHT_DECAY, cap,
-                               ema_decay=ema_decay, ema_warmup=ema_warmup, ema_buffer=ema_buf)
-        self.d_opt = make_adam(self.D, s.D_BASE_LR, (s.D_BETA1, s.D_BETA2), s.D_EPS, s.D_WEIGHT_DECAY, cap)
+                               ema_decay=ema_decay, ema_warmup=ema_warmup, ema_buffer=ema_buf, max_grad_norm=g_clip,
+                               skip_nonfinite=guard)
+        self.d_opt = make_adam(self.D, s.D_BASE_LR, (s.D_BETA1, s.D_BETA2), s.D_EPS, s.D_WEIGHT_DECAY, cap,
+                               max_grad_norm=d_clip, skip_nonfinite=guard)
         self.adv = BCEWithLogitsLoss()                      # train.py:59
         self.real = 1.0 - config.EXP.LABEL_SMOOTHING        # train.py:113
         self.fake = 0.0                                     # train.py:114
@@ -378,6 +414,16 @@ class TrainEngine:
     def sync_ema_buffers(self):
         """Copy G's BatchNorm buffers into g_ema; call before the shadow is validated or saved."""
         sync_shadow_buffers(self.G, self.g_ema)
+
+    def grad_stats(self):
+        """{"G": ..., "D": ...}: each optimizer's gradient record as Python numbers, None where the feature is off; host copies."""
+        return {"G": self.g_opt.grad_stats(), "D": self.d_opt.grad_stats()}
+
+    def clip_state(self):
+        return _clip_state({"G": self.g_opt, "D": self.d_opt})
+
+    def load_clip_state(self, clip):
+        _load_clip_state({"G": self.g_opt, "D": self.d_opt}, clip)
 
     def _steps(self):
         if self._it is not None:               # merged iterations; generator-only graph between them when D is updated every n-th step

@@ -1012,6 +1012,41 @@ def ema_flat(ema, p, steps, ema_decay, ema_warmup):
           "sst_ema_flat")
 
 
+class NormJobs:
+    """The job table of grad_sumsq: (start, count) int64 pairs, once in host memory (the library checks it before every launch) and
+    once on the device (the kernel reads it).  Built once, before any graph capture."""
+
+    def __init__(self, jobs, device):
+        if not jobs:
+            raise _abi.HipPathError("NormJobs: the job table is empty")
+        self.host = torch.tensor(jobs, dtype=torch.int64).reshape(-1, 2).contiguous()
+        self.dev = self.host.to(device)
+        self.njobs = self.host.shape[0]
+
+
+def grad_sumsq(g, jobs, partials):
+    """partials[j] <- fp64 sum of squares of job j's elements of the flat gradient buffer g (csrc/optim.hip): one read of the
+    parameter elements, pad words never touched, fixed order."""
+    assert partials.dtype == torch.float64 and partials.numel() >= jobs.njobs and g.numel() % 4 == 0
+    args = (ptr(g), g.numel(), ptr(jobs.dev), jobs.host.data_ptr(), jobs.njobs, ptr(partials))
+    _launch_hbm(_abi.lib().sst_grad_sumsq, args, "sst_grad_sumsq", "grad_sumsq_kernel", 4.0 * g.numel(), (g, jobs, partials))
+
+
+def adam_flat_clip(p, g, m, v, ema, lr_dev, steps, beta1, beta2, eps, weight_decay, ema_decay, ema_warmup, partials, npartials,
+                   max_norm, skip_nonfinite, record):
+    """adam_flat (ema None) / adam_flat_ema on g * coef, coef and the skip decision taken on the device from grad_sumsq's partials
+    and left in `record` (6 doubles: norm, coef, skipped_now, n_skipped, n_clipped, n_steps_seen).  The update moves the bytes it
+    always moved; the norm pass before it is 4 B per element."""
+    assert p.numel() == g.numel() == m.numel() == v.numel() and p.numel() % 4 == 0 and (ema is None or ema.numel() == p.numel())
+    assert partials.dtype == record.dtype == torch.float64 and record.numel() == 6 and 0 < npartials <= partials.numel()
+    args = (ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), ptr(lr_dev), ptr(steps), steps.numel(), float(beta1), float(beta2),
+            float(eps), float(weight_decay), float(ema_decay), int(bool(ema_warmup)), ptr(partials), int(npartials), float(max_norm),
+            int(bool(skip_nonfinite)), ptr(record))
+    name, nbytes = ("adam_flat_clip_kernel", 28.0) if ema is None else ("adam_flat_ema_clip_kernel", 36.0)
+    _launch_hbm(_abi.lib().sst_adam_flat_clip, args, "sst_adam_flat_clip", name, nbytes * p.numel(),
+                (p, g, m, v, ema, lr_dev, steps, partials, record))
+
+
 class WgradGroup:
     """Collects weight-gradient jobs of identical shape and issues them as ONE launch (+ one grouped slab reduce).
     The slab is cached per (shape, count); the job table (device pointers of every layer) is a kernel argument."""

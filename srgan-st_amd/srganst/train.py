@@ -23,7 +23,7 @@ from .engine import TrainEngine
 from .model import Discriminator, Generator
 from .utils import init_random_seed, load_state_dict, start_workers
 from .validate import _validate
-from .warmup import _NullWriter, _writer
+from .warmup import _NullWriter, _writer, log_grad_stats
 
 
 def train(config: Config, train_dataset=None, test_dataset=None, max_steps_per_epoch=None):
@@ -74,6 +74,7 @@ def train(config: Config, train_dataset=None, test_dataset=None, max_steps_per_e
         checkpoint.load_scheduler_state(d_scheduler, resume["d_sched"])
         if engine.g_ema is not None:
             engine.g_ema.load_state_dict(resume["g_ema"])
+        engine.load_clip_state(resume.get("clip"))       # absent (written with the feature off): the counters start at zero
     ema_validate = engine.g_ema is not None and bool(config.SOLVER.get("G_EMA_VALIDATE", True))
     writer = _writer(config.EXP.NAME) if rank == 0 else _NullWriter()
     writer.add_text("Config/Params", config.get_all_params())
@@ -116,8 +117,9 @@ def train(config: Config, train_dataset=None, test_dataset=None, max_steps_per_e
                 writer.add_scalar(f"Train/G_{name}", v, batches_done)
             writer.add_scalar("Train/D(GT)_Probability", torch.sigmoid(torch.mean(engine.pred_gt)).item(), batches_done)
             writer.add_scalar("Train/D(SR)_Probability", torch.sigmoid(torch.mean(engine.pred_sr)).item(), batches_done)
+            skipped = log_grad_stats(writer, engine.grad_stats(), batches_done)
             print(f"[Epoch {epoch+1}/{config.EXP.N_EPOCHS}] [Batch {batch_num}/{len(train_loader)}] "
-                  f"[D loss: {float(d_loss)}] [G loss: {sum(vals.values())}] [G losses: {vals}]")
+                  f"[D loss: {float(d_loss)}] [G loss: {sum(vals.values())}] [G losses: {vals}]{skipped}")
         g_scheduler.step()
         d_scheduler.step()
         generator.eval()
@@ -153,7 +155,8 @@ def train(config: Config, train_dataset=None, test_dataset=None, max_steps_per_e
                 checkpoint.save_training_state(results_dir + "/" + checkpoint.STATE_FILE, epoch=epoch + 1, generator=generator,
                                                g_opt=engine.g_opt, g_sched=g_scheduler, discriminator=discriminator,
                                                d_opt=engine.d_opt, d_sched=d_scheduler, g_ema=engine.g_ema,
-                                               best=(best_psnr, best_ssim), config=config, world_size=world)
+                                               best=(best_psnr, best_ssim), config=config, world_size=world,
+                                               clip=engine.clip_state())
     engine.close()
     return generator, discriminator
 

@@ -34,6 +34,20 @@ def _writer(name):
         return _NullWriter()
 
 
+def log_grad_stats(writer, stats, batches_done):
+    """Train/{G,D}_GradNorm, _ClipCoef, _Skipped for the networks whose optimizer clips or guards (engine.grad_stats()); returns
+    the skipped counts as a piece of the printed line ("" with the feature off)."""
+    line = ""
+    for net, st in stats.items():
+        if st is None:
+            continue
+        writer.add_scalar(f"Train/{net}_GradNorm", st["norm"], batches_done)
+        writer.add_scalar(f"Train/{net}_ClipCoef", st["coef"], batches_done)
+        writer.add_scalar(f"Train/{net}_Skipped", st["n_skipped"], batches_done)
+        line += f" [{net} skipped: {st['n_skipped']}/{st['n_steps_seen']}]"
+    return line
+
+
 def warmup(config: Config, train_dataset=None, test_dataset=None, max_steps_per_epoch=None):
     rank, local, world = sdist.init_from_env(config.DIST.BACKEND)
     init_random_seed(config.DATA.SEED)
@@ -52,6 +66,7 @@ def warmup(config: Config, train_dataset=None, test_dataset=None, max_steps_per_
         engine.opt.load_state_dict(resume["g_opt"])
         if engine.g_ema is not None:
             engine.g_ema.load_state_dict(resume["g_ema"])
+        engine.load_clip_state(resume.get("clip"))       # absent (written with the feature off): the counters start at zero
     ema_validate = engine.g_ema is not None and bool(config.SOLVER.get("G_EMA_VALIDATE", True))
     train_ds = train_dataset or TrainImageDataset(config.DATA.TRAIN_GT_IMAGES_DIR, config.DATA.UPSCALE_FACTOR)
     test_ds = test_dataset or TestImageDataset(config.DATA.TEST_GT_IMAGES_DIR, config.DATA.TEST_LR_IMAGES_DIR)
@@ -101,7 +116,8 @@ def warmup(config: Config, train_dataset=None, test_dataset=None, max_steps_per_
             writer.add_scalar("Train/G_Loss", sum(vals.values()), batches_done)
             for name, v in vals.items():
                 writer.add_scalar(f"Train/G_{name}", v, batches_done)
-            print(f"[Epoch {epoch+1}/{config.EXP.N_EPOCHS}] [Batch {batch_num}/{len(train_loader)}] [G losses: {vals}]")
+            skipped = log_grad_stats(writer, engine.grad_stats(), batches_done)
+            print(f"[Epoch {epoch+1}/{config.EXP.N_EPOCHS}] [Batch {batch_num}/{len(train_loader)}] [G losses: {vals}]{skipped}")
         generator.eval()
         if rank == 0:
             engine.sync_ema_buffers()             # the averaged generator takes G's BatchNorm buffers before it is run or saved
@@ -130,7 +146,8 @@ def warmup(config: Config, train_dataset=None, test_dataset=None, max_steps_per_
             if config.EXP.get("SAVE_STATE", True):       # last in the epoch: the RNG streams go in as the next epoch will find them
                 checkpoint.save_training_state(results_dir + "/" + checkpoint.STATE_FILE, epoch=epoch + 1, generator=generator,
                                                g_opt=engine.opt, g_sched=None, g_ema=engine.g_ema, best=(best_psnr, best_ssim),
-                                               batches_done=batches_done, config=config, world_size=world)
+                                               batches_done=batches_done, config=config, world_size=world,
+                                               clip=engine.clip_state())
     engine.close()
     return generator
 
