@@ -58,6 +58,23 @@ int sst_st_pixel_loss_fwd(const float* sr, const float* gt, float* loss, float* 
 int sst_st_pixel_loss_bwd(const float* sr, const float* gt, const float* gS, float* dsr, const float* scale_dev, float scale_host,
                           float pix_weight, int pix_mode, int accumulate, int B, int H, int W, float sigma, float rho,
                           void* stream);
+/* ---- structure-tensor loss and maps at any (sigma, rho) with radii R1 <= 8, R2 <= 20 (csrc/st_general.hip):
+ * separable 1-D passes over whole planes in a caller-provided workspace, radii as runtime values.  The entries above keep their
+ * two tile builds and their refusals; these run every pair within the bound (the two built pairs included).
+ * sst_st_route (host only): *r1, *r2 = the radii; returns 0 when (sigma, rho) selects a tile build, 1 for the general path, and
+ *   SST_ERR_UNSUPPORTED "... (sigma,rho)=(..) -> radii (..) not built" when R1 > 8 or R2 > 20.
+ * sst_st_general_workspace: floats, with N = B*H*W: scratch 14 N (one buffer for forward, backward and maps), saved 2 N (Ix, Iy of
+ *   sr: the forward writes them, the backward reads them), partials B * ceil(H/32) * ceil(W/32).
+ * fwd: loss[0], gS as sst_st_loss_fwd; counter must be 0 at the first call and re-arms itself.   bwd: as sst_st_loss_bwd, from
+ *   `saved` in place of sr.   maps: sst_st_maps's outputs and layouts.  Everything is validated on the host before any launch.   */
+int sst_st_route(float sigma, float rho, int* r1, int* r2);
+int sst_st_general_workspace(int B, int H, int W, int64_t* scratch_floats, int64_t* saved_floats, int64_t* partial_floats);
+int sst_st_general_fwd(const float* sr, const float* gt, float* loss, float* gS, float* saved, float* scratch, float* partials,
+                       unsigned* counter, int B, int H, int W, float sigma, float rho, int normalize, void* stream);
+int sst_st_general_bwd(const float* saved, const float* gS, float* dsr, float* scratch, const float* scale_dev, float scale_host,
+                       int accumulate, int B, int H, int W, float sigma, float rho, void* stream);
+int sst_st_general_maps(const float* x, const float* gt, float* Sx, float* Sgt, float* Fx, float* Fgt, float* d, float* tile_sums,
+                        float* scratch, int B, int H, int W, float sigma, float rho, int normalize, void* stream);
 
 /* ---- convolution (fp32 MFMA implicit GEMM, NHWC) --------------------------------------------------
  * Replaces the cuDNN/oneDNN kernels behind nn.Conv2d fwd/bwd of model.py:32-56,101,113,127,159,173,176.

@@ -28,6 +28,11 @@ SIGNATURES = {
     "sst_st_pixel_loss_bwd": (c_int, [P, P, P, P, P, c_float, c_float, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P]),
     "sst_st_maps_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
     "sst_st_maps": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_int, P]),
+    "sst_st_route": (c_int, [c_float, c_float, POINTER(c_int), POINTER(c_int)]),
+    "sst_st_general_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "sst_st_general_fwd": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_int, P]),
+    "sst_st_general_bwd": (c_int, [P, P, P, P, P, c_float, c_int, c_int, c_int, c_int, c_float, c_float, P]),
+    "sst_st_general_maps": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_int, P]),
     "sst_conv_packed_floats": (c_int64, [c_int, c_int, c_int]),
     "sst_conv_pack": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "sst_conv_pack_multi": (c_int, [P, c_int, c_int, P]),

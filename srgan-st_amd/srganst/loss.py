@@ -1,6 +1,7 @@
 """Generator criterions on the HIP path.  Mirrors reference loss.py (criterion(sr, gt) -> 0-dim).
 
-StructureTensorLoss  <- reference loss.py:380-413 (+ utils.py:194-280), kernels csrc/st_loss.hip
+StructureTensorLoss  <- reference loss.py:380-413 (+ utils.py:194-280), kernels csrc/st_loss.hip (radii (2,8), (4,10)) and
+                        csrc/st_general.hip (every other (sigma, rho) up to radii 8 / 20)
 ContentLossVGG       <- reference loss.py:11-70, in vgg_loss.py (re-exported here)
 BestBuddyLoss / GramLoss / PatchwiseStructureTensorLoss <- reference loss.py:78-228, 292-375, kernels csrc/bb_loss.hip
 ContentLossDiscriminator <- reference loss.py:231-289, in disc_loss.py (re-exported here)
@@ -62,8 +63,92 @@ class _StLossFn(torch.autograd.Function):
         return dx, None, None, None, None, None
 
 
+# Dev switch (tests and timing only): send the two built radius pairs down the general path of csrc/st_general.hip as well.
+ST_FORCE_GENERAL = os.environ.get("SST_ST_GENERAL", "0") not in ("", "0")
+
+
+def st_route(sigma, rho, what="StructureTensorLoss"):
+    """Which kernels run this (sigma, rho): -> (general, (R1, R2)).  general is False for the two 32 x 32-tile builds (csrc/st_loss.hip,
+    csrc/st_maps.hip) and True for the separable path (csrc/st_general.hip, radii up to 8 / 20); beyond that bound HipPathError with
+    the library's "... radii (R1,R2) not built".  Host only."""
+    r1, r2 = ctypes.c_int(), ctypes.c_int()
+    rc = _abi.lib().sst_st_route(float(sigma), float(rho), ctypes.byref(r1), ctypes.byref(r2))
+    if rc < 0:
+        _abi.check(rc, what)
+    return bool(rc) or ST_FORCE_GENERAL, (r1.value, r2.value)
+
+
+def _st_general_workspace(x, gt, radii, ws):
+    """The general path's counterpart of _st_workspace: scratch planes, partials and counter in the criterion's cache `ws`, keyed by
+    device, shape and radii (a warm-up call allocates them before a graph capture) -> floats of the per-call saved planes."""
+    if x.dtype != torch.float32 or gt.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.shape != gt.shape:
+        raise _abi.HipPathError(f"StructureTensorLoss: expected fp32 [B,3,H,W] pairs, got {tuple(x.shape)} / {tuple(gt.shape)}")
+    B, _, H, W = x.shape
+    scratch, saved, partials = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    _abi.check(_abi.lib().sst_st_general_workspace(B, H, W, ctypes.byref(scratch), ctypes.byref(saved), ctypes.byref(partials)),
+               "sst_st_general_workspace")
+    key = (x.device, B, H, W, radii)
+    if ws.get("general_key") != key:
+        ws["general_key"] = key
+        ws["general_scratch"] = torch.empty(scratch.value, device=x.device, dtype=torch.float32)
+        ws["general_partials"] = torch.empty(partials.value, device=x.device, dtype=torch.float32)
+        ws["general_counter"] = torch.zeros(1, device=x.device, dtype=torch.int32)
+    return saved.value
+
+
+def _st_general_fwd(x, gt, sigma, rho, normalize, ws, radii):
+    """The general path's forward -> (loss, gS, saved planes, scratch).  gS and the saved planes (Ix, Iy of sr) belong to the call,
+    like gS on the tile path; the scratch planes are the criterion's and only live inside one entry point."""
+    from . import ops
+    n_saved = _st_general_workspace(x, gt, radii, ws)
+    x = x.contiguous()
+    gt = gt.contiguous()
+    B, _, H, W = x.shape
+    gS = torch.empty_like(x)
+    saved = torch.empty(n_saved, device=x.device, dtype=torch.float32)
+    loss = torch.empty((), device=x.device, dtype=torch.float32)
+    scratch = ws["general_scratch"]
+    args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(gS), _abi.ptr(saved), _abi.ptr(scratch), _abi.ptr(ws["general_partials"]),
+            _abi.ptr(ws["general_counter"]), B, H, W, sigma, rho, int(normalize))
+    # algorithmic bytes as on the tile path: the forward reads sr + gt (the planes in between are this path's own traffic)
+    ops._launch_hbm(_abi.lib().sst_st_general_fwd, args, "sst_st_general_fwd", "stg_loss_fwd_kernel", 2.0 * x.numel() * 4,
+                    (x, gt, loss, gS, saved, ws))
+    return loss, gS, saved, scratch
+
+
+def _st_general_bwd(gS, saved, scratch, dsr, g, scale_host, accumulate, sigma, rho):
+    """dsr (+)= scale_host * g[0] * d loss / d sr on the general path."""
+    from . import ops
+    B, _, H, W = gS.shape
+    bargs = (_abi.ptr(saved), _abi.ptr(gS), _abi.ptr(dsr), _abi.ptr(scratch), _abi.ptr(g), float(scale_host), int(accumulate), B, H, W,
+             sigma, rho)
+    ops._launch_hbm(_abi.lib().sst_st_general_bwd, bargs, "sst_st_general_bwd", "stg_hadj_out_kernel", 1.0 * gS.numel() * 4,
+                    (saved, gS, dsr, scratch, g))
+
+
+class _StGeneralFn(torch.autograd.Function):
+    """_StLossFn on the general path."""
+
+    @staticmethod
+    def forward(ctx, x, gt, sigma, rho, normalize, ws, radii):
+        loss, gS, saved, scratch = _st_general_fwd(x, gt, sigma, rho, normalize, ws, radii)
+        ctx.save_for_backward(gS, saved)
+        ctx.cfg = (sigma, rho, scratch)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        gS, saved = ctx.saved_tensors
+        sigma, rho, scratch = ctx.cfg
+        dx = torch.empty_like(gS)
+        _st_general_bwd(gS, saved, scratch, dx, grad_out.contiguous().to(torch.float32), 1.0, False, sigma, rho)
+        return dx, None, None, None, None, None, None
+
+
 class StructureTensorLoss(nn.Module):
-    """Same constructor and call protocol as reference loss.py:380-413."""
+    """Same constructor and call protocol as reference loss.py:380-413.  Any (sigma, rho) whose radii max(int(4 s + 0.5), 1) are at
+    most 8 (sigma) and 20 (rho), i.e. sigma up to about 2.1 and rho up to about 5.1: the pairs with radii (2, 8) and (4, 10) run the
+    32 x 32-tile kernels (csrc/st_loss.hip), every other pair the separable path (csrc/st_general.hip); beyond the bound HipPathError."""
 
     def __init__(self, sigma: float = 0.5, rho: float = 2.0, normalize: bool = True):
         super().__init__()
@@ -73,6 +158,9 @@ class StructureTensorLoss(nn.Module):
         self._ws = {}
 
     def forward(self, x, gt):
+        general, radii = st_route(self.sigma, self.rho)
+        if general:
+            return _StGeneralFn.apply(x, gt, float(self.sigma), float(self.rho), bool(self.normalize), self._ws, radii)
         return _StLossFn.apply(x, gt, float(self.sigma), float(self.rho), bool(self.normalize), self._ws)
 
     def __repr__(self):
@@ -159,7 +247,10 @@ class _CriterionSumFn(torch.autograd.Function):
         st_i = [i for i, t in enumerate(terms) if isinstance(t, StructureTensorLoss)]
         px_i = [i for i, t in enumerate(terms) if isinstance(t, (MSELoss, L1Loss))]
         ctx.fused_pair = None
-        if FUSE_PIXEL_INTO_ST and len(st_i) == 1 and len(px_i) == 1 and sr.dim() == 4 and sr.shape[1] == 3:
+        # (the fused kernels are the tile builds': a structure-tensor term on the general route runs unfused, below)
+        routes = [st_route(t.sigma, t.rho) if isinstance(t, StructureTensorLoss) else None for t in terms]
+        if (FUSE_PIXEL_INTO_ST and len(st_i) == 1 and len(px_i) == 1 and sr.dim() == 4 and sr.shape[1] == 3
+                and not routes[st_i[0]][0]):
             t = terms[st_i[0]]
             mode = 0 if isinstance(terms[px_i[0]], MSELoss) else 1
             st_loss, pix_loss, gS = _st_pixel_fwd(sr, gt, float(t.sigma), float(t.rho), bool(t.normalize), t._ws, mode)
@@ -171,7 +262,11 @@ class _CriterionSumFn(torch.autograd.Function):
                     raise _abi.HipPathError("criterion sum: unexpected term next to the fused pixel + structure-tensor pair")
         else:
             for i, t in enumerate(terms):
-                if isinstance(t, StructureTensorLoss):
+                if isinstance(t, StructureTensorLoss) and routes[i][0]:
+                    st_loss, *kept = _st_general_fwd(sr, gt, float(t.sigma), float(t.rho), bool(t.normalize), t._ws, routes[i][1])
+                    raw.append(st_loss)
+                    saved.append(tuple(kept))
+                elif isinstance(t, StructureTensorLoss):
                     raw.append(_StLossFn.forward(_Ctx(saved), sr, gt, float(t.sigma), float(t.rho), bool(t.normalize), t._ws))
                 else:
                     raw.append(ops.pixel_loss_fwd(sr, gt, 0 if isinstance(t, MSELoss) else 1, t._ws))
@@ -204,7 +299,9 @@ class _CriterionSumFn(torch.autograd.Function):
                             (sr, gt, ctx.gS[si], dsr, g))
             return dsr, None, None, None, None
         for i, (t, w) in enumerate(zip(ctx.terms, ctx.weights)):
-            if isinstance(t, StructureTensorLoss):
+            if isinstance(t, StructureTensorLoss) and isinstance(ctx.gS[i], tuple):       # general route: (gS, saved planes, scratch)
+                _st_general_bwd(*ctx.gS[i], dsr, g, w, i > 0, float(t.sigma), float(t.rho))
+            elif isinstance(t, StructureTensorLoss):
                 bargs = (_abi.ptr(sr), _abi.ptr(ctx.gS[i]), _abi.ptr(dsr), _abi.ptr(g), w, int(i > 0), B, H, W, float(t.sigma), float(t.rho))
                 ops._launch_hbm(_abi.lib().sst_st_loss_bwd, bargs, "sst_st_loss_bwd", "st_loss_bwd_kernel", 1.0 * sr.numel() * 4,
                                 (sr, ctx.gS[i], dsr, g))

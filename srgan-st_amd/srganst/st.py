@@ -36,6 +36,14 @@ def workspace_floats(B: int, H: int, W: int) -> int:
     return n.value
 
 
+def general_scratch_floats(B: int, H: int, W: int) -> int:
+    """Floats of the plane workspace of the general path (csrc/st_general.hip: sst_st_general_maps) = 14 B H W."""
+    scratch, saved, partials = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    _abi.check(_abi.lib().sst_st_general_workspace(B, H, W, ctypes.byref(scratch), ctypes.byref(saved), ctypes.byref(partials)),
+               "sst_st_general_workspace")
+    return scratch.value
+
+
 def _checked(name: str, t) -> Tensor:
     if not isinstance(t, Tensor) or not t.is_cuda:
         raise HipPathError(f"st_maps: {name} must be a tensor on a ROCm device (no CPU fallback)")
@@ -48,7 +56,8 @@ def _checked(name: str, t) -> Tensor:
 
 def st_maps(sr: Tensor, gt: Tensor | None = None, sigma: float = 0.5, rho: float = 2.0, normalize: bool = True,
             want=("Sx", "d")) -> dict:
-    """The general form: one launch of sst_st_maps -> dict of the outputs named in ``want``.
+    """The general form: sst_st_maps (one launch) or, off the two built radius pairs, sst_st_general_maps -> dict of the outputs
+    named in ``want``.
 
     sr, gt: fp32 [B,3,H,W] on one ROCm device (made contiguous if they are not); gt may be None when only maps of sr are wanted.
     want, any of:
@@ -57,8 +66,10 @@ def st_maps(sr: Tensor, gt: Tensor | None = None, sigma: float = 0.5, rho: float
       "d"           [B,H,W]    per-pixel distance between the structure tensors of sr and gt (StructureTensorLoss's integrand)
       "tile_sums"   [B,tiles]  fp32 sum of d over each 32 x 32 tile
       "distance"    [B] fp64   per-image mean of d: the tile sums added in fp64 in index order, over H * W
-    (sigma, rho) must select one of the built radius pairs, as for StructureTensorLoss.  Analysis op: inputs are detached, no
-    gradient.  Runs on the current stream, never syncs with the host, bit-identical from call to call."""
+    (sigma, rho): any pair whose radii max(int(4 s + 0.5), 1) are at most 8 (sigma) and 20 (rho), as for StructureTensorLoss and by
+    the same routes: radii (2, 8) and (4, 10) run the tile kernel, every other pair the separable passes of csrc/st_general.hip (in a
+    workspace of 14 B H W floats allocated per call); beyond the bound HipPathError.  Analysis op: inputs are detached, no gradient.
+    Runs on the current stream, never syncs with the host, bit-identical from call to call."""
     want = tuple(want)
     unknown = [w for w in want if w not in OUTPUTS]
     if unknown or not want:
@@ -74,6 +85,8 @@ def st_maps(sr: Tensor, gt: Tensor | None = None, sigma: float = 0.5, rho: float
         if missing:
             raise HipPathError(f"st_maps: {missing} need gt")
     B, _, H, W = sr.shape
+    from .loss import st_route
+    general, _ = st_route(sigma, rho, "st_maps")
     with torch.no_grad(), torch.cuda.device(sr.device):
         def new(*shape):
             return torch.empty(*shape, dtype=torch.float32, device=sr.device)
@@ -83,8 +96,13 @@ def st_maps(sr: Tensor, gt: Tensor | None = None, sigma: float = 0.5, rho: float
         if "tile_sums" in want or "distance" in want:
             bufs["tile_sums"] = new(B, workspace_floats(B, H, W) // B)
         p = {k: _abi.ptr(bufs.get(k)) for k in ("Sx", "Sgt", "Fx", "Fgt", "d", "tile_sums")}
-        _abi.check(_abi.lib().sst_st_maps(_abi.ptr(sr), _abi.ptr(gt), p["Sx"], p["Sgt"], p["Fx"], p["Fgt"], p["d"], p["tile_sums"],
-                                          B, H, W, float(sigma), float(rho), int(bool(normalize)), _abi.stream_ptr()), "sst_st_maps")
+        if general:
+            _abi.check(_abi.lib().sst_st_general_maps(_abi.ptr(sr), _abi.ptr(gt), p["Sx"], p["Sgt"], p["Fx"], p["Fgt"], p["d"],
+                                                      p["tile_sums"], _abi.ptr(new(general_scratch_floats(B, H, W))), B, H, W, float(sigma),
+                                                      float(rho), int(bool(normalize)), _abi.stream_ptr()), "sst_st_general_maps")
+        else:
+            _abi.check(_abi.lib().sst_st_maps(_abi.ptr(sr), _abi.ptr(gt), p["Sx"], p["Sgt"], p["Fx"], p["Fgt"], p["d"], p["tile_sums"],
+                                              B, H, W, float(sigma), float(rho), int(bool(normalize)), _abi.stream_ptr()), "sst_st_maps")
         if "distance" in want:
             bufs["distance"] = bufs["tile_sums"].sum(dim=1, dtype=torch.float64) / float(H * W)
     return {k: bufs[k] for k in want}

@@ -1,0 +1,445 @@
+"""GPU: the structure-tensor loss and maps off the two tile builds - the separable path of csrc/st_general.hip, radii up to 8 / 20 -
+held to the fp64 oracle: a grid of (sigma, rho) from radii (1, 1) to the bound, normalize on / off, gS on its own, small and ragged
+images, batch independence, the path forced onto the tile builds' pairs, criterion_sum, a NaN input, the maps, graph replay and the
+refusal beyond the bound.
+
+fp64-truth rule (conftest): loss   |hip - l64| <= max(1e-3 |l64|, 3 |l32 - l64|)
+                            grads  rel_err(hip, g64) <= max(1e-3, 3 rel_err(g32, g64))
+where l32 / g32 come from the fp32 oracle (the reference's arithmetic: tests/test_st_general.py holds it to the reference at these
+radii) and l64 / g64 from the same oracle in fp64.  Every case proves from the fp64 oracle that it is not vacuous.  Run with -s for
+the measured errors."""
+import ctypes
+import functools
+import math
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conftest import rel_err, truth_bound
+
+pytestmark = pytest.mark.gpu
+
+UP = 0.7                                              # non-unit upstream gradient throughout
+
+
+def radius_of(s):
+    """csrc/st_tile.h radius_of: the kernel sees sigma / rho as fp32."""
+    return max(int(4.0 * float(np.float32(s)) + 0.5), 1)
+
+
+# (sigma, rho) -> radii, none of them a tile build: smallest radii, R2 < R1, the widest k next to the narrowest g, the bound, and the
+# largest values that still round into it
+PAIRS = {(0.3, 0.3): (1, 1), (0.35, 0.6): (1, 2), (0.35, 5.0): (1, 20), (0.5, 1.0): (2, 4), (0.7, 1.4): (3, 6), (1.0, 2.0): (4, 8),
+         (1.0, 0.6): (4, 2), (1.5, 3.0): (6, 12), (2.0, 1.0): (8, 4), (2.0, 5.0): (8, 20), (2.1, 5.1): (8, 20)}
+BUILDS = {(2, 8): (0.5, 2.0), (4, 10): (1.0, 2.5)}   # the tile builds' pairs, for the forced runs
+
+
+def _images(seed, B, H, W, noise=0.08, scale=1.0):
+    """tests/test_st_loss_fp64_gpu.py:_images - smooth texture (bicubic-upsampled noise) for gt and gt + noise for sr, both in
+    [0, 1] x scale."""
+    gen = torch.Generator().manual_seed(seed)
+    base = torch.rand(B, 3, max(H // 6, 2), max(W // 6, 2), generator=gen)
+    gt = F.interpolate(base, size=(H, W), mode="bicubic", align_corners=False)
+    gt = (gt + 0.05 * torch.randn(gt.shape, generator=gen)).clamp(0, 1)
+    x = (gt + noise * torch.randn(gt.shape, generator=gen)).clamp(0, 1)
+    return x * scale, gt * scale
+
+
+def _hip(x, gt, sigma, rho, norm):
+    from srganst.loss import StructureTensorLoss
+    xg = x.cuda().requires_grad_(True)
+    loss = StructureTensorLoss(sigma, rho, norm)(xg, gt.cuda())
+    (gx,) = torch.autograd.grad(loss * UP, xg)
+    torch.cuda.synchronize()
+    return loss.detach().cpu().double(), gx.cpu().double() / UP
+
+
+def _oracle(x, gt, sigma, rho, norm):
+    from oracle import st as ost
+    l32, g32 = ost.st_loss_and_grad(x, gt, sigma, rho, norm)
+    l64, g64 = ost.st_loss_and_grad(x.double(), gt.double(), sigma, rho, norm)
+    return l32.double(), g32.double(), l64, g64
+
+
+@functools.lru_cache(maxsize=None)
+def _case(seed, B, H, W, sigma, rho, norm):
+    """Inputs, oracle results and the non-vacuity figure of one standard case, computed once and shared (never modified)."""
+    x, gt = _images(seed, B, H, W, scale=1.0 if norm else 255.0)
+    return x, gt, _oracle(x, gt, sigma, rho, norm), _frac_l2_above_1(x, gt, sigma, rho, norm)
+
+
+def _check(name, hip, ref, grad=True):
+    """Applies the fp64-truth rule to (loss, grad) and prints the measured errors."""
+    (lh, gh), (l32, g32, l64, g64) = hip, ref
+    e_l, b_l = abs(lh - l64).item(), max(1e-3 * abs(l64).item(), 3 * abs(l32 - l64).item())
+    e_g, b_g = rel_err(gh, g64), truth_bound(g32, g64)
+    print(f"[{name}] loss {lh.item():.6e} |hip-l64| {e_l:.3e} <= {b_l:.3e} | grad rel err {e_g:.3e} <= {b_g:.3e}")
+    assert torch.isfinite(lh) and bool(torch.isfinite(gh).all()), name
+    assert e_l <= b_l, f"{name}: loss |hip - fp64| = {e_l:.3e} > {b_l:.3e} (hip {lh.item():.9e}, fp64 {l64.item():.9e})"
+    if grad:
+        assert e_g <= b_g, f"{name}: grad rel err {e_g:.3e} > {b_g:.3e}"
+
+
+def _frac_l2_above_1(x, gt, sigma, rho, norm):
+    from oracle import st as ost
+    return float((ost.st_intermediates(x.double(), gt.double(), sigma, rho, norm)["L"][:, 1] > 1).double().mean())
+
+
+def test_pairs_are_off_the_tile_builds_and_inside_the_bound():
+    from srganst.loss import st_route
+    for (sigma, rho), radii in PAIRS.items():
+        assert (radius_of(sigma), radius_of(rho)) == radii and radii not in BUILDS and radii[0] <= 8 and radii[1] <= 20
+        assert st_route(sigma, rho) == (True, radii)
+    assert {(radius_of(s), radius_of(r)) for s, r in BUILDS.values()} == set(BUILDS)
+
+
+# ------------------------------------------------------------------------------------------------ A. parameter space
+@pytest.mark.parametrize("norm", [True, False])
+@pytest.mark.parametrize("sigma, rho", list(PAIRS))
+def test_st_params_vs_fp64(sigma, rho, norm):
+    """normalize=False on [0, 1] images is degenerate (every eigenvalue of adj(S1) S2 is below 1): those inputs are on the 0..255
+    scale."""
+    x, gt, ref, frac = _case(int(sigma * 100 + rho * 10) + norm, 2, 48, 40, sigma, rho, norm)
+    assert frac >= 0.1, f"vacuous case: only {frac:.1%} of the pixels have l2 > 1"
+    _check(f"A sigma={sigma} rho={rho} radii={PAIRS[sigma, rho]} normalize={norm} l2>1 {frac:.0%}", _hip(x, gt, sigma, rho, norm), ref)
+
+
+# ------------------------------------------------------------------------------------------------ B. gS on its own
+@pytest.mark.parametrize("norm", [True, False])
+@pytest.mark.parametrize("sigma, rho", [(1.0, 2.0), (2.0, 5.0)])
+def test_gs_pointwise_vs_fp64(sigma, rho, norm):
+    """gS = d(per-pixel distance) / d(Jxx, Jyy, Jxy of sr) straight from sst_st_general_fwd, against fp64 autograd of the oracle's
+    pointwise math (normalize, inverse, eigenvalues, distance) on the fp64 structure tensors; yardstick: the same autograd in fp32.
+    The saved planes are Ix, Iy of sr."""
+    from oracle import st as ost
+    from srganst import _abi
+    B, H, W = 2, 45, 38
+    x, gt = _images(23 + norm + radius_of(sigma), B, H, W, scale=1.0 if norm else 255.0)
+    lib = _abi.lib()
+    ns, nv, npart = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    _abi.check(lib.sst_st_general_workspace(B, H, W, ctypes.byref(ns), ctypes.byref(nv), ctypes.byref(npart)), "sst_st_general_workspace")
+    xd, gd = x.cuda(), gt.cuda()
+    loss = torch.empty((), device="cuda")
+    gS = torch.full_like(xd, float("nan"))
+    saved = torch.full((nv.value,), float("nan"), device="cuda")
+    scratch = torch.empty(ns.value, device="cuda")
+    partials = torch.empty(npart.value, device="cuda")
+    counter = torch.zeros(1, device="cuda", dtype=torch.int32)
+    _abi.check(lib.sst_st_general_fwd(_abi.ptr(xd), _abi.ptr(gd), _abi.ptr(loss), _abi.ptr(gS), _abi.ptr(saved), _abi.ptr(scratch),
+                                      _abi.ptr(partials), _abi.ptr(counter), B, H, W, sigma, rho, int(norm), _abi.stream_ptr()),
+               "sst_st_general_fwd")
+    torch.cuda.synchronize()
+    assert counter.item() == 0                                          # the ticket counter re-armed itself
+
+    def ref(dtype):
+        S1 = ost.structure_tensor(ost.grayscale(x.to(dtype)), sigma, rho).requires_grad_(True)
+        S2 = ost.structure_tensor(ost.grayscale(gt.to(dtype)), sigma, rho)
+        d = ost.pixel_distance(S1, S2, norm)
+        (g,) = torch.autograd.grad(d.sum(), S1)
+        return d.detach(), g.double()
+
+    def grads(dtype):                                                    # Ix, Iy of sr: utils.py:219-222
+        im = ost.grayscale(x.to(dtype))
+        g, dg = ost.gaussian_kernel(sigma, also_dg=True, dtype=dtype)
+        ix = F.conv2d(F.conv2d(im, dg.reshape(1, 1, -1, 1), padding="same"), g.reshape(1, 1, 1, -1), padding="same")
+        iy = F.conv2d(F.conv2d(im, g.reshape(1, 1, -1, 1), padding="same"), dg.reshape(1, 1, 1, -1), padding="same")
+        return torch.stack((ix[:, 0], iy[:, 0]))
+
+    (d32, gs32), (d64, gs64) = ref(torch.float32), ref(torch.float64)
+    frac = _frac_l2_above_1(x, gt, sigma, rho, norm)
+    assert frac >= 0.1 and float(gs64.abs().max()) > 0, frac
+    e, b = rel_err(gS.cpu(), gs64), truth_bound(gs32, gs64)
+    e_i, b_i = rel_err(saved.cpu().reshape(2, B, H, W), grads(torch.float64)), truth_bound(grads(torch.float32), grads(torch.float64))
+    print(f"[B gS sigma={sigma} rho={rho} normalize={norm}] rel err {e:.3e} <= {b:.3e}; saved Ix, Iy {e_i:.3e} <= {b_i:.3e}; "
+          f"loss {loss.item():.6e} vs fp64 {d64.mean().item():.6e}")
+    assert bool(torch.isfinite(gS).all()) and bool(torch.isfinite(saved).all())
+    assert e <= b, (e, b)
+    assert e_i <= b_i, (e_i, b_i)
+    assert abs(loss.item() - d64.mean().item()) <= max(1e-3 * d64.mean().item(), 3 * abs(d32.double().mean() - d64.mean()).item())
+
+
+# ------------------------------------------------------------------------------------------------ C. geometry
+SIZES = [1, 2, 5, 13, 31, 32, 33, 65]
+
+
+@pytest.mark.parametrize("H", SIZES)
+@pytest.mark.parametrize("sigma, rho", [(2.0, 5.0), (0.35, 0.6)])
+def test_geometry(sigma, rho, H):
+    """Every W in SIZES for this H: images smaller than the 28 px reach of radii (8, 20), one-pixel rows and columns, strips partial
+    in one direction only.  Tiny images can be (nearly) structureless; non-vacuity is asserted over the whole sweep of each pair."""
+    for W in SIZES:
+        x, gt = _images(H * 100 + W, 2, H, W, noise=0.1)
+        _check(f"C sigma={sigma} rho={rho} {H}x{W}", _hip(x, gt, sigma, rho, True), _oracle(x, gt, sigma, rho, True))
+    if H >= 13:
+        x, gt = _images(H * 100 + 65, 2, H, 65, noise=0.1)
+        assert _frac_l2_above_1(x, gt, sigma, rho, True) >= 0.1
+
+
+# ------------------------------------------------------------------------------------------------ D. batch independence
+def test_batch_independence():
+    """Five distinct images: the batched loss is the mean of the five single-image losses, and permuting the batch permutes the
+    gradient bit for bit (the plane index of every pass)."""
+    from srganst.loss import StructureTensorLoss
+    sigma, rho = 1.0, 2.0
+    x, gt = _images(9, 5, 37, 70)
+    x[2] = x[2] * 0.5                                  # make the images differ in more than their noise
+    gt[4] = gt[4].flip(-1)
+    assert _frac_l2_above_1(x, gt, sigma, rho, True) >= 0.1
+    crit = StructureTensorLoss(sigma, rho)
+    lh, gh = _hip(x, gt, sigma, rho, True)
+    singles = [crit(x[i:i + 1].cuda(), gt[i:i + 1].cuda()).item() for i in range(5)]
+    assert len(set(singles)) == 5
+    assert abs(lh.item() - np.mean(singles)) <= 1e-6 * abs(lh.item()), (lh.item(), singles)
+    perm = torch.tensor([3, 0, 4, 1, 2])
+    lp, gp = _hip(x[perm].contiguous(), gt[perm].contiguous(), sigma, rho, True)
+    assert torch.equal(gp, gh[perm])
+    assert abs(lp - lh).item() <= 1e-6 * abs(lh.item())
+    _check("D batch", (lh, gh), _oracle(x, gt, sigma, rho, True))
+
+
+# ------------------------------------------------------------------------------------------------ E. forced onto the tile builds' pairs
+@pytest.mark.parametrize("norm", [True, False])
+@pytest.mark.parametrize("radii", list(BUILDS))
+def test_forced_general_path_against_the_tile_path(monkeypatch, radii, norm):
+    """ST_FORCE_GENERAL sends a built pair down the general path: both paths obey the truth rule and agree with each other within
+    it.  With the switch off the pair runs the tile kernels, launches and bits of a plain call."""
+    from srganst import loss as sl
+    from srganst import ops
+    sigma, rho = BUILDS[radii]
+    x, gt, ref, frac = _case(31 + radii[0] + norm, 2, 48, 40, sigma, rho, norm)
+    assert frac >= 0.1
+
+    def traced(force):
+        monkeypatch.setattr(sl, "ST_FORCE_GENERAL", force)
+        monkeypatch.setattr(ops, "TRACE_HBM", {})
+        out = _hip(x, gt, sigma, rho, norm)
+        return out, sorted(ops.TRACE_HBM)
+
+    assert sl.ST_FORCE_GENERAL is False
+    plain = _hip(x, gt, sigma, rho, norm)
+    tile, tile_launches = traced(False)
+    general, general_launches = traced(True)
+    again, again_launches = traced(False)
+    assert tile_launches == again_launches == ["st_loss_fwd_kernel"]
+    assert general_launches == ["stg_hadj_out_kernel", "stg_loss_fwd_kernel"]
+    for other in (tile, again):
+        assert torch.equal(other[0], plain[0]) and torch.equal(other[1], plain[1])
+    _check(f"E tile radii={radii} normalize={norm}", tile, ref)
+    _check(f"E general radii={radii} normalize={norm}", general, ref)
+    e, b = rel_err(general[1], tile[1]), truth_bound(ref[1], ref[3])
+    print(f"[E radii={radii} normalize={norm}] general vs tile: grad rel err {e:.3e} <= {b:.3e}, "
+          f"loss {general[0].item():.9e} vs {tile[0].item():.9e}")
+    assert e <= b, (e, b)
+
+
+# ------------------------------------------------------------------------------------------------ F. criterion_sum
+@pytest.mark.parametrize("pix", ["mse", "l1"])
+@pytest.mark.parametrize("st_first", [True, False])
+def test_criterion_sum_general_route(pix, st_first):
+    """criterion_sum with one pixel and one ST term off the tile builds: the two terms run unfused and accumulate into one d(sr),
+    in either order; total and gradient against the oracle's sum, the weighted ST value against the stand-alone criterion."""
+    from oracle import st as ost
+    from srganst import loss as sl
+    from srganst import ops
+    sigma, rho, norm = 1.0, 2.0, True
+    x, gt = _images(11 + len(pix), 2, 40, 72)
+    assert _frac_l2_above_1(x, gt, sigma, rho, norm) >= 0.1
+    crit = F.mse_loss if pix == "mse" else F.l1_loss
+    w_st = 1 / 3
+    w_pix = w_st * float(ost.st_loss(x, gt, sigma, rho, norm) / crit(x, gt))      # both terms carry the same weight in the total
+    st_term, pix_term = sl.StructureTensorLoss(sigma, rho, norm), sl.MSELoss() if pix == "mse" else sl.L1Loss()
+    terms, weights = ([st_term, pix_term], [w_st, w_pix]) if st_first else ([pix_term, st_term], [w_pix, w_st])
+    k = 0 if st_first else 1
+    xg = x.cuda().requires_grad_(True)
+    saved_trace, ops.TRACE_HBM = ops.TRACE_HBM, {}
+    try:
+        total, weighted = sl.criterion_sum(xg, gt.cuda(), terms, weights)
+        (gx,) = torch.autograd.grad(total * UP, xg)
+        launches = set(ops.TRACE_HBM)
+    finally:
+        ops.TRACE_HBM = saved_trace
+    alone = sl.StructureTensorLoss(sigma, rho, norm)(x.cuda(), gt.cuda())
+    torch.cuda.synchronize()
+    assert {"stg_loss_fwd_kernel", "stg_hadj_out_kernel"} <= launches and not {"st_loss_fwd_kernel", "st_loss_bwd_kernel"} & launches
+    assert np.float32(weighted[k].item()) == np.float32(alone.item()) * np.float32(weights[k]), (weighted, alone)
+
+    def oracle(dtype):
+        xo = x.to(dtype).requires_grad_(True)
+        t = w_st * ost.st_loss(xo, gt.to(dtype), sigma, rho, norm) + w_pix * crit(xo, gt.to(dtype))
+        (g,) = torch.autograd.grad(t, xo)
+        return t.detach().double(), g.double()
+
+    (l32, g32), (l64, g64) = oracle(torch.float32), oracle(torch.float64)
+    _check(f"F {pix} st_first={st_first}", (total.detach().cpu().double(), gx.cpu().double() / UP), (l32, g32, l64, g64))
+
+
+# ------------------------------------------------------------------------------------------------ G. a NaN input
+@pytest.mark.parametrize("where", ["corner", "inside"])
+def test_nan_in_sr(where):
+    """One NaN in sr, in batch entry 1 of 3.  The loss is non-finite exactly when the fp32 oracle's is.  The other images' gradients
+    are bit-identical to a run without the bad value.  In the affected image the gradient is non-finite exactly where the oracle's
+    is, and every pixel farther than 2 (R1 + R2) from the bad one (outside its receptive field through forward and backward) is
+    bit-identical to the clean run."""
+    from oracle import st as ost
+    sigma, rho = 1.0, 2.0
+    R = radius_of(sigma) + radius_of(rho)
+    H, W = 64, 68
+    x, gt = _images(77 + len(where), 3, H, W)
+    yx = (0, 0) if where == "corner" else (30, 33)
+    xb = x.clone()
+    xb[1, 1, yx[0], yx[1]] = float("nan")
+    _, gh_clean = _hip(x, gt, sigma, rho, True)
+    lh, gh = _hip(xb, gt, sigma, rho, True)
+    l32, g32 = ost.st_loss_and_grad(xb, gt, sigma, rho, True)
+    print(f"[G {where}] loss {lh.item()} (oracle {l32.item()}), non-finite grads hip {int((~torch.isfinite(gh)).sum())} "
+          f"oracle {int((~torch.isfinite(g32)).sum())}")
+    assert not bool(torch.isfinite(l32))
+    assert bool(torch.isfinite(lh)) == bool(torch.isfinite(l32)), (lh.item(), l32.item())
+    for b in (0, 2):
+        assert torch.equal(gh[b], gh_clean[b]), b
+    bad = ~torch.isfinite(g32[1])
+    assert bool(bad.any())
+    assert torch.equal(~torch.isfinite(gh[1]), bad), "non-finite gradient pattern differs from the oracle's"
+    far = torch.ones(H, W, dtype=torch.bool)
+    far[max(yx[0] - 2 * R, 0):yx[0] + 2 * R + 1, max(yx[1] - 2 * R, 0):yx[1] + 2 * R + 1] = False
+    assert bool(far.any())
+    assert torch.equal(gh[1][:, far], gh_clean[1][:, far])
+    assert bool(torch.isfinite(g32[1][:, far]).all())
+
+
+# ------------------------------------------------------------------------------------------------ H. maps
+ALL = ("Sx", "Sgt", "Fx", "Fgt", "d", "tile_sums", "distance")
+
+
+def _features(S):
+    """(t, c2, s2) planes of S [B,3,H,W] in S's dtype: the definition in srganst/st.py."""
+    t = S[:, 0] + S[:, 1]
+    den = t + 1e-12
+    return torch.stack((t, (S[:, 0] - S[:, 1]) / den, 2 * S[:, 2] / den), dim=1)
+
+
+def _maps_oracle(x, gt, sigma, rho, norm, dtype):
+    from oracle import st as ost
+    it = ost.st_intermediates(x.to(dtype), gt.to(dtype), sigma, rho, norm)
+    return {"Sx": it["S1"], "Sgt": it["S2"], "Fx": _features(it["S1"]), "Fgt": _features(it["S2"]), "d": it["d"], "L": it["L"],
+            "distance": it["d"].mean(dim=(1, 2))}
+
+
+def _maps_hip(x, gt, sigma, rho, norm=True, want=ALL):
+    from srganst import st
+    out = st.st_maps(x.cuda(), None if gt is None else gt.cuda(), sigma, rho, norm, want=want)
+    torch.cuda.synchronize()
+    return {k: v.cpu() for k, v in out.items()}
+
+
+@pytest.mark.parametrize("norm", [True, False])
+@pytest.mark.parametrize("sigma, rho", [(1.0, 2.0), (2.0, 5.0)])
+def test_maps_vs_fp64(sigma, rho, norm):
+    """The bounds of tests/test_st_maps_gpu.py:test_maps_vs_fp64 on a ragged 3 x 2-tile batch, and the per-image distances against
+    the loss.  The features' 1e-12 guard must stay below half an fp32 ulp of the trace: trace >= 1e-12 / 2^-24 = 1.7e-5."""
+    from srganst.loss import StructureTensorLoss
+    B, H, W = 2, 70, 45
+    x, gt = _images(300 + radius_of(sigma) + norm, B, H, W, scale=1.0 if norm else 255.0)
+    o32, o64 = _maps_oracle(x, gt, sigma, rho, norm, torch.float32), _maps_oracle(x, gt, sigma, rho, norm, torch.float64)
+    frac = float((o64["L"][:, 1] > 1).double().mean())
+    assert frac >= 0.1, f"vacuous case: only {frac:.1%} of the pixels have l2 > 1"
+    trace = min(float(o64["Fx"][:, 0].min()), float(o64["Fgt"][:, 0].min()))
+    assert trace >= 1.7e-5, f"trace {trace:.3e}: the 1e-12 guard of the features would take part"
+    got = _maps_hip(x, gt, sigma, rho, norm)
+    name = f"H sigma={sigma} rho={rho} normalize={norm} {B}x{H}x{W}"
+    for key in ("Sx", "Sgt", "d", "Fx", "Fgt"):
+        assert got[key].dtype == torch.float32 and got[key].shape == o64[key].shape, (key, got[key].shape)
+        assert bool(torch.isfinite(got[key]).all()), key
+        e, b = rel_err(got[key], o64[key]), truth_bound(o32[key], o64[key])
+        print(f"[{name}] {key}: rel err {e:.3e} <= {b:.3e}")
+        assert e <= b, f"{name} {key}: rel err {e:.3e} > {b:.3e}"
+    tiles = ((H + 31) // 32) * ((W + 31) // 32)
+    assert tuple(got["tile_sums"].shape) == (B, tiles) and got["distance"].dtype == torch.float64
+    l32, l64 = o32["distance"].double(), o64["distance"]
+    for b in range(B):
+        e, bound = abs(got["distance"][b].item() - l64[b].item()), max(1e-3 * abs(l64[b].item()), 3 * abs(l32[b].item() - l64[b].item()))
+        print(f"[{name}] image {b}: distance {got['distance'][b].item():.6e} |hip-l64| {e:.3e} <= {bound:.3e}")
+        assert math.isfinite(got["distance"][b].item()) and e <= bound, (b, e, bound)
+    loss = StructureTensorLoss(sigma, rho, norm)(x.cuda(), gt.cuda()).item()
+    assert abs(got["distance"].mean().item() - loss) <= 1e-6 * abs(loss), (got["distance"].mean().item(), loss)
+
+
+@pytest.mark.parametrize("sigma, rho", [(1.0, 2.0), (2.0, 5.0)])
+def test_maps_optional_outputs_are_the_same_bits(sigma, rho):
+    x, gt = _images(51 + radius_of(sigma), 2, 33, 31)
+    full = _maps_hip(x, gt, sigma, rho)
+    for key in ALL:
+        alone = _maps_hip(x, gt, sigma, rho, want=(key,))
+        assert list(alone) == [key]
+        assert torch.equal(alone[key], full[key]), f"{key} requested alone differs from the all-outputs call"
+    x_only = _maps_hip(x, None, sigma, rho, want=("Sx", "Fx"))
+    assert torch.equal(x_only["Sx"], full["Sx"]) and torch.equal(x_only["Fx"], full["Fx"])
+    swapped = _maps_hip(gt, x, sigma, rho, want=("Sx", "Sgt"))             # both images run the same passes
+    assert torch.equal(swapped["Sx"], full["Sgt"]) and torch.equal(swapped["Sgt"], full["Sx"])
+
+
+# ------------------------------------------------------------------------------------------------ I. graph capture
+def test_graph_replay_matches_eager():
+    """criterion_sum forward + backward at (1.5, 3.0), captured after one warm-up call (which allocates the criterion's workspace)
+    and replayed on two different inputs copied into the static tensors: loss and gradient bits equal the eager calls' each time, so
+    the ticket counter re-arms inside the graph.  Everything is launched on the capturing stream: one chain, no side streams."""
+    from srganst import loss as sl
+    sigma, rho = 1.5, 3.0
+    B, H, W = 2, 48, 40
+    inputs = [_images(seed, B, H, W) for seed in (501, 502, 503)]
+    assert all(_frac_l2_above_1(x, gt, sigma, rho, True) >= 0.1 for x, gt in inputs)
+    weights = [1 / 3, 1.0]
+
+    def run(terms, xs, gs):
+        total, weighted = sl.criterion_sum(xs, gs, terms, weights)
+        (gx,) = torch.autograd.grad(total, xs)
+        return total, weighted, gx
+
+    eager = []
+    for x, gt in inputs:
+        terms = [sl.StructureTensorLoss(sigma, rho), sl.MSELoss()]
+        total, weighted, gx = run(terms, x.cuda().requires_grad_(True), gt.cuda())
+        eager.append((total.detach().clone(), weighted.clone(), gx.clone()))
+    torch.cuda.synchronize()
+    assert not torch.equal(eager[1][0], eager[2][0])
+
+    terms = [sl.StructureTensorLoss(sigma, rho), sl.MSELoss()]
+    xs = inputs[0][0].cuda().requires_grad_(True)
+    gs = inputs[0][1].cuda()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        run(terms, xs, gs)                                               # warm-up: allocates the workspace
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    ws_ptr = terms[0]._ws["general_scratch"].data_ptr()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        total, weighted, gx = run(terms, xs, gs)
+    assert terms[0]._ws["general_scratch"].data_ptr() == ws_ptr          # nothing of the workspace was re-allocated in the capture
+    for k in (1, 2, 1):
+        with torch.no_grad():
+            xs.copy_(inputs[k][0])
+            gs.copy_(inputs[k][1])
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(total, eager[k][0]) and torch.equal(weighted, eager[k][1]), (k, total, eager[k][0])
+        assert torch.equal(gx, eager[k][2]), k
+    del graph
+
+
+# ------------------------------------------------------------------------------------------------ J. beyond the bound
+@pytest.mark.parametrize("sigma, rho, radii", [(2.2, 2.0, (9, 8)), (1.0, 5.2, (4, 21))])
+def test_radii_beyond_the_bound_raise_cleanly(sigma, rho, radii):
+    from srganst import st
+    from srganst._abi import HipPathError
+    from srganst.loss import StructureTensorLoss
+    assert (radius_of(sigma), radius_of(rho)) == radii
+    x, gt, ref, _ = _case(110, 2, 48, 40, 1.0, 2.0, True)
+    with pytest.raises(HipPathError, match=rf"radii \({radii[0]},{radii[1]}\) not built"):
+        StructureTensorLoss(sigma, rho)(x.cuda().requires_grad_(True), gt.cuda())
+    with pytest.raises(HipPathError, match=rf"radii \({radii[0]},{radii[1]}\) not built"):
+        st.st_distance(x.cuda(), gt.cuda(), sigma, rho)
+    _check("J (1.0, 2.0) after the refusal", _hip(x, gt, 1.0, 2.0, True), ref)
