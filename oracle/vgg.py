@@ -2,7 +2,7 @@
 
 Restates reference loss.py:11-70: ImageNet normalisation (mean .485/.456/.406, std .229/.224/.225), torchvision VGG19
 ``features[0..35]`` (16 conv3x3+ReLU, 4 MaxPool2d(2) before index 36), taps at features.17 / .26 / .35 (ReLU outputs
-relu3_4 / relu4_4 / relu5_4) weighted 1/8, 1/4, 1/2 (config.py:60-64), criterion MSE.
+relu3_4 / relu4_4 / relu5_4) weighted 1/8, 1/4, 1/2 (config.py:60-64), criterion MSE ("mse" / "l2") or L1 (loss.py:34-39).
 PARITY UNPINNED: the reference fetches torchvision's IMAGENET1K_V1 weights from the network (loss.py:46); torchvision
 and the weights are both unavailable, so this restatement cannot be checked against reference outputs.  It follows
 torchvision's published VGG19 layer list; weights are seeded random (torchvision's own VGG init: kaiming_normal
@@ -47,6 +47,18 @@ def init_vgg_state(seed=0, upto=35):
     return sd
 
 
+def init_vgg_state_biased(seed=0, upto=35, bias_std=0.1):
+    """init_vgg_state(seed) with every conv bias redrawn as bias_std * randn (own generator, seeded seed + 1, so the weights are
+    those of init_vgg_state(seed)).  torchvision's init zeroes the biases, the ImageNet weights do not: a state with zero biases
+    cannot tell whether a conv adds its bias at all."""
+    sd = init_vgg_state(seed, upto)
+    g = torch.Generator().manual_seed(seed + 1)
+    for k in sd:
+        if k.endswith(".bias"):
+            sd[k] = bias_std * torch.randn(sd[k].shape, generator=g)
+    return sd
+
+
 def vgg_features(sd, x, taps=(17, 26, 35)):
     mean = torch.tensor(MEAN, dtype=x.dtype).view(1, 3, 1, 1)
     std = torch.tensor(STD, dtype=x.dtype).view(1, 3, 1, 1)
@@ -64,12 +76,16 @@ def vgg_features(sd, x, taps=(17, 26, 35)):
     return feats
 
 
-def content_loss(sd, x, gt, layers=None):
+def content_loss(sd, x, gt, layers=None, criterion="mse"):
+    """loss.py:51-70: sum_layer weight * criterion(feat(x), feat(gt)); criterion "mse" | "l2" (MSELoss) or "l1" (L1Loss)."""
+    if criterion not in ("mse", "l2", "l1"):
+        raise NotImplementedError("%s criterion has not been implmented." % criterion)
+    crit = F.l1_loss if criterion == "l1" else F.mse_loss
     layers = layers or {"features.17": 1 / 8, "features.26": 1 / 4, "features.35": 1 / 2}
     taps = tuple(int(k.split(".")[1]) for k in layers)
     fx, fg = vgg_features(sd, x, taps), vgg_features(sd, gt, taps)
     loss = x.new_zeros(())
     for name, w in layers.items():
         i = int(name.split(".")[1])
-        loss = loss + w * F.mse_loss(fx[i], fg[i])
+        loss = loss + w * crit(fx[i], fg[i])
     return loss

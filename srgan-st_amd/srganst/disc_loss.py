@@ -75,6 +75,8 @@ class _DiscFeatFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
+        if not ctx.needs_input_grad[0]:             # only gt asks for a gradient: it gets none (forward kept nothing)
+            return None, None, None, None
         module, saved, taps, B = ctx.module, ctx.saved, ctx.taps, ctx.B
         feats = module.D.features
         wd = module.packed(1)

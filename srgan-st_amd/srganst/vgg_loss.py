@@ -81,6 +81,8 @@ class _VggFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
+        if not ctx.needs_input_grad[0]:             # only gt asks for a gradient: it gets none (forward kept nothing)
+            return None, None, None, None
         module, saved, feats, B = ctx.module, ctx.saved, ctx.feats, ctx.B
         taps, weights = module.taps, module.tap_weights
         wd = module.packed(1)

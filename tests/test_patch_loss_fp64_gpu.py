@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from conftest import rel_err
+from graph_refs import graph_vs_eager
 
 pytestmark = pytest.mark.gpu
 
@@ -224,42 +225,6 @@ def test_patch_loss_non_finite_inputs_follow_torch_min(kind, where, dist):
           f"{int(nonfinite.sum())} non-finite rows")
 
 
-def _graph_vs_eager(patch_name, patch_crit, reuse_d_sr):
-    from srganst.config import Config
-    from srganst.engine import TrainEngine
-    from srganst.loss import MSELoss, StructureTensorLoss
-    from srganst.model import Discriminator, Generator
-
-    def run(use_graph):
-        cfg = Config()
-        cfg.MODEL.G_N_CHANNEL, cfg.MODEL.G_N_RCB, cfg.MODEL.D_N_CHANNEL = 16, 2, 8
-        cfg.KERNEL.REUSE_D_SR, cfg.KERNEL.BATCH_D_STEP = reuse_d_sr, True
-        torch.manual_seed(1)
-        D, G = Discriminator(cfg).cuda().train(), Generator(cfg).cuda().train()
-        cfg.add_g_criterion("Pixel", MSELoss(), 1.0)
-        cfg.add_g_criterion("ST", StructureTensorLoss(), 1 / 3)
-        cfg.add_g_criterion(patch_name, patch_crit(), cfg.MODEL.G_LOSS.CRITERION_WEIGHTS[patch_name])
-        cfg.SOLVER.D_UPDATE_INTERVAL = 1
-        eng = TrainEngine(cfg, G, D, use_graph=use_graph, adam_capturable=True)
-        gen = torch.Generator().manual_seed(2)
-        for _ in range(5):
-            gt = torch.rand(4, 3, 96, 96, generator=gen).cuda()
-            lr = torch.rand(4, 3, 24, 24, generator=gen).cuda()
-            eng.step(gt, lr)
-        torch.cuda.synchronize()
-        assert eng.graph_active == use_graph
-        assert patch_name in eng.loss_values
-        return G.state_dict(), D.state_dict(), {k: v.item() for k, v in eng.loss_values.items()}
-
-    g1, d1, l1 = run(False)
-    g2, d2, l2 = run(True)
-    for k in g1:
-        assert torch.equal(g1[k], g2[k]), k
-    for k in d1:
-        assert torch.equal(d1[k], d2[k]), k
-    assert l1 == l2, (l1, l2)
-
-
 @pytest.mark.parametrize("schedule", ["shared", "batched"])
 @pytest.mark.parametrize("loss", ["BestBuddy", "Gram", "PatchwiseST-l2", "PatchwiseST-l1"])
 def test_train_engine_graph_equals_eager_with_patch_loss(loss, schedule):
@@ -270,4 +235,4 @@ def test_train_engine_graph_equals_eager_with_patch_loss(loss, schedule):
     from srganst.loss import BestBuddyLoss, GramLoss, PatchwiseStructureTensorLoss
     name, _, dist = loss.partition("-")
     cls = {"BestBuddy": BestBuddyLoss, "Gram": GramLoss, "PatchwiseST": PatchwiseStructureTensorLoss}[name]
-    _graph_vs_eager(name, lambda: cls(dist_norm=dist or "l2"), schedule == "shared")
+    graph_vs_eager(lambda cfg: [(name, cls(dist_norm=dist or "l2"))], schedule == "shared")
