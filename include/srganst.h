@@ -75,6 +75,23 @@ int sst_st_general_bwd(const float* saved, const float* gS, float* dsr, float* s
                        int accumulate, int B, int H, int W, float sigma, float rho, void* stream);
 int sst_st_general_maps(const float* x, const float* gt, float* Sx, float* Sgt, float* Fx, float* Fgt, float* d, float* tile_sums,
                         float* scratch, int B, int H, int W, float sigma, float rho, int normalize, void* stream);
+/* ---- SSIM loss (loss.py: SSIMLoss; csrc/ssim_loss.hip): loss[0] = 1 - mean(S) over batch, planes and the
+ * (H-10) x (W-10) valid region of the 11-tap sigma 1.5 window, C1 = k1^2, C2 = k2^2 (images on the 0..1 scale).  sr, gt, dsr: NCHW
+ * fp32 [B,3,H,W], H, W >= 11.  planes: 1 = one luma plane (65.481 R + 128.553 G + 24.966 B + 16) / 255, 3 = the RGB planes.
+ * sst_ssim_loss_workspace: map_floats = B * planes * (H-10) * (W-10) * 3 (the forward's saved maps dS/da, dS/dexx, dS/dexy, laid out
+ *   [B*planes][3][H-10][W-10]); partial_floats = 2 * B * planes * ceil((H-10)/32) * ceil((W-10)/32): one fp64 partial per workgroup,
+ *   so `partials` must be 8-byte aligned.
+ * fwd: maps may be null (no gradient wanted: nothing is written there).  counter must be 0 at the first call and re-arms itself;
+ *   the partials are summed in index order by the last-arriving workgroup: one launch, the same bits in every run.
+ * bwd: dsr (+)= scale_host * (scale_dev ? *scale_dev : 1) * d loss / d sr from the maps of the forward of the same (sr, gt); gt
+ *   is a constant.  One launch.
+ * Everything is validated on the host before any launch (null pointer, H or W < 11, planes not 1 or 3, k1 or k2 <= 0: non-zero
+ * return, message in sst_last_error); no allocation, no sync, asynchronous on `stream`. */
+int sst_ssim_loss_workspace(int B, int H, int W, int planes, int64_t* map_floats, int64_t* partial_floats);
+int sst_ssim_loss_fwd(const float* sr, const float* gt, float* loss, float* maps, float* partials, unsigned* counter, int B, int H,
+                      int W, int planes, double k1, double k2, void* stream);
+int sst_ssim_loss_bwd(const float* sr, const float* gt, const float* maps, float* dsr, const float* scale_dev, float scale_host,
+                      int accumulate, int B, int H, int W, int planes, void* stream);
 
 /* ---- convolution (fp32 MFMA implicit GEMM, NHWC) --------------------------------------------------
  * Replaces the cuDNN/oneDNN kernels behind nn.Conv2d fwd/bwd of model.py:32-56,101,113,127,159,173,176.

@@ -2,6 +2,7 @@
 
 StructureTensorLoss  <- reference loss.py:380-413 (+ utils.py:194-280), kernels csrc/st_loss.hip (radii (2,8), (4,10)) and
                         csrc/st_general.hip (every other (sigma, rho) up to radii 8 / 20)
+SSIMLoss             1 - mean SSIM, the criterion for the second number validate reports; kernels csrc/ssim_loss.hip
 ContentLossVGG       <- reference loss.py:11-70, in vgg_loss.py (re-exported here)
 BestBuddyLoss / GramLoss / PatchwiseStructureTensorLoss <- reference loss.py:78-228, 292-375, kernels csrc/bb_loss.hip
 ContentLossDiscriminator <- reference loss.py:231-289, in disc_loss.py (re-exported here)
@@ -165,6 +166,95 @@ class StructureTensorLoss(nn.Module):
 
     def __repr__(self):
         return f"StructureTensorLoss(sigma={self.sigma}, rho={self.rho}, normalize={self.normalize})"
+
+
+# ------------------------------------------------------------------------------------------------
+SSIM_MIN_SIDE = 11        # the 11-tap window's valid region is empty below it
+
+
+def _ssim_workspace(x, gt, planes, ws):
+    """Checks an SSIM input pair and (re)builds the forward's partials / last-arriver counter in the criterion's cache `ws` when
+    device, shape or plane count changed -> floats of the per-call gradient maps."""
+    for name, t in (("sr", x), ("gt", gt)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _abi.HipPathError(f"SSIMLoss: {name} must be a tensor on a ROCm device (no CPU fallback)")
+        if t.dtype != torch.float32:
+            raise _abi.HipPathError(f"SSIMLoss: {name} must be fp32, got {t.dtype}")
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape != gt.shape or x.device != gt.device:
+        raise _abi.HipPathError(f"SSIMLoss: expected fp32 [B,3,H,W] pairs on one device, got {tuple(x.shape)} / {tuple(gt.shape)}")
+    B, _, H, W = x.shape
+    if B < 1 or H < SSIM_MIN_SIDE or W < SSIM_MIN_SIDE:
+        raise _abi.HipPathError(f"SSIMLoss: images of {W}x{H} are below the {SSIM_MIN_SIDE}-px minimum of the SSIM window")
+    n_maps, n_part = ctypes.c_int64(), ctypes.c_int64()
+    _abi.check(_abi.lib().sst_ssim_loss_workspace(B, H, W, planes, ctypes.byref(n_maps), ctypes.byref(n_part)), "sst_ssim_loss_workspace")
+    key = (x.device, B, H, W, planes)
+    if ws.get("key") != key:
+        ws["key"] = key
+        ws["partials"] = torch.empty(n_part.value, device=x.device, dtype=torch.float32)
+        ws["counter"] = torch.zeros(1, device=x.device, dtype=torch.int32)
+    return n_maps.value
+
+
+class _SsimLossFn(torch.autograd.Function):
+    """1 - mean SSIM (csrc/ssim_loss.hip).  want_grad False (no_grad, or sr does not require grad): the gradient maps are neither
+    allocated nor written."""
+
+    @staticmethod
+    def forward(ctx, x, gt, planes, k1, k2, ws, want_grad):
+        from . import ops
+        n_maps = _ssim_workspace(x, gt, planes, ws)
+        x = x.contiguous()
+        gt = gt.contiguous()
+        B, _, H, W = x.shape
+        maps = torch.empty(n_maps, device=x.device, dtype=torch.float32) if want_grad else None
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(maps), _abi.ptr(ws["partials"]), _abi.ptr(ws["counter"]), B, H, W,
+                planes, k1, k2)
+        # algorithmic bytes: the forward reads sr + gt, the backward writes d(sr)
+        ops._launch_hbm(_abi.lib().sst_ssim_loss_fwd, args, "sst_ssim_loss_fwd", "ssim_loss_fwd_kernel", 2.0 * x.numel() * 4,
+                        (x, gt, loss, maps, ws))
+        ctx.planes = planes
+        if want_grad:
+            ctx.save_for_backward(x, gt, maps)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import ops
+        if not ctx.saved_tensors:
+            raise _abi.HipPathError("SSIMLoss: the gradient is taken with respect to sr only (gt is a constant)")
+        x, gt, maps = ctx.saved_tensors
+        B, _, H, W = x.shape
+        dx = torch.empty_like(x)
+        g = grad_out.contiguous().to(torch.float32)
+        bargs = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(maps), _abi.ptr(dx), _abi.ptr(g), 1.0, 0, B, H, W, ctx.planes)
+        ops._launch_hbm(_abi.lib().sst_ssim_loss_bwd, bargs, "sst_ssim_loss_bwd", "ssim_loss_bwd_kernel", 1.0 * x.numel() * 4,
+                        (x, gt, maps, dx, g))
+        return dx, None, None, None, None, None, None
+
+
+class SSIMLoss(nn.Module):
+    """1 - mean SSIM(sr, gt): the 11-tap sigma 1.5 Gaussian window over its valid region, C1 = k1^2, C2 = k2^2 for images on the
+    0..1 scale - the SSIM validate reports (csrc/metrics.hip) as a criterion, without the uint8 quantisation and the clamp.
+    channel "y": one luma plane (65.481 R + 128.553 G + 24.966 B + 16) / 255; "rgb": the mean over the three planes.  fp32
+    [B,3,H,W] pairs with H, W >= 11; the gradient is taken with respect to sr only.  Kernels: csrc/ssim_loss.hip."""
+
+    def __init__(self, channel: str = "y", k1: float = 0.01, k2: float = 0.03):
+        super().__init__()
+        if channel not in ("y", "rgb"):
+            raise ValueError(f"SSIMLoss: channel must be 'y' or 'rgb', got {channel!r}")
+        for name, k in (("k1", k1), ("k2", k2)):
+            if not (isinstance(k, (int, float)) and 0.0 < float(k) < float("inf")):
+                raise ValueError(f"SSIMLoss: {name} must be a positive number, got {k!r}")
+        self.channel, self.k1, self.k2 = channel, float(k1), float(k2)
+        self._ws = {}
+
+    def forward(self, x, gt):
+        want_grad = torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad
+        return _SsimLossFn.apply(x, gt, 1 if self.channel == "y" else 3, self.k1, self.k2, self._ws, want_grad)
+
+    def __repr__(self):
+        return f"SSIMLoss(channel={self.channel!r}, k1={self.k1}, k2={self.k2})"
 
 
 # ------------------------------------------------------------------------------------------------
