@@ -4,11 +4,10 @@
 
 Kernel graph (like vgg_loss.py): SR and GT go through the first discriminator layers as ONE batch of 2B (eval-mode BatchNorm is
 a per-channel affine, applied together with LeakyReLU while the next conv stages its input); a tap is the conv output plus its
-affine, the criterion kernel applies affine + LeakyReLU itself (csrc/misc.hip: feat_loss_*); backward runs on the SR half
-only (activation/affine backward, stride-1 / stride-2 data-gradient convs), no weight gradients (frozen)."""
+affine, the criterion kernel applies affine + LeakyReLU itself (csrc/misc.hip: feat_loss_*, one ops.reduction_ws workspace per tap
+in ``_ws``) and the taps are summed by ops.weighted_sum; backward runs on the SR half only (activation/affine backward, stride-1 /
+stride-2 data-gradient convs), no weight gradients (frozen)."""
 from __future__ import annotations
-
-import ctypes
 
 import torch
 from torch import nn
@@ -25,15 +24,10 @@ _PLAN = [(0, None, 1), (2, 3, 2), (5, 6, 1), (8, 9, 2), (11, 12, 1), (14, 15, 2)
 
 def _feat_loss_fwd(a, b, scale, shift, C, mode, ws):
     n = a.numel()
-    key = (a.device, n)
-    if ws.get("key") != key:
-        ws["key"] = key
-        ws["partials"] = torch.empty(_abi.lib().sst_pixel_loss_blocks(n), device=a.device, dtype=torch.float32)
-        ws["counter"] = torch.zeros(1, device=a.device, dtype=torch.int32)
+    partials, counter = ops.reduction_ws(ws, (a.device, n), lambda: _abi.lib().sst_pixel_loss_blocks(n))
     loss = torch.empty((), device=a.device, dtype=torch.float32)
     _abi.check(_abi.lib().sst_feat_loss_fwd(_abi.ptr(a), _abi.ptr(b), _abi.ptr(scale), _abi.ptr(shift), LRELU, C, _abi.ptr(loss),
-                                            _abi.ptr(ws["partials"]), _abi.ptr(ws["counter"]), n, mode, _abi.stream_ptr()),
-               "sst_feat_loss_fwd")
+                                            _abi.ptr(partials), _abi.ptr(counter), n, mode, _abi.stream_ptr()), "sst_feat_loss_fwd")
     return loss
 
 
@@ -65,10 +59,7 @@ class _DiscFeatFn(torch.autograd.Function):
             h, act = y, ops.ACT_SLOPE
         terms = [_feat_loss_fwd(y[:B], y[B:], sc, sh, y.shape[-1], module.mode, module._ws.setdefault(t, {}))
                  for t, (y, sc, sh) in sorted(taps.items())]
-        arr = (ctypes.c_void_p * len(terms))(*[t.data_ptr() for t in terms])
-        wts = (ctypes.c_float * len(terms))(*[float(module.tap_weights[t]) for t in sorted(taps)])
-        out = torch.empty((), device=x.device, dtype=torch.float32)
-        _abi.check(_abi.lib().sst_weighted_sum(arr, wts, len(terms), _abi.ptr(out), None, _abi.stream_ptr()), "sst_weighted_sum")
+        out, _ = ops.weighted_sum(terms, [module.tap_weights[t] for t in sorted(taps)], False)
         if need:
             ctx.module, ctx.saved, ctx.taps, ctx.B = module, saved, taps, B
         return out

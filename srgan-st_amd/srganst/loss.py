@@ -1,11 +1,16 @@
 """Generator criterions on the HIP path.  Mirrors reference loss.py (criterion(sr, gt) -> 0-dim).
 
+MSELoss / L1Loss     nn.MSELoss() of reference config.py:88-90 and its L1 variant, kernels csrc/misc.hip (pixel_loss_*)
 StructureTensorLoss  <- reference loss.py:380-413 (+ utils.py:194-280), kernels csrc/st_loss.hip (radii (2,8), (4,10)) and
                         csrc/st_general.hip (every other (sigma, rho) up to radii 8 / 20)
 SSIMLoss             1 - mean SSIM, the criterion for the second number validate reports; kernels csrc/ssim_loss.hip
 ContentLossVGG       <- reference loss.py:11-70, in vgg_loss.py (re-exported here)
 BestBuddyLoss / GramLoss / PatchwiseStructureTensorLoss <- reference loss.py:78-228, 292-375, kernels csrc/bb_loss.hip
 ContentLossDiscriminator <- reference loss.py:231-289, in disc_loss.py (re-exported here)
+
+The four pixel-space criteria speak one term protocol (_Term): stand-alone they run under one autograd node
+(_TermFn), summed under another (_CriterionSumFn, with the fused pixel + structure-tensor pair _StPixelPair as one more term), and
+each of their library entries is launched from one place.
 """
 from __future__ import annotations
 
@@ -15,53 +20,65 @@ import os
 import torch
 from torch import nn
 
-from . import _abi
+from . import _abi, ops
 
 
-def _st_workspace(x, gt, ws):
-    """Checks a structure-tensor input pair and (re)builds the kernels' partials / last-arriver counter in the criterion's cache `ws`
-    when device or shape changed -> the workspace size in floats."""
-    if x.dtype != torch.float32 or gt.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.shape != gt.shape:
-        raise _abi.HipPathError(f"StructureTensorLoss: expected fp32 [B,3,H,W] pairs, got {tuple(x.shape)} / {tuple(gt.shape)}")
-    B, _, H, W = x.shape
-    n = ctypes.c_int64()
-    _abi.check(_abi.lib().sst_st_loss_workspace(B, H, W, ctypes.byref(n)), "sst_st_loss_workspace")
-    key = (x.device, B, H, W)
-    if ws.get("key") != key:
-        ws["key"] = key
-        ws["partials"] = torch.empty(n.value, device=x.device, dtype=torch.float32)
-        ws["counter"] = torch.zeros(1, device=x.device, dtype=torch.int32)
-    return n.value
+def _check_pair(who, x, gt, image=True, gt_too=True, on_device=False):
+    """The input check of the criteria: an fp32 pair of equal shape; image: [B,3,H,W]; gt_too: gt's dtype counts as well as sr's;
+    on_device: both are tensors on one ROCm device, and what is wrong with either is named."""
+    if on_device:
+        for name, t in (("sr", x), ("gt", gt)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise _abi.HipPathError(f"{who}: {name} must be a tensor on a ROCm device (no CPU fallback)")
+            if t.dtype != torch.float32:
+                raise _abi.HipPathError(f"{who}: {name} must be fp32, got {t.dtype}")
+    bad = x.dtype != torch.float32 or (gt_too and gt.dtype != torch.float32) or x.shape != gt.shape
+    if bad or (image and (x.dim() != 4 or x.shape[1] != 3)) or (on_device and x.device != gt.device):
+        raise _abi.HipPathError(f"{who}: expected fp32 {'[B,3,H,W] pairs' if image else 'tensors of equal shape'}"
+                                f"{' on one device' if on_device else ''}, got {tuple(x.shape)} / {tuple(gt.shape)}")
 
 
-class _StLossFn(torch.autograd.Function):
+class _Term(nn.Module):
+    """A pixel-space criterion of (sr, gt) as the autograd nodes below drive it - the term protocol:
+
+    _route()                      host only, before anything is launched: which kernels will run (None where there is one route)
+    _check(sr, gt)                refuses a pair the kernels do not take (HipPathError); launches and allocates nothing
+    _fwd(sr, gt, want_grad, route) -> (raw 0-dim loss, saved): sr, gt contiguous; `saved` is whatever _bwd needs besides sr and gt
+                                  and belongs to the call; the reduction workspace lives in self._ws and belongs to the criterion
+    _bwd(sr, gt, saved, dsr, g, scale_host, accumulate)   dsr (+)= scale_host * g[0] * d raw / d sr; dsr is the caller's buffer,
+                                  g a device scalar"""
+
+    def __init__(self):
+        super().__init__()
+        self._ws = {}
+
+    def _route(self):
+        return None
+
+    def forward(self, x, gt):
+        want_grad = torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad
+        return _TermFn.apply(x, gt, self, want_grad)
+
+
+class _TermFn(torch.autograd.Function):
+    """One _Term stand-alone."""
+
     @staticmethod
-    def forward(ctx, x, gt, sigma, rho, normalize, ws):
-        from . import ops
-        _st_workspace(x, gt, ws)
-        x = x.contiguous()
-        gt = gt.contiguous()
-        B, _, H, W = x.shape
-        gS = torch.empty_like(x)
-        loss = torch.empty((), device=x.device, dtype=torch.float32)
-        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(gS), _abi.ptr(ws["partials"]), _abi.ptr(ws["counter"]), B, H, W,
-                sigma, rho, int(normalize))
-        # algorithmic bytes (SURVEY 8d): forward reads sr + gt, backward writes d(sr): 3 x 3*H*W*4 B per image in all
-        ops._launch_hbm(_abi.lib().sst_st_loss_fwd, args, "sst_st_loss_fwd", "st_loss_fwd_kernel", 2.0 * x.numel() * 4, (x, gt, loss, gS, ws))
-        ctx.save_for_backward(x, gS)
-        ctx.cfg = (sigma, rho)
+    def forward(ctx, x, gt, term, want_grad):
+        route = term._route()
+        term._check(x, gt)
+        x, gt = x.contiguous(), gt.contiguous()
+        loss, ctx.kept = term._fwd(x, gt, want_grad, route)
+        ctx.term = term
+        ctx.save_for_backward(x, gt)
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
-        x, gS = ctx.saved_tensors
-        sigma, rho = ctx.cfg
-        B, _, H, W = x.shape
+        x, gt = ctx.saved_tensors
         dx = torch.empty_like(x)
-        g = grad_out.contiguous().to(torch.float32)
-        _abi.check(_abi.lib().sst_st_loss_bwd(_abi.ptr(x), _abi.ptr(gS), _abi.ptr(dx), _abi.ptr(g), 1.0, 0, B, H, W,
-                                              sigma, rho, _abi.stream_ptr()), "sst_st_loss_bwd")
-        return dx, None, None, None, None, None
+        ctx.term._bwd(x, gt, ctx.kept, dx, grad_out.contiguous().to(torch.float32), 1.0, False)
+        return dx, None, None, None
 
 
 # Dev switch (tests and timing only): send the two built radius pairs down the general path of csrc/st_general.hip as well.
@@ -79,74 +96,7 @@ def st_route(sigma, rho, what="StructureTensorLoss"):
     return bool(rc) or ST_FORCE_GENERAL, (r1.value, r2.value)
 
 
-def _st_general_workspace(x, gt, radii, ws):
-    """The general path's counterpart of _st_workspace: scratch planes, partials and counter in the criterion's cache `ws`, keyed by
-    device, shape and radii (a warm-up call allocates them before a graph capture) -> floats of the per-call saved planes."""
-    if x.dtype != torch.float32 or gt.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or x.shape != gt.shape:
-        raise _abi.HipPathError(f"StructureTensorLoss: expected fp32 [B,3,H,W] pairs, got {tuple(x.shape)} / {tuple(gt.shape)}")
-    B, _, H, W = x.shape
-    scratch, saved, partials = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-    _abi.check(_abi.lib().sst_st_general_workspace(B, H, W, ctypes.byref(scratch), ctypes.byref(saved), ctypes.byref(partials)),
-               "sst_st_general_workspace")
-    key = (x.device, B, H, W, radii)
-    if ws.get("general_key") != key:
-        ws["general_key"] = key
-        ws["general_scratch"] = torch.empty(scratch.value, device=x.device, dtype=torch.float32)
-        ws["general_partials"] = torch.empty(partials.value, device=x.device, dtype=torch.float32)
-        ws["general_counter"] = torch.zeros(1, device=x.device, dtype=torch.int32)
-    return saved.value
-
-
-def _st_general_fwd(x, gt, sigma, rho, normalize, ws, radii):
-    """The general path's forward -> (loss, gS, saved planes, scratch).  gS and the saved planes (Ix, Iy of sr) belong to the call,
-    like gS on the tile path; the scratch planes are the criterion's and only live inside one entry point."""
-    from . import ops
-    n_saved = _st_general_workspace(x, gt, radii, ws)
-    x = x.contiguous()
-    gt = gt.contiguous()
-    B, _, H, W = x.shape
-    gS = torch.empty_like(x)
-    saved = torch.empty(n_saved, device=x.device, dtype=torch.float32)
-    loss = torch.empty((), device=x.device, dtype=torch.float32)
-    scratch = ws["general_scratch"]
-    args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(gS), _abi.ptr(saved), _abi.ptr(scratch), _abi.ptr(ws["general_partials"]),
-            _abi.ptr(ws["general_counter"]), B, H, W, sigma, rho, int(normalize))
-    # algorithmic bytes as on the tile path: the forward reads sr + gt (the planes in between are this path's own traffic)
-    ops._launch_hbm(_abi.lib().sst_st_general_fwd, args, "sst_st_general_fwd", "stg_loss_fwd_kernel", 2.0 * x.numel() * 4,
-                    (x, gt, loss, gS, saved, ws))
-    return loss, gS, saved, scratch
-
-
-def _st_general_bwd(gS, saved, scratch, dsr, g, scale_host, accumulate, sigma, rho):
-    """dsr (+)= scale_host * g[0] * d loss / d sr on the general path."""
-    from . import ops
-    B, _, H, W = gS.shape
-    bargs = (_abi.ptr(saved), _abi.ptr(gS), _abi.ptr(dsr), _abi.ptr(scratch), _abi.ptr(g), float(scale_host), int(accumulate), B, H, W,
-             sigma, rho)
-    ops._launch_hbm(_abi.lib().sst_st_general_bwd, bargs, "sst_st_general_bwd", "stg_hadj_out_kernel", 1.0 * gS.numel() * 4,
-                    (saved, gS, dsr, scratch, g))
-
-
-class _StGeneralFn(torch.autograd.Function):
-    """_StLossFn on the general path."""
-
-    @staticmethod
-    def forward(ctx, x, gt, sigma, rho, normalize, ws, radii):
-        loss, gS, saved, scratch = _st_general_fwd(x, gt, sigma, rho, normalize, ws, radii)
-        ctx.save_for_backward(gS, saved)
-        ctx.cfg = (sigma, rho, scratch)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        gS, saved = ctx.saved_tensors
-        sigma, rho, scratch = ctx.cfg
-        dx = torch.empty_like(gS)
-        _st_general_bwd(gS, saved, scratch, dx, grad_out.contiguous().to(torch.float32), 1.0, False, sigma, rho)
-        return dx, None, None, None, None, None, None
-
-
-class StructureTensorLoss(nn.Module):
+class StructureTensorLoss(_Term):
     """Same constructor and call protocol as reference loss.py:380-413.  Any (sigma, rho) whose radii max(int(4 s + 0.5), 1) are at
     most 8 (sigma) and 20 (rho), i.e. sigma up to about 2.1 and rho up to about 5.1: the pairs with radii (2, 8) and (4, 10) run the
     32 x 32-tile kernels (csrc/st_loss.hip), every other pair the separable path (csrc/st_general.hip); beyond the bound HipPathError."""
@@ -156,13 +106,62 @@ class StructureTensorLoss(nn.Module):
         self.sigma = sigma
         self.rho = rho
         self.normalize = normalize
-        self._ws = {}
 
-    def forward(self, x, gt):
-        general, radii = st_route(self.sigma, self.rho)
-        if general:
-            return _StGeneralFn.apply(x, gt, float(self.sigma), float(self.rho), bool(self.normalize), self._ws, radii)
-        return _StLossFn.apply(x, gt, float(self.sigma), float(self.rho), bool(self.normalize), self._ws)
+    def _route(self):
+        return st_route(self.sigma, self.rho)
+
+    def _check(self, x, gt):
+        _check_pair("StructureTensorLoss", x, gt)
+
+    def _tile_ws(self, x):
+        """The tile kernels' partials / last-arriver counter, keyed by device and shape -> (floats of the partials, partials, counter)."""
+        B, _, H, W = x.shape
+        n = ctypes.c_int64()
+        _abi.check(_abi.lib().sst_st_loss_workspace(B, H, W, ctypes.byref(n)), "sst_st_loss_workspace")
+        return (n.value, *ops.reduction_ws(self._ws, (x.device, B, H, W), n.value))
+
+    def _fwd(self, x, gt, want_grad, route):
+        """gS = d(per-pixel distance) / d(structure tensor of sr) is written either way: it belongs to the call, and with what
+        else is saved it says which route ran.  Algorithmic bytes: forward reads sr + gt, backward writes d(sr) -
+        3 x 3*H*W*4 B per image in all (the planes in between are the general path's own traffic)."""
+        general, radii = route
+        B, _, H, W = x.shape
+        cfg, ws = (float(self.sigma), float(self.rho)), self._ws
+        gS = torch.empty_like(x)
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        if not general:
+            _, partials, counter = self._tile_ws(x)
+            args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(gS), _abi.ptr(partials), _abi.ptr(counter), B, H, W, *cfg,
+                    int(bool(self.normalize)))
+            ops._launch_hbm(_abi.lib().sst_st_loss_fwd, args, "sst_st_loss_fwd", "st_loss_fwd_kernel", 2.0 * x.numel() * 4, (x, gt, loss, gS, ws))
+            return loss, (cfg, gS)
+        # general route: scratch planes next to partials and counter, keyed by the radii as well (a warm-up call allocates them before
+        # a graph capture); they only live inside one entry point.  The saved planes (Ix, Iy of sr) belong to the call, like gS.
+        n_scratch, n_saved, n_part = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _abi.check(_abi.lib().sst_st_general_workspace(B, H, W, ctypes.byref(n_scratch), ctypes.byref(n_saved), ctypes.byref(n_part)),
+                   "sst_st_general_workspace")
+        key = (x.device, B, H, W, radii)
+        if ws.get("general_key") != key:
+            ws["general_scratch"] = torch.empty(n_scratch.value, device=x.device, dtype=torch.float32)
+        partials, counter = ops.reduction_ws(ws, key, n_part.value, "general_")
+        planes, scratch = torch.empty(n_saved.value, device=x.device, dtype=torch.float32), ws["general_scratch"]
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(gS), _abi.ptr(planes), _abi.ptr(scratch), _abi.ptr(partials),
+                _abi.ptr(counter), B, H, W, *cfg, int(bool(self.normalize)))
+        ops._launch_hbm(_abi.lib().sst_st_general_fwd, args, "sst_st_general_fwd", "stg_loss_fwd_kernel", 2.0 * x.numel() * 4,
+                        (x, gt, loss, gS, planes, ws))
+        return loss, (cfg, gS, planes, scratch)
+
+    def _bwd(self, x, gt, saved, dsr, g, scale_host, accumulate):
+        cfg, gS, *general = saved                       # what the forward kept says which route it took
+        B, _, H, W = x.shape
+        if not general:
+            args = (_abi.ptr(x), _abi.ptr(gS), _abi.ptr(dsr), _abi.ptr(g), float(scale_host), int(accumulate), B, H, W, *cfg)
+            ops._launch_hbm(_abi.lib().sst_st_loss_bwd, args, "sst_st_loss_bwd", "st_loss_bwd_kernel", 1.0 * x.numel() * 4, (x, gS, dsr, g))
+            return
+        planes, scratch = general
+        args = (_abi.ptr(planes), _abi.ptr(gS), _abi.ptr(dsr), _abi.ptr(scratch), _abi.ptr(g), float(scale_host), int(accumulate), B, H, W, *cfg)
+        ops._launch_hbm(_abi.lib().sst_st_general_bwd, args, "sst_st_general_bwd", "stg_hadj_out_kernel", 1.0 * x.numel() * 4,
+                        (planes, gS, dsr, scratch, g))
 
     def __repr__(self):
         return f"StructureTensorLoss(sigma={self.sigma}, rho={self.rho}, normalize={self.normalize})"
@@ -172,68 +171,7 @@ class StructureTensorLoss(nn.Module):
 SSIM_MIN_SIDE = 11        # the 11-tap window's valid region is empty below it
 
 
-def _ssim_workspace(x, gt, planes, ws):
-    """Checks an SSIM input pair and (re)builds the forward's partials / last-arriver counter in the criterion's cache `ws` when
-    device, shape or plane count changed -> floats of the per-call gradient maps."""
-    for name, t in (("sr", x), ("gt", gt)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise _abi.HipPathError(f"SSIMLoss: {name} must be a tensor on a ROCm device (no CPU fallback)")
-        if t.dtype != torch.float32:
-            raise _abi.HipPathError(f"SSIMLoss: {name} must be fp32, got {t.dtype}")
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape != gt.shape or x.device != gt.device:
-        raise _abi.HipPathError(f"SSIMLoss: expected fp32 [B,3,H,W] pairs on one device, got {tuple(x.shape)} / {tuple(gt.shape)}")
-    B, _, H, W = x.shape
-    if B < 1 or H < SSIM_MIN_SIDE or W < SSIM_MIN_SIDE:
-        raise _abi.HipPathError(f"SSIMLoss: images of {W}x{H} are below the {SSIM_MIN_SIDE}-px minimum of the SSIM window")
-    n_maps, n_part = ctypes.c_int64(), ctypes.c_int64()
-    _abi.check(_abi.lib().sst_ssim_loss_workspace(B, H, W, planes, ctypes.byref(n_maps), ctypes.byref(n_part)), "sst_ssim_loss_workspace")
-    key = (x.device, B, H, W, planes)
-    if ws.get("key") != key:
-        ws["key"] = key
-        ws["partials"] = torch.empty(n_part.value, device=x.device, dtype=torch.float32)
-        ws["counter"] = torch.zeros(1, device=x.device, dtype=torch.int32)
-    return n_maps.value
-
-
-class _SsimLossFn(torch.autograd.Function):
-    """1 - mean SSIM (csrc/ssim_loss.hip).  want_grad False (no_grad, or sr does not require grad): the gradient maps are neither
-    allocated nor written."""
-
-    @staticmethod
-    def forward(ctx, x, gt, planes, k1, k2, ws, want_grad):
-        from . import ops
-        n_maps = _ssim_workspace(x, gt, planes, ws)
-        x = x.contiguous()
-        gt = gt.contiguous()
-        B, _, H, W = x.shape
-        maps = torch.empty(n_maps, device=x.device, dtype=torch.float32) if want_grad else None
-        loss = torch.empty((), device=x.device, dtype=torch.float32)
-        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(maps), _abi.ptr(ws["partials"]), _abi.ptr(ws["counter"]), B, H, W,
-                planes, k1, k2)
-        # algorithmic bytes: the forward reads sr + gt, the backward writes d(sr)
-        ops._launch_hbm(_abi.lib().sst_ssim_loss_fwd, args, "sst_ssim_loss_fwd", "ssim_loss_fwd_kernel", 2.0 * x.numel() * 4,
-                        (x, gt, loss, maps, ws))
-        ctx.planes = planes
-        if want_grad:
-            ctx.save_for_backward(x, gt, maps)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        from . import ops
-        if not ctx.saved_tensors:
-            raise _abi.HipPathError("SSIMLoss: the gradient is taken with respect to sr only (gt is a constant)")
-        x, gt, maps = ctx.saved_tensors
-        B, _, H, W = x.shape
-        dx = torch.empty_like(x)
-        g = grad_out.contiguous().to(torch.float32)
-        bargs = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(maps), _abi.ptr(dx), _abi.ptr(g), 1.0, 0, B, H, W, ctx.planes)
-        ops._launch_hbm(_abi.lib().sst_ssim_loss_bwd, bargs, "sst_ssim_loss_bwd", "ssim_loss_bwd_kernel", 1.0 * x.numel() * 4,
-                        (x, gt, maps, dx, g))
-        return dx, None, None, None, None, None, None
-
-
-class SSIMLoss(nn.Module):
+class SSIMLoss(_Term):
     """1 - mean SSIM(sr, gt): the 11-tap sigma 1.5 Gaussian window over its valid region, C1 = k1^2, C2 = k2^2 for images on the
     0..1 scale - the SSIM validate reports (csrc/metrics.hip) as a criterion, without the uint8 quantisation and the clamp.
     channel "y": one luma plane (65.481 R + 128.553 G + 24.966 B + 16) / 255; "rgb": the mean over the three planes.  fp32
@@ -247,76 +185,99 @@ class SSIMLoss(nn.Module):
             if not (isinstance(k, (int, float)) and 0.0 < float(k) < float("inf")):
                 raise ValueError(f"SSIMLoss: {name} must be a positive number, got {k!r}")
         self.channel, self.k1, self.k2 = channel, float(k1), float(k2)
-        self._ws = {}
 
-    def forward(self, x, gt):
-        want_grad = torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad
-        return _SsimLossFn.apply(x, gt, 1 if self.channel == "y" else 3, self.k1, self.k2, self._ws, want_grad)
+    def _check(self, x, gt):
+        _check_pair("SSIMLoss", x, gt, on_device=True)
+        B, _, H, W = x.shape
+        if B < 1 or H < SSIM_MIN_SIDE or W < SSIM_MIN_SIDE:
+            raise _abi.HipPathError(f"SSIMLoss: images of {W}x{H} are below the {SSIM_MIN_SIDE}-px minimum of the SSIM window")
+
+    def _fwd(self, x, gt, want_grad, route):
+        """want_grad False (no_grad, or sr does not require grad): the gradient maps are neither allocated nor written."""
+        B, _, H, W = x.shape
+        planes = 1 if self.channel == "y" else 3
+        n_maps, n_part = ctypes.c_int64(), ctypes.c_int64()
+        _abi.check(_abi.lib().sst_ssim_loss_workspace(B, H, W, planes, ctypes.byref(n_maps), ctypes.byref(n_part)), "sst_ssim_loss_workspace")
+        partials, counter = ops.reduction_ws(self._ws, (x.device, B, H, W, planes), n_part.value)
+        maps = torch.empty(n_maps.value, device=x.device, dtype=torch.float32) if want_grad else None
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(maps), _abi.ptr(partials), _abi.ptr(counter), B, H, W, planes, self.k1, self.k2)
+        # algorithmic bytes: the forward reads sr + gt, the backward writes d(sr)
+        ops._launch_hbm(_abi.lib().sst_ssim_loss_fwd, args, "sst_ssim_loss_fwd", "ssim_loss_fwd_kernel", 2.0 * x.numel() * 4,
+                        (x, gt, loss, maps, self._ws))
+        return loss, (planes, maps) if want_grad else None
+
+    def _bwd(self, x, gt, saved, dsr, g, scale_host, accumulate):
+        if saved is None:
+            raise _abi.HipPathError("SSIMLoss: the gradient is taken with respect to sr only (gt is a constant)")
+        planes, maps = saved
+        B, _, H, W = x.shape
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(maps), _abi.ptr(dsr), _abi.ptr(g), float(scale_host), int(accumulate), B, H, W, planes)
+        ops._launch_hbm(_abi.lib().sst_ssim_loss_bwd, args, "sst_ssim_loss_bwd", "ssim_loss_bwd_kernel", 1.0 * x.numel() * 4,
+                        (x, gt, maps, dsr, g))
 
     def __repr__(self):
         return f"SSIMLoss(channel={self.channel!r}, k1={self.k1}, k2={self.k2})"
 
 
 # ------------------------------------------------------------------------------------------------
-class _PixelLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, gt, mode, ws):
-        from . import ops
-        if x.shape != gt.shape or x.dtype != torch.float32:
-            raise _abi.HipPathError("pixel loss: fp32 tensors of equal shape")
-        x, gt = x.contiguous(), gt.contiguous()
-        ctx.save_for_backward(x, gt)
-        ctx.mode = mode
-        return ops.pixel_loss_fwd(x, gt, mode, ws)
+class _PixelLoss(_Term):
+    mode = None               # sst_pixel_loss_*: 0 MSE, 1 L1
 
-    @staticmethod
-    def backward(ctx, grad_out):
-        from . import ops
-        x, gt = ctx.saved_tensors
-        return ops.pixel_loss_bwd(x, gt, ctx.mode, scale_dev=grad_out.contiguous()), None, None, None
+    def _check(self, x, gt):
+        _check_pair("pixel loss", x, gt, image=False, gt_too=False)
+
+    def _fwd(self, x, gt, want_grad, route):
+        return ops.pixel_loss_fwd(x, gt, self.mode, self._ws), None
+
+    def _bwd(self, x, gt, saved, dsr, g, scale_host, accumulate):
+        ops.pixel_loss_bwd(x, gt, self.mode, scale_dev=g, scale_host=scale_host, out=dsr, accumulate=accumulate)
 
 
-class MSELoss(nn.Module):
+class MSELoss(_PixelLoss):
     """nn.MSELoss() of reference config.py:88-90 on the HIP path."""
-
-    def __init__(self):
-        super().__init__()
-        self._ws = {}
-
-    def forward(self, x, gt):
-        return _PixelLossFn.apply(x, gt, 0, self._ws)
+    mode = 0
 
 
-class L1Loss(nn.Module):
+class L1Loss(_PixelLoss):
     """Pixel-L1 variant named by BASELINE.json configs[0] (one-line config change in the reference)."""
-
-    def __init__(self):
-        super().__init__()
-        self._ws = {}
-
-    def forward(self, x, gt):
-        return _PixelLossFn.apply(x, gt, 1, self._ws)
+    mode = 1
 
 
 # ------------------------------------------------------------------------------------------------
 FUSE_PIXEL_INTO_ST = os.environ.get("SST_FUSE_PIXEL_ST", "1") != "0"
 
 
-def _st_pixel_fwd(x, gt, sigma, rho, normalize, ws, mode):
-    """Structure-tensor loss and pixel criterion (mode 0 MSE / 1 L1) of (x, gt) in one launch -> (st_loss, pixel_loss, gS)."""
-    from . import ops
-    n = _st_workspace(x, gt, ws)
-    B, _, H, W = x.shape
-    if ws.get("pix_partials") is None or ws["pix_partials"].numel() != n or ws["pix_partials"].device != x.device:
-        ws["pix_partials"] = torch.empty(n, device=x.device, dtype=torch.float32)
-    gS = torch.empty_like(x)
-    loss = torch.empty((), device=x.device, dtype=torch.float32)
-    pix = torch.empty((), device=x.device, dtype=torch.float32)
-    args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(gS), _abi.ptr(ws["partials"]), _abi.ptr(ws["counter"]), _abi.ptr(pix),
-            _abi.ptr(ws["pix_partials"]), int(mode), B, H, W, sigma, rho, int(normalize))
-    ops._launch_hbm(_abi.lib().sst_st_pixel_loss_fwd, args, "sst_st_pixel_loss_fwd", "st_loss_fwd_kernel", 2.0 * x.numel() * 4,
-                    (x, gt, loss, gS, ws, pix))
-    return loss, pix, gS
+class _StPixelPair:
+    """A tile-route StructureTensorLoss and a pixel criterion as one term: the pixel criterion rides along in the structure-tensor
+    kernels - same reads of sr / gt, two launches less per step (forward and backward).  Two raw values, two host scales; the
+    workspace is the structure-tensor term's."""
+
+    def __init__(self, st, pixel):
+        self.st, self.pixel = st, pixel
+
+    def _fwd(self, x, gt, want_grad, route):
+        st, ws = self.st, self.st._ws
+        B, _, H, W = x.shape
+        cfg = (float(st.sigma), float(st.rho))
+        n, partials, counter = st._tile_ws(x)
+        pix_partials, _ = ops.reduction_ws(ws, (x.device, n), n, "pix_")
+        gS = torch.empty_like(x)
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        pix = torch.empty((), device=x.device, dtype=torch.float32)
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(gS), _abi.ptr(partials), _abi.ptr(counter), _abi.ptr(pix),
+                _abi.ptr(pix_partials), self.pixel.mode, B, H, W, *cfg, int(bool(st.normalize)))
+        ops._launch_hbm(_abi.lib().sst_st_pixel_loss_fwd, args, "sst_st_pixel_loss_fwd", "st_loss_fwd_kernel", 2.0 * x.numel() * 4,
+                        (x, gt, loss, gS, ws, pix))
+        return (loss, pix), (cfg, gS)
+
+    def _bwd(self, x, gt, saved, dsr, g, scale_host, accumulate):
+        cfg, gS = saved
+        B, _, H, W = x.shape
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(gS), _abi.ptr(dsr), _abi.ptr(g), float(scale_host[0]), float(scale_host[1]),
+                self.pixel.mode, int(accumulate), B, H, W, *cfg)
+        ops._launch_hbm(_abi.lib().sst_st_pixel_loss_bwd, args, "sst_st_pixel_loss_bwd", "st_loss_bwd_kernel", 1.0 * x.numel() * 4,
+                        (x, gt, gS, dsr, g))
 
 
 class _CriterionSumFn(torch.autograd.Function):
@@ -325,49 +286,28 @@ class _CriterionSumFn(torch.autograd.Function):
     weight folded into their scale - no per-term mul / add launches (reference train.py:129-140 / warmup.py:79-86 loop)."""
 
     @staticmethod
-    def forward(ctx, sr, gt, terms, weights, ws):
-        from . import ops
-        if sr.dtype != torch.float32 or sr.shape != gt.shape:
-            raise _abi.HipPathError("criterion sum: fp32 tensors of equal shape")
+    def forward(ctx, sr, gt, terms, weights):
+        _check_pair("criterion sum", sr, gt, image=False, gt_too=False)
         sr, gt = sr.contiguous(), gt.contiguous()
-        lib = _abi.lib()
-        raw, saved = [], []
-        # one structure-tensor term + one pixel term (the step's usual pair): the pixel criterion rides along in the structure-tensor
-        # kernels - same reads of sr / gt, two launches less per step (forward and backward)
-        st_i = [i for i, t in enumerate(terms) if isinstance(t, StructureTensorLoss)]
-        px_i = [i for i, t in enumerate(terms) if isinstance(t, (MSELoss, L1Loss))]
-        ctx.fused_pair = None
-        # (the fused kernels are the tile builds': a structure-tensor term on the general route runs unfused, below)
-        routes = [st_route(t.sigma, t.rho) if isinstance(t, StructureTensorLoss) else None for t in terms]
-        if (FUSE_PIXEL_INTO_ST and len(st_i) == 1 and len(px_i) == 1 and sr.dim() == 4 and sr.shape[1] == 3
-                and not routes[st_i[0]][0]):
-            t = terms[st_i[0]]
-            mode = 0 if isinstance(terms[px_i[0]], MSELoss) else 1
-            st_loss, pix_loss, gS = _st_pixel_fwd(sr, gt, float(t.sigma), float(t.rho), bool(t.normalize), t._ws, mode)
-            raw, saved = [None] * len(terms), [None] * len(terms)
-            raw[st_i[0]], raw[px_i[0]], saved[st_i[0]] = st_loss, pix_loss, gS
-            ctx.fused_pair = (st_i[0], px_i[0], mode)
-            for i, t2 in enumerate(terms):
-                if raw[i] is None:
-                    raise _abi.HipPathError("criterion sum: unexpected term next to the fused pixel + structure-tensor pair")
-        else:
-            for i, t in enumerate(terms):
-                if isinstance(t, StructureTensorLoss) and routes[i][0]:
-                    st_loss, *kept = _st_general_fwd(sr, gt, float(t.sigma), float(t.rho), bool(t.normalize), t._ws, routes[i][1])
-                    raw.append(st_loss)
-                    saved.append(tuple(kept))
-                elif isinstance(t, StructureTensorLoss):
-                    raw.append(_StLossFn.forward(_Ctx(saved), sr, gt, float(t.sigma), float(t.rho), bool(t.normalize), t._ws))
-                else:
-                    raw.append(ops.pixel_loss_fwd(sr, gt, 0 if isinstance(t, MSELoss) else 1, t._ws))
-                    saved.append(None)
-        n = len(terms)
-        total = torch.empty((), device=sr.device, dtype=torch.float32)
-        weighted = torch.empty(n, device=sr.device, dtype=torch.float32)
-        ptrs = (ctypes.c_void_p * n)(*[_abi.ptr(r) for r in raw])
-        wts = (ctypes.c_float * n)(*[float(w) for w in weights])
-        _abi.check(lib.sst_weighted_sum(ptrs, wts, n, _abi.ptr(total), _abi.ptr(weighted), _abi.stream_ptr()), "sst_weighted_sum")
-        ctx.terms, ctx.weights, ctx.gS = terms, [float(w) for w in weights], saved
+        routes = [t._route() for t in terms]            # every host-side decision and refusal comes before the first launch
+        for t in terms:
+            t._check(sr, gt)
+        steps = [(t, (i,)) for i, t in enumerate(terms)]                   # (what runs, the terms it computes)
+        # one structure-tensor term on the tile route + one pixel term (the step's usual pair) run as _StPixelPair (the fused
+        # kernels are the tile builds': a structure-tensor term on the general route runs unfused)
+        st = [i for i, t in enumerate(terms) if isinstance(t, StructureTensorLoss)]
+        px = [i for i, t in enumerate(terms) if isinstance(t, _PixelLoss)]
+        if FUSE_PIXEL_INTO_ST and len(st) == 1 and len(px) == 1 and not routes[st[0]][0]:
+            pair = (st[0], px[0])
+            steps = [(_StPixelPair(terms[st[0]], terms[px[0]]), pair)] + [s for s in steps if s[1][0] not in pair]
+        raw, kept = [None] * len(terms), []
+        for op, idx in steps:
+            out, k = op._fwd(sr, gt, True, routes[idx[0]])
+            kept.append(k)
+            for i, r in zip(idx, out if len(idx) > 1 else (out,)):
+                raw[i] = r
+        total, weighted = ops.weighted_sum(raw, weights, True)
+        ctx.steps, ctx.kept, ctx.weights = steps, kept, [float(w) for w in weights]
         ctx.save_for_backward(sr, gt)
         ctx.mark_non_differentiable(weighted)
         ctx.set_materialize_grads(False)                 # no zeros kernel for the gradient slot of `weighted`
@@ -375,48 +315,24 @@ class _CriterionSumFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_total, _grad_weighted):
-        from . import ops
         sr, gt = ctx.saved_tensors
         g = grad_total.contiguous().to(torch.float32)
-        B, _, H, W = sr.shape
         dsr = torch.empty_like(sr)
-        if ctx.fused_pair is not None:
-            si, pi, mode = ctx.fused_pair
-            t = ctx.terms[si]
-            bargs = (_abi.ptr(sr), _abi.ptr(gt), _abi.ptr(ctx.gS[si]), _abi.ptr(dsr), _abi.ptr(g), ctx.weights[si], ctx.weights[pi], mode, 0,
-                     B, H, W, float(t.sigma), float(t.rho))
-            ops._launch_hbm(_abi.lib().sst_st_pixel_loss_bwd, bargs, "sst_st_pixel_loss_bwd", "st_loss_bwd_kernel", 1.0 * sr.numel() * 4,
-                            (sr, gt, ctx.gS[si], dsr, g))
-            return dsr, None, None, None, None
-        for i, (t, w) in enumerate(zip(ctx.terms, ctx.weights)):
-            if isinstance(t, StructureTensorLoss) and isinstance(ctx.gS[i], tuple):       # general route: (gS, saved planes, scratch)
-                _st_general_bwd(*ctx.gS[i], dsr, g, w, i > 0, float(t.sigma), float(t.rho))
-            elif isinstance(t, StructureTensorLoss):
-                bargs = (_abi.ptr(sr), _abi.ptr(ctx.gS[i]), _abi.ptr(dsr), _abi.ptr(g), w, int(i > 0), B, H, W, float(t.sigma), float(t.rho))
-                ops._launch_hbm(_abi.lib().sst_st_loss_bwd, bargs, "sst_st_loss_bwd", "st_loss_bwd_kernel", 1.0 * sr.numel() * 4,
-                                (sr, ctx.gS[i], dsr, g))
-            else:
-                ops.pixel_loss_bwd(sr, gt, 0 if isinstance(t, MSELoss) else 1, scale_dev=g, scale_host=w, out=dsr, accumulate=i > 0)
-        return dsr, None, None, None, None
-
-
-class _Ctx:
-    """Stand-in for an autograd ctx when a Function's forward is re-used inside another node: keeps the gS tensor."""
-
-    def __init__(self, saved):
-        self._saved = saved
-
-    def save_for_backward(self, x, gS):
-        self._saved.append(gS)
+        for n, ((op, idx), k) in enumerate(zip(ctx.steps, ctx.kept)):
+            w = [ctx.weights[i] for i in idx]
+            op._bwd(sr, gt, k, dsr, g, w if len(idx) > 1 else w[0], n > 0)
+        return dsr, None, None, None
 
 
 def fusable(criterion) -> bool:
+    """Whether engine._criterion_total hands the criterion to criterion_sum.  SSIMLoss speaks the term protocol but stays outside:
+    taking it in changes the launches of a step with an SSIM term."""
     return isinstance(criterion, (MSELoss, L1Loss, StructureTensorLoss))
 
 
-def criterion_sum(sr, gt, terms, weights, ws=None):
+def criterion_sum(sr, gt, terms, weights):
     """-> (total, weighted values [len(terms)]) for fusable() criterions of (sr, gt)."""
-    return _CriterionSumFn.apply(sr, gt, list(terms), list(weights), ws)
+    return _CriterionSumFn.apply(sr, gt, list(terms), list(weights))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -441,6 +357,26 @@ def _torch_bicubic_taps(in_size: int, out_size: int, device, scale=None):
     return w.contiguous().to(device), idx.contiguous().to(device)
 
 
+def _gt_pyramid(gt, cache, nps, extract):
+    """The candidate side of the patch losses: extract(image, h, w, offset) on GT at full resolution, then on GT at 1/2 and 1/4
+    resolution (F.interpolate(scale_factor=0.5 / 0.25, mode='bicubic'): floor sizes, coordinates mapped with the factor), the offset
+    running by nps = patches per level.  The tap tables are cached in `cache` per (device, H, W)."""
+    B, _, H, W = gt.shape
+    key = (gt.device, H, W)
+    if cache.get("key") != key:
+        cache["key"] = key
+        cache["taps"] = [(_torch_bicubic_taps(H, H // s, gt.device, s), _torch_bicubic_taps(W, W // s, gt.device, s)) for s in (2, 4)]
+    extract(gt, H, W, 0)
+    off = nps[0]
+    for k, s in enumerate((2, 4)):
+        (wy, iy), (wx, ix) = cache["taps"][k]
+        small = torch.empty(B, 3, H // s, W // s, device=gt.device, dtype=torch.float32)
+        _abi.check(_abi.lib().sst_bicubic(_abi.ptr(gt), _abi.ptr(small), _abi.ptr(wy), _abi.ptr(iy), _abi.ptr(wx), _abi.ptr(ix), B * 3, H, W,
+                                          H // s, W // s, 4, 4, 0, _abi.stream_ptr()), "sst_bicubic")
+        extract(small, H // s, W // s, off)
+        off += nps[k + 1]
+
+
 class _BestBuddyGeneralFn(torch.autograd.Function):
     """BestBuddyLoss with any patch geometry (ksize <= 6, pad, stride; reference loss.py:86,116-134) and either matching distance
     (utils.py:157-191): patch tables in global memory (sst_bbg_unfold), tiled matching (sst_bbg_match), the unfold's adjoint for the
@@ -448,33 +384,19 @@ class _BestBuddyGeneralFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gt, alpha, beta, l2, ksize, pad, stride, dist_l1, cache):
-        if x.dtype != torch.float32 or x.shape != gt.shape or x.dim() != 4 or x.shape[1] != 3:
-            raise _abi.HipPathError("BestBuddyLoss: fp32 [B,3,H,W] pairs")
+        _check_pair("BestBuddyLoss", x, gt, gt_too=False)
         B, _, H, W = x.shape
         x, gt = x.contiguous(), gt.contiguous()
         lib, dev = _abi.lib(), x.device
-        sizes = [(H // s, W // s) for s in (1, 2, 4)]                 # F.interpolate(scale_factor=0.5 / 0.25): floor
-        nps = [lib.sst_bbg_patches(h, w, ksize, pad, stride) for h, w in sizes]
+        nps = [lib.sst_bbg_patches(H // s, W // s, ksize, pad, stride) for s in (1, 2, 4)]
         if min(nps) <= 0:
             raise _abi.HipPathError(f"BestBuddyLoss: a {ksize}x{ksize} patch (pad {pad}) does not fit the 1/4-resolution image")
-        key = (dev, H, W)
-        if cache.get("key") != key:
-            cache["key"] = key
-            cache["taps"] = [(_torch_bicubic_taps(H, H // s, dev, s), _torch_bicubic_taps(W, W // s, dev, s)) for s in (2, 4)]
         D, ncand, np_ = 3 * ksize * ksize, sum(nps), nps[0]
         cand = torch.empty(B, ncand, D, device=dev, dtype=torch.float32)
         cnrm = torch.empty(B, ncand, device=dev, dtype=torch.float32)
         st = _abi.stream_ptr()
-        _abi.check(lib.sst_bbg_unfold(_abi.ptr(gt), _abi.ptr(cand), _abi.ptr(cnrm), B, H, W, ksize, pad, stride, ncand, 0, st), "sst_bbg_unfold")
-        off = nps[0]
-        for k, s in enumerate((2, 4)):
-            (wy, iy), (wx, ix) = cache["taps"][k]
-            small = torch.empty(B, 3, H // s, W // s, device=dev, dtype=torch.float32)
-            _abi.check(lib.sst_bicubic(_abi.ptr(gt), _abi.ptr(small), _abi.ptr(wy), _abi.ptr(iy), _abi.ptr(wx), _abi.ptr(ix), B * 3, H, W,
-                                       H // s, W // s, 4, 4, 0, st), "sst_bicubic")
-            _abi.check(lib.sst_bbg_unfold(_abi.ptr(small), _abi.ptr(cand), _abi.ptr(cnrm), B, H // s, W // s, ksize, pad, stride, ncand, off, st),
-                       "sst_bbg_unfold")
-            off += nps[k + 1]
+        _gt_pyramid(gt, cache, nps, lambda img, h, w, off: _abi.check(
+            lib.sst_bbg_unfold(_abi.ptr(img), _abi.ptr(cand), _abi.ptr(cnrm), B, h, w, ksize, pad, stride, ncand, off, st), "sst_bbg_unfold"))
         srf = torch.empty(B, np_, D, device=dev, dtype=torch.float32)
         _abi.check(lib.sst_bbg_unfold(_abi.ptr(x), _abi.ptr(srf), None, B, H, W, ksize, pad, stride, np_, 0, st), "sst_bbg_unfold")
         ind = torch.empty(B, np_, device=dev, dtype=torch.int32)
@@ -497,32 +419,19 @@ class _BestBuddyGeneralFn(torch.autograd.Function):
 class _BestBuddyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gt, alpha, beta, l2, cache, gram=0, st_mats=None, dist_l1=0):
-        if x.dtype != torch.float32 or x.shape != gt.shape or x.dim() != 4 or x.shape[1] != 3:
-            raise _abi.HipPathError("BestBuddyLoss / GramLoss: fp32 [B,3,H,W] pairs")
+        _check_pair("BestBuddyLoss / GramLoss", x, gt, gt_too=False)
         B, _, H, W = x.shape
         if H % 12 or W % 12:
             raise _abi.HipPathError("BestBuddyLoss: H and W must be multiples of 12 (3x3 patches at scales 1, 1/2, 1/4)")
         x, gt = x.contiguous(), gt.contiguous()
         lib, dev = _abi.lib(), x.device
-        key = (dev, H, W)
-        if cache.get("key") != key:
-            cache["key"] = key
-            cache["taps"] = [(_torch_bicubic_taps(H, H // s, dev), _torch_bicubic_taps(W, W // s, dev)) for s in (2, 4)]
         nps = [(H // s // 3) * (W // s // 3) for s in (1, 2, 4)]
         ncand = sum(nps)
         cand = torch.empty(B, ncand, lib.sst_bb_feature_dim(int(gram)), device=dev, dtype=torch.float32)
         cnrm = torch.empty(B, ncand, device=dev, dtype=torch.float32)
         st = _abi.stream_ptr()
-        _abi.check(lib.sst_bb_patches(_abi.ptr(gt), _abi.ptr(cand), _abi.ptr(cnrm), B, H, W, ncand, 0, int(gram), _abi.ptr(st_mats), st), "sst_bb_patches")
-        off = nps[0]
-        for k, s in enumerate((2, 4)):                       # GT at 1/2 and 1/4 resolution (torch bicubic), then its patches
-            (wy, iy), (wx, ix) = cache["taps"][k]
-            small = torch.empty(B, 3, H // s, W // s, device=dev, dtype=torch.float32)
-            _abi.check(lib.sst_bicubic(_abi.ptr(gt), _abi.ptr(small), _abi.ptr(wy), _abi.ptr(iy), _abi.ptr(wx), _abi.ptr(ix), B * 3, H, W,
-                                       H // s, W // s, 4, 4, 0, st), "sst_bicubic")
-            _abi.check(lib.sst_bb_patches(_abi.ptr(small), _abi.ptr(cand), _abi.ptr(cnrm), B, H // s, W // s, ncand, off, int(gram),
-                                          _abi.ptr(st_mats), st), "sst_bb_patches")
-            off += nps[k + 1]
+        _gt_pyramid(gt, cache, nps, lambda img, h, w, off: _abi.check(
+            lib.sst_bb_patches(_abi.ptr(img), _abi.ptr(cand), _abi.ptr(cnrm), B, h, w, ncand, off, int(gram), _abi.ptr(st_mats), st), "sst_bb_patches"))
         ind = torch.empty(B, nps[0], device=dev, dtype=torch.int32)
         dsr = torch.empty_like(x)
         partials = torch.empty(lib.sst_bb_blocks(B, H, W), device=dev, dtype=torch.float32)
@@ -538,10 +447,13 @@ class _BestBuddyFn(torch.autograd.Function):
         return dsr * grad_out, None, None, None, None, None, None, None, None
 
 
-def _dist_l1(dist_norm: str) -> int:
+def _patch_modes(dist_norm: str, criterion: str, verb: str = "implmented"):
+    """The dist_norm / criterion arguments of the three patch losses -> (dist_l1, l2), refused in the reference's words."""
     if dist_norm not in ("l1", "l2"):
         raise NotImplementedError("%s norm has not been supported." % dist_norm)          # utils.py:189
-    return int(dist_norm == "l1")
+    if criterion not in ("l1", "l2", "mse"):
+        raise NotImplementedError("%s criterion has not been %s." % (criterion, verb))
+    return int(dist_norm == "l1"), criterion != "l1"
 
 
 class BestBuddyLoss(nn.Module):
@@ -554,11 +466,8 @@ class BestBuddyLoss(nn.Module):
         super().__init__()
         if not (1 <= int(ksize) <= 6 and int(pad) >= 0 and int(stride) >= 1):
             raise NotImplementedError("BestBuddyLoss on the HIP path: 1 <= ksize <= 6, pad >= 0, stride >= 1")
-        self._dl1 = _dist_l1(dist_norm)
-        if criterion not in ("l1", "l2", "mse"):
-            raise NotImplementedError("%s criterion has not been implmented." % criterion)
+        self._dl1, self.l2 = _patch_modes(dist_norm, criterion)
         self.alpha, self.beta, self.ksize, self.pad, self.stride, self.dist_norm = alpha, beta, ksize, pad, stride, dist_norm
-        self.l2 = criterion != "l1"
         self._cache = {}
         self.last_index = None          # [B, n_patches] int32: the selected candidate per SR patch (diagnostics / tests)
 
@@ -582,11 +491,8 @@ class GramLoss(nn.Module):
         super().__init__()
         if ksize != 3:
             raise NotImplementedError("GramLoss on the HIP path: ksize=3 only")
-        self._dl1 = _dist_l1(dist_norm)
-        if criterion not in ("l1", "l2", "mse"):
-            raise NotImplementedError("%s criterion has not been implmented." % criterion)
+        self._dl1, self.l2 = _patch_modes(dist_norm, criterion)
         self.alpha, self.beta, self.ksize, self.dist_norm = alpha, beta, ksize, dist_norm
-        self.l2 = criterion != "l1"
         self._cache = {}
         self.last_index = None
 
@@ -633,11 +539,8 @@ class PatchwiseStructureTensorLoss(nn.Module):
         super().__init__()
         if ksize != 3:
             raise NotImplementedError("PatchwiseStructureTensorLoss on the HIP path: ksize=3 only")
-        self._dl1 = _dist_l1(dist_norm)
-        if criterion not in ("l1", "l2", "mse"):
-            raise NotImplementedError("%s criterion has not been supported." % criterion)
+        self._dl1, self.l2 = _patch_modes(dist_norm, criterion, "supported")
         self.sigma, self.rho, self.alpha, self.beta, self.ksize, self.dist_norm = sigma, rho, alpha, beta, ksize, dist_norm
-        self.l2 = criterion != "l1"
         self._cache = {}
         self._mats = None
         self.last_index = None
@@ -653,7 +556,6 @@ class PatchwiseStructureTensorLoss(nn.Module):
 class _BceFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target_value):
-        from . import ops
         logits = logits.contiguous()
         ctx.save_for_backward(logits)
         ctx.t = target_value
@@ -662,7 +564,6 @@ class _BceFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from . import ops
         (logits,) = ctx.saved_tensors
         _, dl = ops.bce_logits(logits, ctx.t, want_loss=False, want_grad=True, scale_dev=grad_out.contiguous())
         return dl, None
@@ -675,15 +576,9 @@ class _AdvTermFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, total, logits, t, w):
-        from . import ops
         logits = logits.contiguous()
         raw, _ = ops.bce_logits(logits, t, want_loss=True)
-        out = torch.empty((), device=logits.device, dtype=torch.float32)
-        weighted = torch.empty(2, device=logits.device, dtype=torch.float32)
-        tot = total.contiguous()
-        ptrs = (ctypes.c_void_p * 2)(_abi.ptr(tot), _abi.ptr(raw))
-        wts = (ctypes.c_float * 2)(1.0, float(w))
-        _abi.check(_abi.lib().sst_weighted_sum(ptrs, wts, 2, _abi.ptr(out), _abi.ptr(weighted), _abi.stream_ptr()), "sst_weighted_sum")
+        out, weighted = ops.weighted_sum([total.contiguous(), raw], [1.0, w], True)
         ctx.save_for_backward(logits)
         ctx.t, ctx.w = t, float(w)
         ctx.mark_non_differentiable(weighted)
@@ -692,7 +587,6 @@ class _AdvTermFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _gw):
-        from . import ops
         (logits,) = ctx.saved_tensors
         _, dl = ops.bce_logits(logits, ctx.t, want_loss=False, want_grad=True, scale_dev=g.contiguous(), scale_host=ctx.w)
         return g, dl, None, None

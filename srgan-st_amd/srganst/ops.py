@@ -6,6 +6,7 @@ per-kernel parity tests.  No arithmetic happens in Python.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 
 import torch
@@ -479,16 +480,25 @@ def clamp_bwd(g, pre, dbias=None, accumulate=False):
     return out
 
 
+def reduction_ws(ws, key, n_partials, prefix=""):
+    """The workspace of a last-arriver reduction, kept in the caller's cache dict `ws` under prefix + "key" / "partials" / "counter":
+    fp32 partials [n_partials] and a zeroed int32 counter on key[0] (the device), rebuilt only when `key` changes - so a warm-up
+    call allocates what a later graph capture touches.  n_partials may be a callable; it is asked on a rebuild only.
+    -> (partials, counter)"""
+    if ws.get(prefix + "key") != key:
+        n = n_partials() if callable(n_partials) else n_partials
+        ws[prefix + "key"] = key
+        ws[prefix + "partials"] = torch.empty(n, device=key[0], dtype=torch.float32)
+        ws[prefix + "counter"] = torch.zeros(1, device=key[0], dtype=torch.int32)
+    return ws[prefix + "partials"], ws[prefix + "counter"]
+
+
 def pixel_loss_fwd(x, gt, mode, ws):
     n = x.numel()
-    key = (x.device, n)
-    if ws.get("key") != key:
-        ws["key"] = key
-        ws["partials"] = _f32(_abi.lib().sst_pixel_loss_blocks(n), like=x)
-        ws["counter"] = torch.zeros(1, device=x.device, dtype=torch.int32)
+    partials, counter = reduction_ws(ws, (x.device, n), lambda: _abi.lib().sst_pixel_loss_blocks(n))
     loss = _f32((), like=x)
-    check(_abi.lib().sst_pixel_loss_fwd(ptr(x), ptr(gt), ptr(loss), ptr(ws["partials"]), ptr(ws["counter"]), n, mode,
-                                        stream_ptr()), "sst_pixel_loss_fwd")
+    check(_abi.lib().sst_pixel_loss_fwd(ptr(x), ptr(gt), ptr(loss), ptr(partials), ptr(counter), n, mode, stream_ptr()),
+          "sst_pixel_loss_fwd")
     return loss
 
 
@@ -507,6 +517,17 @@ def bce_logits(logits, target, want_loss=True, want_grad=False, scale_dev=None, 
     check(_abi.lib().sst_bce_logits(ptr(logits), float(target), ptr(loss), ptr(dl), ptr(scale_dev), float(scale_host),
                                     logits.numel(), stream_ptr()), "sst_bce_logits")
     return loss, dl
+
+
+def weighted_sum(raws, weights, want_each):
+    """0-dim fp32 device scalars and host weights -> (sum_i w_i * raw_i, [w_i * raw_i] or None) in one tiny launch."""
+    n = len(raws)
+    total = _f32((), like=raws[0])
+    each = _f32(n, like=raws[0]) if want_each else None
+    ptrs = (ctypes.c_void_p * n)(*[ptr(r) for r in raws])
+    wts = (ctypes.c_float * n)(*[float(w) for w in weights])
+    check(_abi.lib().sst_weighted_sum(ptrs, wts, n, ptr(total), ptr(each), stream_ptr()), "sst_weighted_sum")
+    return total, each
 
 
 def pack_conv_s2_dgrad(w, out=None):

@@ -8,7 +8,8 @@ throughput and kernel parity can still be measured.  Frozen weights => no weight
 
 Kernel graph: SR and GT go through the stack as ONE batch of 2B (the weights stream once); convs are the generic
 fp32-MFMA kernel with ReLU applied on load, ReLU+MaxPool is one kernel, the feature criterion is the pixel-loss
-kernel in relu mode; backward runs on the SR half only (dgrad convs, max-pool routing, ReLU masks)."""
+kernel in relu mode (ops.pixel_loss_fwd / _bwd, one reduction workspace per tap in ``_ws``) and the taps are summed by
+ops.weighted_sum; backward runs on the SR half only (dgrad convs, max-pool routing, ReLU masks)."""
 from __future__ import annotations
 
 import torch
@@ -62,19 +63,8 @@ class _VggFn(torch.autograd.Function):
             else:
                 h, act = y, ops.ACT_SLOPE
                 i += 2
-        loss_terms, ws = [], module._ws
-        total = None
-        for t in taps:
-            y = feats[t]
-            n = y[:B].numel()
-            l = ops.pixel_loss_fwd(y[:B], y[B:], module.mode | 2, ws.setdefault(t, {}))
-            loss_terms.append(l)
-        # weighted sum of the (<= 8) scalars in one tiny launch
-        import ctypes
-        arr = (ctypes.c_void_p * len(taps))(*[l.data_ptr() for l in loss_terms])
-        wts = (ctypes.c_float * len(taps))(*[float(weights[t]) for t in taps])
-        out = torch.empty((), device=x.device, dtype=torch.float32)
-        _abi.check(_abi.lib().sst_weighted_sum(arr, wts, len(taps), _abi.ptr(out), None, _abi.stream_ptr()), "sst_weighted_sum")
+        loss_terms = [ops.pixel_loss_fwd(feats[t][:B], feats[t][B:], module.mode | 2, module._ws.setdefault(t, {})) for t in taps]
+        out, _ = ops.weighted_sum(loss_terms, [weights[t] for t in taps], False)      # the (<= 8) scalars in one tiny launch
         if need:
             ctx.module, ctx.saved, ctx.feats, ctx.B = module, saved, feats, B
         return out
