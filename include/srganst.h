@@ -92,6 +92,27 @@ int sst_ssim_loss_fwd(const float* sr, const float* gt, float* loss, float* maps
                       int W, int planes, double k1, double k2, void* stream);
 int sst_ssim_loss_bwd(const float* sr, const float* gt, const float* maps, float* dsr, const float* scale_dev, float scale_host,
                       int accumulate, int B, int H, int W, int planes, void* stream);
+/* ---- focal frequency loss (loss.py: FocalFrequencyLoss; csrc/freq_loss.hip): per image and RGB plane, with
+ * d = sr - gt and D its orthonormal 2-D DFT, e = |D|^2, w = sqrt(e)^alpha / max over the plane of sqrt(e)^alpha (NaN -> 0, clamped to
+ * [0,1], a constant for the gradient): loss[0] = mean over batch, planes and the H x W frequencies of w e.  sr, gt, dsr: NCHW fp32
+ * [B,3,H,W], 1 <= H, W <= 512 (any size: a direct DFT), B >= 1 and 3 B <= 65535; alpha finite and >= 0.  With Wh = W/2 + 1 (the half
+ * spectrum kx = 0 .. W/2; column 0 counts once, column W/2 once when W is even, every other column twice) and S = B*3*H*Wh*2:
+ * sst_freq_loss_workspace: saved_floats = S (w .* D as interleaved (re, im), laid out [B*3][H][Wh]: written by the forward, read by
+ *   the backward, owned by the call); scratch_floats = 2 S + B*3 * ceil(Wh/32) * ceil(H/32) (the row-pass output [B*3][Wh][H] complex,
+ *   the spectrum [B*3][H][Wh] complex, then one maximum of e per workgroup of the column pass; the backward reuses the first S floats;
+ *   contents are dead between entries, so one buffer per criterion serves every call of a shape); partial_floats =
+ *   2 * B*3 * ceil(H*Wh/1024): one fp64 partial per workgroup of the weighting kernel.  saved, scratch and partials must be 8-byte
+ *   aligned; counter is one 32-bit word, 0 at the first call, and re-arms itself.
+ * fwd: three launches (rows, columns, weighting); saved may be null (no gradient wanted: nothing is written there).  The partials are
+ *   summed in index order by the last-arriving workgroup: the same bits in every run.
+ * bwd: two launches (columns, rows): dsr (+)= scale_host * (scale_dev ? *scale_dev : 1) * d loss / d sr from `saved`; gt is a constant.
+ * Everything is validated on the host before any launch (null pointer, B < 1, H or W outside 1..512 "... size HxW not built", alpha
+ * negative or not finite, grid limits: non-zero return, message in sst_last_error); no allocation, no sync, asynchronous on `stream`. */
+int sst_freq_loss_workspace(int B, int H, int W, int64_t* saved_floats, int64_t* scratch_floats, int64_t* partial_floats);
+int sst_freq_loss_fwd(const float* sr, const float* gt, float* loss, float* saved, float* scratch, float* partials, unsigned* counter,
+                      int B, int H, int W, double alpha, void* stream);
+int sst_freq_loss_bwd(const float* saved, float* dsr, float* scratch, const float* scale_dev, float scale_host, int accumulate, int B,
+                      int H, int W, void* stream);
 
 /* ---- convolution (fp32 MFMA implicit GEMM, NHWC) --------------------------------------------------
  * Replaces the cuDNN/oneDNN kernels behind nn.Conv2d fwd/bwd of model.py:32-56,101,113,127,159,173,176.

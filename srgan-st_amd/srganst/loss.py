@@ -4,11 +4,12 @@ MSELoss / L1Loss     nn.MSELoss() of reference config.py:88-90 and its L1 varian
 StructureTensorLoss  <- reference loss.py:380-413 (+ utils.py:194-280), kernels csrc/st_loss.hip (radii (2,8), (4,10)) and
                         csrc/st_general.hip (every other (sigma, rho) up to radii 8 / 20)
 SSIMLoss             1 - mean SSIM, the criterion for the second number validate reports; kernels csrc/ssim_loss.hip
+FocalFrequencyLoss   the focal frequency loss (Jiang et al., ICCV 2021): a 2-D DFT and its adjoint; kernels csrc/freq_loss.hip
 ContentLossVGG       <- reference loss.py:11-70, in vgg_loss.py (re-exported here)
 BestBuddyLoss / GramLoss / PatchwiseStructureTensorLoss <- reference loss.py:78-228, 292-375, kernels csrc/bb_loss.hip
 ContentLossDiscriminator <- reference loss.py:231-289, in disc_loss.py (re-exported here)
 
-The four pixel-space criteria speak one term protocol (_Term): stand-alone they run under one autograd node
+The five pixel-space criteria speak one term protocol (_Term): stand-alone they run under one autograd node
 (_TermFn), summed under another (_CriterionSumFn, with the fused pixel + structure-tensor pair _StPixelPair as one more term), and
 each of their library entries is launched from one place.
 """
@@ -218,6 +219,62 @@ class SSIMLoss(_Term):
 
     def __repr__(self):
         return f"SSIMLoss(channel={self.channel!r}, k1={self.k1}, k2={self.k2})"
+
+
+# ------------------------------------------------------------------------------------------------
+FREQ_MAX_SIDE = 512       # the direct DFT's tables are built for H, W up to this
+
+
+class FocalFrequencyLoss(_Term):
+    """The focal frequency loss (Jiang et al., ICCV 2021) with the published defaults - one patch per image, no averaged spectrum, no
+    log weights, per-plane normalisation: with D the orthonormal 2-D DFT of sr - gt per image and RGB plane and e = |D|^2,
+    loss = mean(w e), w = sqrt(e)^alpha / max over the plane of sqrt(e)^alpha (NaN -> 0, clamped to [0, 1], a constant for the
+    gradient); alpha = 0 is the pixel MSE (Parseval).  fp32 [B,3,H,W] pairs with 1 <= H, W <= 512 of any size (a direct DFT, no radix
+    restriction); the gradient is taken with respect to sr only.  Kernels: csrc/freq_loss.hip."""
+
+    def __init__(self, alpha: float = 1.0):
+        super().__init__()
+        if isinstance(alpha, bool) or not (isinstance(alpha, (int, float)) and 0.0 <= float(alpha) < float("inf")):
+            raise ValueError(f"FocalFrequencyLoss: alpha must be a finite number >= 0, got {alpha!r}")
+        self.alpha = float(alpha)
+
+    def _check(self, x, gt):
+        _check_pair("FocalFrequencyLoss", x, gt, on_device=True)
+        B, _, H, W = x.shape
+        if B < 1 or not (1 <= H <= FREQ_MAX_SIDE and 1 <= W <= FREQ_MAX_SIDE):
+            raise _abi.HipPathError(f"FocalFrequencyLoss: size {H}x{W} not built (1 <= H, W <= {FREQ_MAX_SIDE}, B >= 1)")
+
+    def _fwd(self, x, gt, want_grad, route):
+        """want_grad False (no_grad, or sr does not require grad): the weighted spectrum is neither allocated nor written.  The
+        transforms' planes (scratch) and the reduction workspace belong to the criterion, keyed by device and shape."""
+        B, _, H, W = x.shape
+        n_saved, n_scratch, n_part = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _abi.check(_abi.lib().sst_freq_loss_workspace(B, H, W, ctypes.byref(n_saved), ctypes.byref(n_scratch), ctypes.byref(n_part)),
+                   "sst_freq_loss_workspace")
+        ws, key = self._ws, (x.device, B, H, W)
+        if ws.get("key") != key:
+            ws["scratch"] = torch.empty(n_scratch.value, device=x.device, dtype=torch.float32)
+        partials, counter = ops.reduction_ws(ws, key, n_part.value)
+        saved = torch.empty(n_saved.value, device=x.device, dtype=torch.float32) if want_grad else None
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(saved), _abi.ptr(ws["scratch"]), _abi.ptr(partials), _abi.ptr(counter),
+                B, H, W, self.alpha)
+        # algorithmic bytes: the forward reads sr + gt, the backward writes d(sr)
+        ops._launch_hbm(_abi.lib().sst_freq_loss_fwd, args, "sst_freq_loss_fwd", "freq_weight_kernel", 2.0 * x.numel() * 4,
+                        (x, gt, loss, saved, ws))
+        return loss, (saved, ws["scratch"]) if want_grad else None
+
+    def _bwd(self, x, gt, saved, dsr, g, scale_host, accumulate):
+        if saved is None:
+            raise _abi.HipPathError("FocalFrequencyLoss: the gradient is taken with respect to sr only (gt is a constant)")
+        saved, scratch = saved                          # the scratch of the forward's shape, whatever the criterion has seen since
+        B, _, H, W = x.shape
+        args = (_abi.ptr(saved), _abi.ptr(dsr), _abi.ptr(scratch), _abi.ptr(g), float(scale_host), int(accumulate), B, H, W)
+        ops._launch_hbm(_abi.lib().sst_freq_loss_bwd, args, "sst_freq_loss_bwd", "freq_pass_kernel", 1.0 * x.numel() * 4,
+                        (saved, dsr, scratch, g))
+
+    def __repr__(self):
+        return f"FocalFrequencyLoss(alpha={self.alpha})"
 
 
 # ------------------------------------------------------------------------------------------------
