@@ -113,6 +113,35 @@ int sst_freq_loss_fwd(const float* sr, const float* gt, float* loss, float* save
                       int B, int H, int W, double alpha, void* stream);
 int sst_freq_loss_bwd(const float* saved, float* dsr, float* scratch, const float* scale_dev, float scale_host, int accumulate, int B,
                       int H, int W, void* stream);
+/* ---- back-projection loss (loss.py: BackProjectionLoss, metrics.py: lr_consistency; csrc/bp_loss.hip): with
+ * down(x)[oy][ox] = sum_tx wx[ox][tx] * (sum_ty wy[oy][ty] * x[iy[oy][ty]][ix[ox][tx]]) - sst_bicubic's arithmetic: fp32 FMAs, taps
+ * in table order, the vertical sum inside - D = down(sr) - T and loss[0] = mean over B*3*oh*ow of |D| (criterion 0) or D^2
+ * (criterion 1).  sr, gt, dsr: NCHW fp32 [B,3,H,W]; scale 2, 4 or 8; oh = H / scale, ow = W / scale; H, W >= scale, any values;
+ * 1 <= B <= 21845.  wy / iy [oh,Ty], wx / ix [ow,Tx]: the tap tables of bicubic.py at 1 / scale in device memory (fp32 weights,
+ * int32 0-based indices that grow with the output and the tap), 1 <= Ty, Tx <= 4 scale + 2.
+ * sst_bp_loss_workspace: saved_floats = B*3*oh*ow (rho'(D) = sign(D), sign(0) = 0, or 2 D, laid out [B,3,oh,ow]: written by the
+ *   forward, read by the backward, owned by the call); partial_floats = 2 * B*3 * ceil(oh/8) * ceil(ow/tile), tile = 32 LR columns
+ *   (16 at scale 8): one fp64 partial per workgroup, so `partials` must be 8-byte aligned.
+ * fwd: one launch.  Exactly one of gt and lr is non-null: gt [B,3,H,W] gives T = down(gt), rounded to the 1/255 grid
+ *   (rintf(255 v) / 255: the bits of sst_bicubic(gt, round_grid = 1)) when round_target; lr [B,3,oh,ow] is T itself.  saved may be
+ *   null (no gradient wanted: nothing is written there); per_image may be null, else fp64 [B]: the mean of rho(D) per image, from the
+ *   same partials.  clamp_sr: sr is clamped to [0,1] as it is loaded (the metric; refused together with saved).  counter is one
+ *   32-bit word, 0 at the first call, and re-arms itself; the partials are summed in index order by the last-arriving workgroup:
+ *   the same bits in every run.
+ * bwd: one launch, a gather: dsr (+)= scale_host * (scale_dev ? *scale_dev : 1) * down^T(saved) / (B*3*oh*ow) through the transposed
+ *   tables ti_y / tw_y [H,Ny], ti_x / tw_x [W,Nx]: per input row (column) the (output index, weight) pairs of the outputs that read
+ *   it (the taps of one output clamped onto a border pixel listed one by one or merged), packed to the front; a list ends at the
+ *   first index < 0 (1 <= Ny, Nx <= 64).
+ * Everything is validated on the host before any launch (null pointer, both or neither of gt / lr, saved with clamp_sr, scale,
+ * criterion, B < 1, H or W < scale "image WxH is below ...", tap counts, list widths, grid limits: non-zero return, message in
+ * sst_last_error); no allocation, no sync, asynchronous on `stream`. */
+int sst_bp_loss_workspace(int B, int H, int W, int scale, int64_t* saved_floats, int64_t* partial_floats);
+int sst_bp_loss_fwd(const float* sr, const float* gt, const float* lr, float* loss, double* per_image, float* saved, float* partials,
+                    unsigned* counter, const float* wy, const int* iy, const float* wx, const int* ix, int B, int H, int W, int scale,
+                    int Ty, int Tx, int criterion, int round_target, int clamp_sr, void* stream);
+int sst_bp_loss_bwd(const float* saved, float* dsr, const float* tw_y, const int* ti_y, const float* tw_x, const int* ti_x,
+                    const float* scale_dev, float scale_host, int accumulate, int B, int H, int W, int scale, int Ny, int Nx,
+                    void* stream);
 
 /* ---- convolution (fp32 MFMA implicit GEMM, NHWC) --------------------------------------------------
  * Replaces the cuDNN/oneDNN kernels behind nn.Conv2d fwd/bwd of model.py:32-56,101,113,127,159,173,176.

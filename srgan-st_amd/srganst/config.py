@@ -74,6 +74,10 @@ class Config:
         # defaults): _metrics.txt and the printed line gain an ``ST:`` column, the drivers log Test/ST.  Checkpoint selection is
         # unchanged.  Works with either validation path; on the device path the values cross to the host once, after the loop
         self.DATA.VALIDATE_ST = False
+        # True: validation also reports the LR consistency of every test image (metrics.lr_consistency: the output, clamped and
+        # downscaled again by the kernel that made the LR input, against the loader's LR image) as an ``LR-PSNR:`` column of
+        # _metrics.txt and the printed line, after ``ST:`` when both are on; the drivers log Test/LR-PSNR.  Either validation path
+        self.DATA.VALIDATE_LR = False
         # T > 0: validation runs the generator tiled (upscale.Upscaler: windows of T LR pixels with the exact halo, so the whole-image
         # forward's result) - test images of any size, beyond what one whole-image forward takes.  0: whole-image forwards
         self.DATA.VALIDATE_TILE = 0

@@ -5,11 +5,13 @@ StructureTensorLoss  <- reference loss.py:380-413 (+ utils.py:194-280), kernels 
                         csrc/st_general.hip (every other (sigma, rho) up to radii 8 / 20)
 SSIMLoss             1 - mean SSIM, the criterion for the second number validate reports; kernels csrc/ssim_loss.hip
 FocalFrequencyLoss   the focal frequency loss (Jiang et al., ICCV 2021): a 2-D DFT and its adjoint; kernels csrc/freq_loss.hip
+BackProjectionLoss   the back-projection (LR-consistency) loss of Best-Buddy GANs (Li et al., AAAI 2022): |down(sr) - lr|, the fused
+                        antialiased bicubic downscale-and-compare and its adjoint; kernels csrc/bp_loss.hip
 ContentLossVGG       <- reference loss.py:11-70, in vgg_loss.py (re-exported here)
 BestBuddyLoss / GramLoss / PatchwiseStructureTensorLoss <- reference loss.py:78-228, 292-375, kernels csrc/bb_loss.hip
 ContentLossDiscriminator <- reference loss.py:231-289, in disc_loss.py (re-exported here)
 
-The five pixel-space criteria speak one term protocol (_Term): stand-alone they run under one autograd node
+The six pixel-space criteria speak one term protocol (_Term): stand-alone they run under one autograd node
 (_TermFn), summed under another (_CriterionSumFn, with the fused pixel + structure-tensor pair _StPixelPair as one more term), and
 each of their library entries is launched from one place.
 """
@@ -275,6 +277,126 @@ class FocalFrequencyLoss(_Term):
 
     def __repr__(self):
         return f"FocalFrequencyLoss(alpha={self.alpha})"
+
+
+# ------------------------------------------------------------------------------------------------
+BP_SCALES = (2, 4, 8)     # the downscaling factors csrc/bp_loss.hip is built for
+
+
+def bp_transposed_tables(weights, indices, in_size: int):
+    """The adjoint of one axis of the clamped-index resampling as gather lists.  weights / indices [out, taps]: a tap table of
+    bicubic._contribute (fp32, 0-based).  -> (tw [in_size, N] fp32, ti [in_size, N] int32): row i lists, by ascending output index,
+    the (output index, weight) pairs of the outputs that read input i, packed to the front; the rest of a row is (-1, 0).  The
+    taps of one output that were clamped onto the same border pixel are merged into one entry (their fp32 weights summed in fp64
+    and rounded once): a border list stays as short as an interior one (4) instead of growing to 6 / 10 / 18 at x2 / x4 / x8, and a
+    wave that holds a border column walks no longer than its neighbours.  N is the longest list (at least 1).  Host tensors."""
+    w, idx = weights.detach().cpu().to(torch.float64).tolist(), indices.detach().cpu().tolist()
+    lists = [{} for _ in range(int(in_size))]
+    for o, (wrow, irow) in enumerate(zip(w, idx)):
+        for wt, i in zip(wrow, irow):
+            lists[int(i)][o] = lists[int(i)].get(o, 0.0) + wt
+    n = max(1, max(len(l) for l in lists))
+    tw, ti = torch.zeros(int(in_size), n, dtype=torch.float32), torch.full((int(in_size), n), -1, dtype=torch.int32)
+    for i, l in enumerate(lists):
+        if l:
+            ti[i, :len(l)] = torch.tensor(sorted(l), dtype=torch.int32)
+            tw[i, :len(l)] = torch.tensor([l[o] for o in sorted(l)], dtype=torch.float64).to(torch.float32)
+    return tw, ti
+
+
+class BackProjectionLoss(_Term):
+    """The back-projection (LR-consistency) loss of Best-Buddy GANs (Li et al., AAAI 2022): mean |down(sr) - T| ("l1", the paper's)
+    or mean (down(sr) - T)^2 ("mse") over batch, RGB and the LR pixels, down = the MATLAB-style antialiased bicubic downscaling by
+    `scale` (2, 4 or 8) that makes the LR input (bicubic.Bicubic's tables and the arithmetic of its device kernel).  Called with
+    (sr, gt) like every criterion, T = down(gt), rounded to the 1/255 grid when round_target - bit for bit the LR image the dataset
+    and the device gathers hand to the generator.  With target="lr" the second argument is the LR image [B,3,H/scale,W/scale]
+    itself.  fp32 [B,3,H,W] with H, W >= scale, not necessarily multiples of it; the gradient is taken with respect to sr only.
+    Kernels: csrc/bp_loss.hip."""
+
+    def __init__(self, scale: int = 4, criterion: str = "l1", round_target: bool = True, target: str = "gt"):
+        super().__init__()
+        if isinstance(scale, bool) or not isinstance(scale, int) or scale not in BP_SCALES:
+            raise ValueError(f"BackProjectionLoss: scale must be one of {BP_SCALES}, got {scale!r}")
+        if criterion not in ("l1", "mse"):
+            raise ValueError(f"BackProjectionLoss: criterion must be 'l1' or 'mse', got {criterion!r}")
+        if target not in ("gt", "lr"):
+            raise ValueError(f"BackProjectionLoss: target must be 'gt' or 'lr', got {target!r}")
+        self.scale, self.criterion, self.round_target, self.target = scale, criterion, bool(round_target), target
+        self._tab = {}            # (device, H, W, scale) -> the forward and the transposed tap tables on the device
+
+    def _lr_shape(self, x):
+        B, _, H, W = x.shape
+        return (B, 3, H // self.scale, W // self.scale)
+
+    def _check(self, x, gt, who="BackProjectionLoss"):
+        if self.target == "gt":
+            _check_pair(who, x, gt, on_device=True)
+        else:
+            for name, t in (("sr", x), ("lr", gt)):
+                if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                    raise _abi.HipPathError(f"{who}: {name} must be a tensor on a ROCm device (no CPU fallback)")
+                if t.dtype != torch.float32:
+                    raise _abi.HipPathError(f"{who}: {name} must be fp32, got {t.dtype}")
+            if x.dim() != 4 or x.shape[1] != 3 or x.device != gt.device:
+                raise _abi.HipPathError(f"{who}: expected fp32 [B,3,H,W] sr and its LR image on one device, got {tuple(x.shape)} / "
+                                        f"{tuple(gt.shape)}")
+        B, _, H, W = x.shape
+        if B < 1 or H < self.scale or W < self.scale:
+            raise _abi.HipPathError(f"{who}: images of {W}x{H} are below the {self.scale}-px minimum of scale {self.scale}")
+        if self.target == "lr" and tuple(gt.shape) != self._lr_shape(x):
+            raise _abi.HipPathError(f"{who}: the LR image of a {tuple(x.shape)} sr at scale {self.scale} is {self._lr_shape(x)}, got "
+                                    f"{tuple(gt.shape)}")
+
+    def _tables(self, device, H, W):
+        """-> (wy, iy, wx, ix, tw_y, ti_y, tw_x, ti_x) on `device`, built on the host once per (device, H, W, scale): an eager
+        warm-up call creates them before a graph capture."""
+        key = (device, H, W, self.scale)
+        if key not in self._tab:
+            from .bicubic import _contribute
+            s = 1.0 / self.scale
+            w0, i0 = _contribute(H, int(H * s), s)
+            w1, i1 = _contribute(W, int(W * s), s)
+            fwd = (w0, i0.to(torch.int32), w1, i1.to(torch.int32))
+            self._tab[key] = tuple(t.contiguous().to(device) for t in fwd + bp_transposed_tables(w0, i0, H) + bp_transposed_tables(w1, i1, W))
+        return self._tab[key]
+
+    def _launch_fwd(self, x, target, want_grad, per_image=False, clamp_sr=False):
+        """The one launch site of sst_bp_loss_fwd -> (loss, per-image fp64 [B] or None, saved or None)."""
+        B, _, H, W = x.shape
+        n_saved, n_part = ctypes.c_int64(), ctypes.c_int64()
+        _abi.check(_abi.lib().sst_bp_loss_workspace(B, H, W, self.scale, ctypes.byref(n_saved), ctypes.byref(n_part)), "sst_bp_loss_workspace")
+        wy, iy, wx, ix = self._tables(x.device, H, W)[:4]
+        partials, counter = ops.reduction_ws(self._ws, (x.device, B, H, W, self.scale), n_part.value)
+        saved = torch.empty(n_saved.value, device=x.device, dtype=torch.float32) if want_grad else None
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        per = torch.empty(B, device=x.device, dtype=torch.float64) if per_image else None
+        gt, lr = (target, None) if self.target == "gt" else (None, target)
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(lr), _abi.ptr(loss), _abi.ptr(per), _abi.ptr(saved), _abi.ptr(partials), _abi.ptr(counter),
+                _abi.ptr(wy), _abi.ptr(iy), _abi.ptr(wx), _abi.ptr(ix), B, H, W, self.scale, wy.shape[1], wx.shape[1],
+                int(self.criterion == "mse"), int(self.round_target), int(bool(clamp_sr)))
+        # algorithmic bytes: the forward reads sr + gt (the LR image in lr mode), the backward writes d(sr)
+        ops._launch_hbm(_abi.lib().sst_bp_loss_fwd, args, "sst_bp_loss_fwd", "bp_loss_fwd_kernel", (x.numel() + target.numel()) * 4.0,
+                        (x, target, loss, saved, self._ws, per, wy, iy, wx, ix))
+        return loss, per, saved
+
+    def _fwd(self, x, gt, want_grad, route):
+        """want_grad False (no_grad, or sr does not require grad): the saved map is neither allocated nor written."""
+        loss, _, saved = self._launch_fwd(x, gt, want_grad)
+        return loss, saved
+
+    def _bwd(self, x, gt, saved, dsr, g, scale_host, accumulate):
+        if saved is None:
+            raise _abi.HipPathError("BackProjectionLoss: the gradient is taken with respect to sr only (the target is a constant)")
+        B, _, H, W = x.shape
+        tw_y, ti_y, tw_x, ti_x = self._tables(x.device, H, W)[4:]
+        args = (_abi.ptr(saved), _abi.ptr(dsr), _abi.ptr(tw_y), _abi.ptr(ti_y), _abi.ptr(tw_x), _abi.ptr(ti_x), _abi.ptr(g), float(scale_host),
+                int(accumulate), B, H, W, self.scale, tw_y.shape[1], tw_x.shape[1])
+        ops._launch_hbm(_abi.lib().sst_bp_loss_bwd, args, "sst_bp_loss_bwd", "bp_loss_bwd_kernel", 1.0 * x.numel() * 4,
+                        (saved, dsr, g, tw_y, ti_y, tw_x, ti_x))
+
+    def __repr__(self):
+        extra = ", target='lr'" if self.target == "lr" else ""
+        return f"BackProjectionLoss(scale={self.scale}, criterion={self.criterion!r}, round_target={self.round_target}{extra})"
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,7 +1,9 @@
 """Validation metrics on the device: validate.image_metrics (tensor2img -> Y channel -> PSNR / SSIM) as one HIP kernel family
 (csrc/metrics.hip: sst_image_metrics), rounding for rounding - not an approximation of the host path but the same numbers up to
 fp64 summation order.  The kernel returns the MSE of Y (0..255 scale) and the mean SSIM per image; PSNR follows on the host from
-the MSE (psnr_from_mse), after ONE device-to-host copy of all results."""
+the MSE (psnr_from_mse), after ONE device-to-host copy of all results.
+lr_consistency is the LR-consistency number reported next to them: the per-image MSE of the re-downscaled output against the LR
+input (csrc/bp_loss.hip, the forward of loss.BackProjectionLoss); lr_psnr_from_mse turns it into the LR-PSNR."""
 from __future__ import annotations
 
 import ctypes
@@ -53,6 +55,34 @@ def image_metrics_device(sr: Tensor, hr: Tensor, want_u8: bool = False, out: Ten
         _abi.check(_abi.lib().sst_image_metrics(_abi.ptr(sr), _abi.ptr(hr), B, H, W, _abi.ptr(out), _abi.ptr(sr_u8), _abi.ptr(hr_u8),
                                                 _abi.ptr(ws), _abi.stream_ptr()), "sst_image_metrics")
     return (out, sr_u8, hr_u8) if want_u8 else out
+
+
+_LR_TERMS = {}         # scale -> the lr-mode mse criterion whose tables and workspace lr_consistency uses
+
+
+def lr_consistency(sr: Tensor, lr: Tensor, scale: int = 4, clamp: bool = True) -> Tensor:
+    """sr fp32 [B,3,H,W] and its LR image lr fp32 [B,3,H/scale,W/scale] on one ROCm device -> fp64 [B] on that device: per image the
+    MSE over RGB, on the 0..1 scale, of down(sr) against lr, down = the antialiased bicubic downscaling that makes LR inputs
+    (loss.BackProjectionLoss's forward kernel, csrc/bp_loss.hip); clamp: sr is clamped to [0,1] first, as tensor2img does.  No
+    gradient; runs on the current stream, no sync.  lr_psnr_from_mse turns a value into the LR-PSNR."""
+    from .loss import BP_SCALES, BackProjectionLoss
+    if scale not in BP_SCALES:
+        raise HipPathError(f"lr_consistency: scale must be one of {BP_SCALES}, got {scale!r}")
+    term = _LR_TERMS.get(scale)
+    if term is None:
+        term = _LR_TERMS[scale] = BackProjectionLoss(scale, "mse", target="lr")
+    term._check(sr, lr, "lr_consistency")
+    with torch.cuda.device(sr.device):
+        _, per_image, _ = term._launch_fwd(sr.detach().contiguous(), lr.detach().contiguous(), False, per_image=True, clamp_sr=clamp)
+    return per_image
+
+
+def lr_psnr_from_mse(mse: float) -> float:
+    """10 log10(1 / mse) for an MSE on the 0..1 scale (lr_consistency's)."""
+    mse = float(mse)
+    if mse == 0:
+        return float("inf")
+    return 10 * math.log10(1.0 / mse)
 
 
 def psnr_from_mse(mse: float) -> float:

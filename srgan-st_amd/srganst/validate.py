@@ -5,7 +5,10 @@ With config.DATA.VALIDATE_ON_DEVICE (or on_device=True) the metrics are taken on
 With config.DATA.VALIDATE_ST (or with_st=True, or --st) every image also gets its structure-tensor distance (st.st_distance): the
 quantity the ``ST`` criterion optimises, reported next to PSNR and SSIM.
 With config.DATA.VALIDATE_TILE = T > 0 (or tile=T, or --tile T) the generator runs tiled (upscale.Upscaler, windows of T LR pixels with
-the exact halo): test images of any size, the whole-image forward's result."""
+the exact halo): test images of any size, the whole-image forward's result.
+With config.DATA.VALIDATE_LR (or with_lr=True, or --lr-consistency) every image also gets its LR consistency (metrics.lr_consistency:
+the generator's output, clamped and downscaled again by the kernel that made the LR input, against that LR input) as an ``LR-PSNR``
+column: the quantity the ``BackProjection`` criterion optimises."""
 from __future__ import annotations
 
 import argparse
@@ -54,14 +57,21 @@ def _st_params(config):
     return float(crit.sigma), float(crit.rho), bool(crit.normalize)
 
 
-def _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params=None):
+def _lr_scale(output, lr_img):
+    """The integer factor between a generator's output and its LR input."""
+    return int(round(output.shape[2] / lr_img.shape[2]))
+
+
+def _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params=None, with_lr=False):
     """The per-image loop of _validate with everything on the device: generator forward -> sst_image_metrics into row idx of one
     [N,2] result buffer, ONE device-to-host copy after the loop.  Nothing syncs per image unless save_images is set (the uint8
     images tensor2img would make then cross per image and are written by _save_png).  st_params: also st_distance(output, hr) per
-    image into an [N] buffer that crosses once as well -> third list."""
-    from .metrics import image_metrics_device, psnr_from_mse
+    image into an [N] buffer that crosses once as well -> third list; with_lr: the same for lr_consistency(output, lr) -> fourth list
+    (LR-PSNR)."""
+    from .metrics import image_metrics_device, lr_consistency, lr_psnr_from_mse, psnr_from_mse
     results = torch.empty(len(val_loader), 2, dtype=torch.float64, device=config.DEVICE)
     st_results = torch.empty(len(val_loader), dtype=torch.float64, device=config.DEVICE) if st_params else None
+    lr_results = torch.empty(len(val_loader), dtype=torch.float64, device=config.DEVICE) if with_lr else None
     with torch.no_grad():
         for idx, (hr_img, lr_img) in enumerate(val_loader):
             lr_img = lr_img.to(config.DEVICE, non_blocking=True)
@@ -78,17 +88,22 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
                 image_metrics_device(output, hr_img, out=row)
             if st_params:
                 st_results[idx:idx + 1].copy_(st_distance(output, hr_img, *st_params))
+            if with_lr:
+                lr_results[idx:idx + 1].copy_(lr_consistency(output, lr_img, _lr_scale(output, lr_img)))
     host = results.cpu().tolist()
-    return [psnr_from_mse(mse) for mse, _ in host], [ssim for _, ssim in host], st_results.cpu().tolist() if st_params else []
+    all_lr = [lr_psnr_from_mse(m) for m in lr_results.cpu().tolist()] if with_lr else []
+    return [psnr_from_mse(mse) for mse, _ in host], [ssim for _, ssim in host], st_results.cpu().tolist() if st_params else [], all_lr
 
 
 def _validate(generator, val_loader, config, save_images=False, concat_with_gt=False, save_metrics=False, on_device=None,
-              with_st=None, tile=None):
+              with_st=None, tile=None, with_lr=None):
     """on_device: None = config.DATA.VALIDATE_ON_DEVICE; True = metrics by the HIP kernel, one host copy per pass
     (_metrics_on_device); False = the host loop below.  Same averages, same printed line, same _metrics.txt either way.
     with_st: None = config.DATA.VALIDATE_ST; True = every image also gets st.st_distance(output, hr) with the configured ``ST``
     criterion's (sigma, rho, normalize), _metrics.txt and the printed line gain an ``ST:`` column and the return value becomes
     (psnr, ssim, st); False = everything as without the option.
+    with_lr: None = config.DATA.VALIDATE_LR; True = every image also gets metrics.lr_consistency(output, the loader's lr_img) as an
+    ``LR-PSNR:`` column (after ``ST:`` when both are on) and the return value gains (lr_psnr,) at its end; False = as without it.
     tile: None = config.DATA.VALIDATE_TILE; T > 0 = a Generator runs through upscale.Upscaler(tile=T) with the exact halo (an image
     that fits in one window takes the plain forward, so small test sets give the numbers they give without the option); 0 = off."""
     if tile is None:
@@ -101,18 +116,22 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
     if with_st is None:
         with_st = bool(config.DATA.get("VALIDATE_ST", False))
     st_params = _st_params(config) if with_st else None
+    if with_lr is None:
+        with_lr = bool(config.DATA.get("VALIDATE_LR", False))
     file = None
     if save_metrics:
         path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
         os.makedirs(path, exist_ok=True)
         file = open(os.path.join(path, "_metrics.txt"), mode="w")
-    all_psnr, all_ssim, all_st = [], [], []
+    all_psnr, all_ssim, all_st, all_lr = [], [], [], []
     if on_device:
-        all_psnr, all_ssim, all_st = _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params)
+        all_psnr, all_ssim, all_st, all_lr = _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params,
+                                                                with_lr)
         if file:
             for idx, (psnr, ssim) in enumerate(zip(all_psnr, all_ssim)):
                 st_col = f" | ST: {all_st[idx]:.4f}" if with_st else ""
-                file.write(f"{idx}.png | PSNR: {psnr:.2f} | SSIM: {ssim:.4f}{st_col}\n")
+                lr_col = f" | LR-PSNR: {all_lr[idx]:.2f}" if with_lr else ""
+                file.write(f"{idx}.png | PSNR: {psnr:.2f} | SSIM: {ssim:.4f}{st_col}{lr_col}\n")
     else:
         with torch.no_grad():
             for idx, (hr_img, lr_img) in enumerate(val_loader):
@@ -131,8 +150,13 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
                 if with_st:                                   # the host-metric path syncs per image anyway
                     all_st.append(st_distance(output, hr_img, *st_params).item())
                     st_col = f" | ST: {all_st[-1]:.4f}"
+                lr_col = ""
+                if with_lr:
+                    from .metrics import lr_consistency, lr_psnr_from_mse
+                    all_lr.append(lr_psnr_from_mse(lr_consistency(output, lr_img, _lr_scale(output, lr_img)).item()))
+                    lr_col = f" | LR-PSNR: {all_lr[-1]:.2f}"
                 if file:
-                    file.write(f"{idx}.png | PSNR: {psnr:.2f} | SSIM: {ssim:.4f}{st_col}\n")
+                    file.write(f"{idx}.png | PSNR: {psnr:.2f} | SSIM: {ssim:.4f}{st_col}{lr_col}\n")
     avg_psnr = sum(all_psnr) / len(all_psnr)
     avg_ssim = sum(all_ssim) / len(all_ssim)
     out = (f"[Test] | PSNR: {avg_psnr:.2f} ± {confidence_interval(all_psnr):.2f} | "
@@ -140,16 +164,19 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
     if with_st:
         avg_st = sum(all_st) / len(all_st)
         out += f"ST: {avg_st:.4f} ± {confidence_interval(all_st):.4f} | "
+    if with_lr:
+        avg_lr = sum(all_lr) / len(all_lr)
+        out += f"LR-PSNR: {avg_lr:.2f} ± {confidence_interval(all_lr):.2f} | "
     out += "\n"
     print(out)
     if file:
         file.write("\n" + out + "\n")
         file.close()
-    return (avg_psnr, avg_ssim, avg_st) if with_st else (avg_psnr, avg_ssim)
+    return (avg_psnr, avg_ssim) + ((avg_st,) if with_st else ()) + ((avg_lr,) if with_lr else ())
 
 
 def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_gt: bool = False, dataset=None, on_device=None,
-         with_st=None, tile=None):
+         with_st=None, tile=None, with_lr=None):
     if not g_path:                # the averaged generator's best when the run kept one (SOLVER.G_EMA_DECAY), else the last iterate's
         g_path = f"results/{config.EXP.NAME}/g_ema_best.pth"
         if not os.path.exists(g_path):
@@ -165,7 +192,7 @@ def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_
         generator = load_state_dict(generator, torch.load(g_path, map_location=config.DEVICE, weights_only=True))
         generator.eval()
     return _validate(generator, loader, config, save_images=save_images, concat_with_gt=concat_w_gt, save_metrics=True,
-                     on_device=on_device, with_st=with_st, tile=tile)
+                     on_device=on_device, with_st=with_st, tile=tile, with_lr=with_lr)
 
 
 if __name__ == "__main__":
@@ -177,6 +204,7 @@ if __name__ == "__main__":
     parser.add_argument("--on-device", action="store_true", help="PSNR / SSIM by the HIP kernel (DATA.VALIDATE_ON_DEVICE)")
     parser.add_argument("--st", action="store_true", help="also the structure-tensor distance per image (DATA.VALIDATE_ST)")
     parser.add_argument("--tile", type=int, default=None, help="run the generator tiled, windows of this many LR pixels (DATA.VALIDATE_TILE)")
+    parser.add_argument("--lr-consistency", action="store_true", help="also the LR-PSNR of the re-downscaled output per image (DATA.VALIDATE_LR)")
     a = parser.parse_args()
     cfg = Config()
     if a.name:
@@ -186,4 +214,4 @@ if __name__ == "__main__":
         cfg.DATA.TEST_GT_IMAGES_DIR = f"/work3/{cfg.EXP.USER}/data/{a.test_set}/GTmod12"
         cfg.DATA.TEST_LR_IMAGES_DIR = f"/work3/{cfg.EXP.USER}/data/{a.test_set}/LRbicx4"
     test(cfg, save_images=not a.no_images, g_path=a.g_path, on_device=True if a.on_device else None,
-         with_st=True if a.st else None, tile=a.tile)
+         with_st=True if a.st else None, tile=a.tile, with_lr=True if a.lr_consistency else None)

@@ -121,14 +121,19 @@ def warmup(config: Config, train_dataset=None, test_dataset=None, max_steps_per_
         generator.eval()
         if rank == 0:
             engine.sync_ema_buffers()             # the averaged generator takes G's BatchNorm buffers before it is run or saved
-            # (psnr, ssim, st) with DATA.VALIDATE_ST; with the average on (and G_EMA_VALIDATE) it is the averaged generator's
-            psnr, ssim, *st = _validate(engine.g_ema if ema_validate else generator, test_loader, config)
+            # (psnr, ssim) + (st,) with DATA.VALIDATE_ST + (lr_psnr,) with DATA.VALIDATE_LR; with the average on (and G_EMA_VALIDATE)
+            # it is the averaged generator's
+            psnr, ssim, *more = _validate(engine.g_ema if ema_validate else generator, test_loader, config)
+            st = more[:1] if config.DATA.get("VALIDATE_ST", False) else []
+            lr_psnr = more[-1:] if config.DATA.get("VALIDATE_LR", False) else []
             if epoch % config.LOG_VALIDATION_PERIOD == 0:
                 print(f"[Test: {epoch+1}/{config.EXP.N_EPOCHS}] [PSNR: {psnr}] [SSIM: {ssim}]")
             writer.add_scalar("Test/PSNR", psnr, epoch + 1)
             writer.add_scalar("Test/SSIM", ssim, epoch + 1)
             if st:
                 writer.add_scalar("Test/ST", st[0], epoch + 1)
+            if lr_psnr:
+                writer.add_scalar("Test/LR-PSNR", lr_psnr[0], epoch + 1)
             results_dir = f"results/{config.EXP.NAME}"
             os.makedirs(results_dir, exist_ok=True)
             torch.save(generator.state_dict(), results_dir + "/g_last.pth")
