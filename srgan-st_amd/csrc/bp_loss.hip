@@ -36,11 +36,6 @@ constexpr int BP_MAX_LIST = 64;        // the longest transposed list the backwa
 
 __host__ __device__ constexpr int bp_tile(int scale) { return scale == 8 ? 16 : 32; }      // LR columns per tile
 
-__device__ __forceinline__ double bp_load_agent_d(const double* p) {
-  return __longlong_as_double(
-      (long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
 __global__ __launch_bounds__(BP_NT) void bp_loss_fwd_kernel(const float* __restrict__ sr, const float* __restrict__ gt,
                                                             const float* __restrict__ lr, float* __restrict__ saved,
                                                             double* partials, unsigned* counter, float* __restrict__ loss,
@@ -108,36 +103,19 @@ __global__ __launch_bounds__(BP_NT) void bp_loss_fwd_kernel(const float* __restr
   }
 
   // ---- one partial per workgroup; the last arriver sums them in index order and re-arms the counter
-  ss = wave_sum_d(ss);
-  if ((tid & 63) == 0) s_red[tid >> 6] = ss;
-  __syncthreads();
   const unsigned per_plane = gridDim.x * gridDim.y, nblk = per_plane * gridDim.z;
-  if (tid == 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < BP_NT / 64; ++k) t += s_red[k];
-    partials[blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)] = t;
-    s_flag = (publish_and_ticket(counter) == nblk - 1) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!s_flag) return;
-  if (tid == 0) acquire_after_ticket();
-  __syncthreads();
+  const unsigned blk = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  if (!last_block_arrive_d<BP_NT>(ss, partials, blk, counter, nblk, &s_flag, s_red)) return;
   if (per_image) {                                   // image b owns the 3 * per_plane consecutive partials of its planes
     const unsigned per_img = 3 * per_plane, nimg = gridDim.z / 3;
     for (unsigned b = tid; b < nimg; b += BP_NT) {
       double t = 0.0;
-      for (unsigned k = 0; k < per_img; ++k) t += bp_load_agent_d(partials + (int64_t)b * per_img + k);
+      for (unsigned k = 0; k < per_img; ++k) t += load_agent_d(partials + (int64_t)b * per_img + k);
       per_image[b] = t / (3.0 * (double)oh * (double)ow);
     }
   }
-  double t = 0.0;
-  for (unsigned i = tid; i < nblk; i += BP_NT) t += bp_load_agent_d(partials + i);
-  t = block_sum_d<BP_NT>(t, s_red);
-  if (tid == 0) {
-    loss[0] = (float)(t / count);
-    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  const double t = last_block_total_d<BP_NT>(partials, counter, nblk, s_red);
+  if (tid == 0) loss[0] = (float)(t / count);
 }
 
 // dsr (+)= scale * (scale_dev ? *scale_dev : 1) * down^T(saved);  scale = scale_host / count.  Block = 64 columns x 4 rows.

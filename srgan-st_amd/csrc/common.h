@@ -108,3 +108,42 @@ __device__ __forceinline__ bool last_block_total(const float* partials, unsigned
   if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   return true;
 }
+
+// The same for fp64 partials (the criteria whose loss is summed in fp64: ssim_loss, freq_loss, bp_loss), in two halves, because a
+// kernel may read the partials for sums of its own between arriving and totalling (bp_loss's per-image values).
+__device__ __forceinline__ double load_agent_d(const double* p) {
+  return __longlong_as_double(
+      (long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+// Arrive - ALL threads of the workgroup, each with its own value `v`: the wave sums, then thread 0 adds them in index order, stores
+// partials[idx] and takes the ticket.  Returns true in the last-arriving workgroup, after the acquire and a barrier: every
+// workgroup's partial is then readable with load_agent_d.  `s_flag` / `red` (NT/64 doubles, shared with the total) are LDS.
+template <int NT>
+__device__ __forceinline__ bool last_block_arrive_d(double v, double* partials, unsigned idx, unsigned* counter, unsigned nblk,
+                                                    unsigned* s_flag, double* red) {
+  v = wave_sum_d(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+#pragma unroll
+    for (int k = 0; k < NT / 64; ++k) t += red[k];
+    partials[idx] = t;
+    *s_flag = (publish_and_ticket(counter) == nblk - 1) ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!*s_flag) return false;
+  if (threadIdx.x == 0) acquire_after_ticket();
+  __syncthreads();
+  return true;
+}
+// Total - all threads of the last arriver only: the sum of partials[0..nblk) in a fixed order (thread i adds i, i + NT, ..., then
+// block_sum_d), valid in every thread; re-arms the counter for the next launch.
+template <int NT>
+__device__ __forceinline__ double last_block_total_d(const double* partials, unsigned* counter, unsigned nblk, double* red) {
+  double t = 0.0;
+  for (unsigned i = threadIdx.x; i < nblk; i += NT) t += load_agent_d(partials + i);
+  t = block_sum_d<NT>(t, red);
+  if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return t;
+}

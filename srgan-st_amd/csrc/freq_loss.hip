@@ -70,11 +70,6 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
-__device__ __forceinline__ double load_agent_d(const double* p) {
-  return __longlong_as_double(
-      (long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
 // in0 / in1: ROW_FWD sr / gt (fp32 planes), else in0 = the complex input (float2) and in1 unused.  out: complex (float2), ROW_ADJ: dsr.
 // pmax (COL_FWD): [plane][gridDim.y * gridDim.x] maxima of e.  scale: COL_FWD 1/sqrt(HW); ROW_ADJ the gradient's host scale.
 template <int MODE>
@@ -240,28 +235,10 @@ __global__ __launch_bounds__(FNT) void freq_weight_kernel(const float2* __restri
   }
 
   // ---- one partial per workgroup; the last arriver sums them in index order and re-arms the counter
-  ss = wave_sum_d(ss);
-  if ((tid & 63) == 0) s_red[tid >> 6] = ss;
-  __syncthreads();
   const unsigned nblk = gridDim.x * gridDim.y;
-  if (tid == 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < FNT / 64; ++k) t += s_red[k];
-    partials[blockIdx.x + gridDim.x * blockIdx.y] = t;
-    s_flag = (publish_and_ticket(counter) == nblk - 1) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!s_flag) return;
-  if (tid == 0) acquire_after_ticket();
-  __syncthreads();
-  double t = 0.0;
-  for (unsigned i = tid; i < nblk; i += FNT) t += load_agent_d(partials + i);
-  t = block_sum_d<FNT>(t, s_red);
-  if (tid == 0) {
-    loss[0] = (float)(t / count);
-    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (!last_block_arrive_d<FNT>(ss, partials, blockIdx.x + gridDim.x * blockIdx.y, counter, nblk, &s_flag, s_red)) return;
+  const double t = last_block_total_d<FNT>(partials, counter, nblk, s_red);
+  if (tid == 0) loss[0] = (float)(t / count);
 }
 
 // shape rules shared by the three entries

@@ -71,11 +71,6 @@ __device__ __forceinline__ float plane_value(const float* __restrict__ img, int6
   return (float)((((r * LUMA_R + g * LUMA_G) + b * LUMA_B) + 16.0) / 255.0);
 }
 
-__device__ __forceinline__ double load_agent_d(const double* p) {
-  return __longlong_as_double(
-      (long long)__hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-
 __global__ __launch_bounds__(LNT) void ssim_loss_fwd_kernel(const float* __restrict__ sr, const float* __restrict__ gt,
                                                             float* __restrict__ maps, double* partials, unsigned* counter,
                                                             float* __restrict__ loss, int H, int W, int planes, double C1, double C2,
@@ -165,28 +160,11 @@ __global__ __launch_bounds__(LNT) void ssim_loss_fwd_kernel(const float* __restr
   }
 
   // ---- one partial per workgroup; the last arriver sums them in index order and re-arms the counter
-  ss = wave_sum_d(ss);
-  if ((tid & 63) == 0) s_red[tid >> 6] = ss;
-  __syncthreads();
   const unsigned nblk = gridDim.x * gridDim.y * gridDim.z;
-  if (tid == 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < LNT / 64; ++k) t += s_red[k];
-    partials[blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)] = t;
-    s_flag = (publish_and_ticket(counter) == nblk - 1) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (!s_flag) return;
-  if (tid == 0) acquire_after_ticket();
-  __syncthreads();
-  double t = 0.0;
-  for (unsigned i = tid; i < nblk; i += LNT) t += load_agent_d(partials + i);
-  t = block_sum_d<LNT>(t, s_red);
-  if (tid == 0) {
-    loss[0] = (float)(1.0 - t / count);
-    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  const unsigned blk = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  if (!last_block_arrive_d<LNT>(ss, partials, blk, counter, nblk, &s_flag, s_red)) return;
+  const double t = last_block_total_d<LNT>(partials, counter, nblk, s_red);
+  if (tid == 0) loss[0] = (float)(1.0 - t / count);
 }
 
 // dsr (+)= scale * (scale_dev ? *scale_dev : 1) * (the three full correlations combined);  scale = -scale_host / count

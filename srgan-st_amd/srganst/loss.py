@@ -26,19 +26,28 @@ from torch import nn
 from . import _abi, ops
 
 
-def _check_pair(who, x, gt, image=True, gt_too=True, on_device=False):
+def _check_pair(who, x, gt, image=True, gt_too=True, on_device=False, second="gt"):
     """The input check of the criteria: an fp32 pair of equal shape; image: [B,3,H,W]; gt_too: gt's dtype counts as well as sr's;
-    on_device: both are tensors on one ROCm device, and what is wrong with either is named."""
+    on_device: both are tensors on one ROCm device, and what is wrong with either is named.  second="lr": the second operand is
+    sr's LR image, whose shape is the caller's to check."""
     if on_device:
-        for name, t in (("sr", x), ("gt", gt)):
+        for name, t in (("sr", x), (second, gt)):
             if not isinstance(t, torch.Tensor) or not t.is_cuda:
                 raise _abi.HipPathError(f"{who}: {name} must be a tensor on a ROCm device (no CPU fallback)")
             if t.dtype != torch.float32:
                 raise _abi.HipPathError(f"{who}: {name} must be fp32, got {t.dtype}")
-    bad = x.dtype != torch.float32 or (gt_too and gt.dtype != torch.float32) or x.shape != gt.shape
+    bad = x.dtype != torch.float32 or (gt_too and gt.dtype != torch.float32) or (second == "gt" and x.shape != gt.shape)
     if bad or (image and (x.dim() != 4 or x.shape[1] != 3)) or (on_device and x.device != gt.device):
-        raise _abi.HipPathError(f"{who}: expected fp32 {'[B,3,H,W] pairs' if image else 'tensors of equal shape'}"
+        what = "tensors of equal shape" if not image else "[B,3,H,W] pairs" if second == "gt" else "[B,3,H,W] sr and its LR image"
+        raise _abi.HipPathError(f"{who}: expected fp32 {what}"
                                 f"{' on one device' if on_device else ''}, got {tuple(x.shape)} / {tuple(gt.shape)}")
+
+
+def _workspace(entry, *dims, n):
+    """sst_<entry>_workspace(dims..., n sizes by reference), checked -> the n sizes (floats) as ints.  Host only."""
+    name, sizes = f"sst_{entry}_workspace", [ctypes.c_int64() for _ in range(n)]
+    _abi.check(getattr(_abi.lib(), name)(*dims, *map(ctypes.byref, sizes)), name)
+    return [v.value for v in sizes]
 
 
 class _Term(nn.Module):
@@ -50,6 +59,7 @@ class _Term(nn.Module):
                                   and belongs to the call; the reduction workspace lives in self._ws and belongs to the criterion
     _bwd(sr, gt, saved, dsr, g, scale_host, accumulate)   dsr (+)= scale_host * g[0] * d raw / d sr; dsr is the caller's buffer,
                                   g a device scalar"""
+    _constant = "gt"          # what the second operand is called where a gradient is asked for it
 
     def __init__(self):
         super().__init__()
@@ -57,6 +67,12 @@ class _Term(nn.Module):
 
     def _route(self):
         return None
+
+    def _kept(self, saved):
+        """`saved` of a forward that ran for a gradient; None (want_grad was False) means the gradient is wanted for the second operand."""
+        if saved is None:
+            raise _abi.HipPathError(f"{type(self).__name__}: the gradient is taken with respect to sr only ({self._constant} is a constant)")
+        return saved
 
     def forward(self, x, gt):
         want_grad = torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad
@@ -119,9 +135,8 @@ class StructureTensorLoss(_Term):
     def _tile_ws(self, x):
         """The tile kernels' partials / last-arriver counter, keyed by device and shape -> (floats of the partials, partials, counter)."""
         B, _, H, W = x.shape
-        n = ctypes.c_int64()
-        _abi.check(_abi.lib().sst_st_loss_workspace(B, H, W, ctypes.byref(n)), "sst_st_loss_workspace")
-        return (n.value, *ops.reduction_ws(self._ws, (x.device, B, H, W), n.value))
+        n, = _workspace("st_loss", B, H, W, n=1)
+        return (n, *ops.reduction_ws(self._ws, (x.device, B, H, W), n))
 
     def _fwd(self, x, gt, want_grad, route):
         """gS = d(per-pixel distance) / d(structure tensor of sr) is written either way: it belongs to the call, and with what
@@ -140,14 +155,9 @@ class StructureTensorLoss(_Term):
             return loss, (cfg, gS)
         # general route: scratch planes next to partials and counter, keyed by the radii as well (a warm-up call allocates them before
         # a graph capture); they only live inside one entry point.  The saved planes (Ix, Iy of sr) belong to the call, like gS.
-        n_scratch, n_saved, n_part = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        _abi.check(_abi.lib().sst_st_general_workspace(B, H, W, ctypes.byref(n_scratch), ctypes.byref(n_saved), ctypes.byref(n_part)),
-                   "sst_st_general_workspace")
-        key = (x.device, B, H, W, radii)
-        if ws.get("general_key") != key:
-            ws["general_scratch"] = torch.empty(n_scratch.value, device=x.device, dtype=torch.float32)
-        partials, counter = ops.reduction_ws(ws, key, n_part.value, "general_")
-        planes, scratch = torch.empty(n_saved.value, device=x.device, dtype=torch.float32), ws["general_scratch"]
+        n_scratch, n_saved, n_part = _workspace("st_general", B, H, W, n=3)
+        partials, counter, scratch = ops.reduction_ws(ws, (x.device, B, H, W, radii), n_part, "general_", scratch=n_scratch)
+        planes = torch.empty(n_saved, device=x.device, dtype=torch.float32)
         args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(gS), _abi.ptr(planes), _abi.ptr(scratch), _abi.ptr(partials),
                 _abi.ptr(counter), B, H, W, *cfg, int(bool(self.normalize)))
         ops._launch_hbm(_abi.lib().sst_st_general_fwd, args, "sst_st_general_fwd", "stg_loss_fwd_kernel", 2.0 * x.numel() * 4,
@@ -199,10 +209,9 @@ class SSIMLoss(_Term):
         """want_grad False (no_grad, or sr does not require grad): the gradient maps are neither allocated nor written."""
         B, _, H, W = x.shape
         planes = 1 if self.channel == "y" else 3
-        n_maps, n_part = ctypes.c_int64(), ctypes.c_int64()
-        _abi.check(_abi.lib().sst_ssim_loss_workspace(B, H, W, planes, ctypes.byref(n_maps), ctypes.byref(n_part)), "sst_ssim_loss_workspace")
-        partials, counter = ops.reduction_ws(self._ws, (x.device, B, H, W, planes), n_part.value)
-        maps = torch.empty(n_maps.value, device=x.device, dtype=torch.float32) if want_grad else None
+        n_maps, n_part = _workspace("ssim_loss", B, H, W, planes, n=2)
+        partials, counter = ops.reduction_ws(self._ws, (x.device, B, H, W, planes), n_part)
+        maps = torch.empty(n_maps, device=x.device, dtype=torch.float32) if want_grad else None
         loss = torch.empty((), device=x.device, dtype=torch.float32)
         args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(maps), _abi.ptr(partials), _abi.ptr(counter), B, H, W, planes, self.k1, self.k2)
         # algorithmic bytes: the forward reads sr + gt, the backward writes d(sr)
@@ -211,9 +220,7 @@ class SSIMLoss(_Term):
         return loss, (planes, maps) if want_grad else None
 
     def _bwd(self, x, gt, saved, dsr, g, scale_host, accumulate):
-        if saved is None:
-            raise _abi.HipPathError("SSIMLoss: the gradient is taken with respect to sr only (gt is a constant)")
-        planes, maps = saved
+        planes, maps = self._kept(saved)
         B, _, H, W = x.shape
         args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(maps), _abi.ptr(dsr), _abi.ptr(g), float(scale_host), int(accumulate), B, H, W, planes)
         ops._launch_hbm(_abi.lib().sst_ssim_loss_bwd, args, "sst_ssim_loss_bwd", "ssim_loss_bwd_kernel", 1.0 * x.numel() * 4,
@@ -250,26 +257,19 @@ class FocalFrequencyLoss(_Term):
         """want_grad False (no_grad, or sr does not require grad): the weighted spectrum is neither allocated nor written.  The
         transforms' planes (scratch) and the reduction workspace belong to the criterion, keyed by device and shape."""
         B, _, H, W = x.shape
-        n_saved, n_scratch, n_part = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-        _abi.check(_abi.lib().sst_freq_loss_workspace(B, H, W, ctypes.byref(n_saved), ctypes.byref(n_scratch), ctypes.byref(n_part)),
-                   "sst_freq_loss_workspace")
-        ws, key = self._ws, (x.device, B, H, W)
-        if ws.get("key") != key:
-            ws["scratch"] = torch.empty(n_scratch.value, device=x.device, dtype=torch.float32)
-        partials, counter = ops.reduction_ws(ws, key, n_part.value)
-        saved = torch.empty(n_saved.value, device=x.device, dtype=torch.float32) if want_grad else None
+        n_saved, n_scratch, n_part = _workspace("freq_loss", B, H, W, n=3)
+        partials, counter, scratch = ops.reduction_ws(self._ws, (x.device, B, H, W), n_part, scratch=n_scratch)
+        saved = torch.empty(n_saved, device=x.device, dtype=torch.float32) if want_grad else None
         loss = torch.empty((), device=x.device, dtype=torch.float32)
-        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(saved), _abi.ptr(ws["scratch"]), _abi.ptr(partials), _abi.ptr(counter),
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(saved), _abi.ptr(scratch), _abi.ptr(partials), _abi.ptr(counter),
                 B, H, W, self.alpha)
         # algorithmic bytes: the forward reads sr + gt, the backward writes d(sr)
         ops._launch_hbm(_abi.lib().sst_freq_loss_fwd, args, "sst_freq_loss_fwd", "freq_weight_kernel", 2.0 * x.numel() * 4,
-                        (x, gt, loss, saved, ws))
-        return loss, (saved, ws["scratch"]) if want_grad else None
+                        (x, gt, loss, saved, self._ws))
+        return loss, (saved, scratch) if want_grad else None
 
     def _bwd(self, x, gt, saved, dsr, g, scale_host, accumulate):
-        if saved is None:
-            raise _abi.HipPathError("FocalFrequencyLoss: the gradient is taken with respect to sr only (gt is a constant)")
-        saved, scratch = saved                          # the scratch of the forward's shape, whatever the criterion has seen since
+        saved, scratch = self._kept(saved)              # the scratch of the forward's shape, whatever the criterion has seen since
         B, _, H, W = x.shape
         args = (_abi.ptr(saved), _abi.ptr(dsr), _abi.ptr(scratch), _abi.ptr(g), float(scale_host), int(accumulate), B, H, W)
         ops._launch_hbm(_abi.lib().sst_freq_loss_bwd, args, "sst_freq_loss_bwd", "freq_pass_kernel", 1.0 * x.numel() * 4,
@@ -312,6 +312,7 @@ class BackProjectionLoss(_Term):
     and the device gathers hand to the generator.  With target="lr" the second argument is the LR image [B,3,H/scale,W/scale]
     itself.  fp32 [B,3,H,W] with H, W >= scale, not necessarily multiples of it; the gradient is taken with respect to sr only.
     Kernels: csrc/bp_loss.hip."""
+    _constant = "the target"
 
     def __init__(self, scale: int = 4, criterion: str = "l1", round_target: bool = True, target: str = "gt"):
         super().__init__()
@@ -329,17 +330,7 @@ class BackProjectionLoss(_Term):
         return (B, 3, H // self.scale, W // self.scale)
 
     def _check(self, x, gt, who="BackProjectionLoss"):
-        if self.target == "gt":
-            _check_pair(who, x, gt, on_device=True)
-        else:
-            for name, t in (("sr", x), ("lr", gt)):
-                if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                    raise _abi.HipPathError(f"{who}: {name} must be a tensor on a ROCm device (no CPU fallback)")
-                if t.dtype != torch.float32:
-                    raise _abi.HipPathError(f"{who}: {name} must be fp32, got {t.dtype}")
-            if x.dim() != 4 or x.shape[1] != 3 or x.device != gt.device:
-                raise _abi.HipPathError(f"{who}: expected fp32 [B,3,H,W] sr and its LR image on one device, got {tuple(x.shape)} / "
-                                        f"{tuple(gt.shape)}")
+        _check_pair(who, x, gt, on_device=True, second=self.target)
         B, _, H, W = x.shape
         if B < 1 or H < self.scale or W < self.scale:
             raise _abi.HipPathError(f"{who}: images of {W}x{H} are below the {self.scale}-px minimum of scale {self.scale}")
@@ -363,11 +354,10 @@ class BackProjectionLoss(_Term):
     def _launch_fwd(self, x, target, want_grad, per_image=False, clamp_sr=False):
         """The one launch site of sst_bp_loss_fwd -> (loss, per-image fp64 [B] or None, saved or None)."""
         B, _, H, W = x.shape
-        n_saved, n_part = ctypes.c_int64(), ctypes.c_int64()
-        _abi.check(_abi.lib().sst_bp_loss_workspace(B, H, W, self.scale, ctypes.byref(n_saved), ctypes.byref(n_part)), "sst_bp_loss_workspace")
+        n_saved, n_part = _workspace("bp_loss", B, H, W, self.scale, n=2)
         wy, iy, wx, ix = self._tables(x.device, H, W)[:4]
-        partials, counter = ops.reduction_ws(self._ws, (x.device, B, H, W, self.scale), n_part.value)
-        saved = torch.empty(n_saved.value, device=x.device, dtype=torch.float32) if want_grad else None
+        partials, counter = ops.reduction_ws(self._ws, (x.device, B, H, W, self.scale), n_part)
+        saved = torch.empty(n_saved, device=x.device, dtype=torch.float32) if want_grad else None
         loss = torch.empty((), device=x.device, dtype=torch.float32)
         per = torch.empty(B, device=x.device, dtype=torch.float64) if per_image else None
         gt, lr = (target, None) if self.target == "gt" else (None, target)
@@ -385,8 +375,7 @@ class BackProjectionLoss(_Term):
         return loss, saved
 
     def _bwd(self, x, gt, saved, dsr, g, scale_host, accumulate):
-        if saved is None:
-            raise _abi.HipPathError("BackProjectionLoss: the gradient is taken with respect to sr only (the target is a constant)")
+        saved = self._kept(saved)
         B, _, H, W = x.shape
         tw_y, ti_y, tw_x, ti_x = self._tables(x.device, H, W)[4:]
         args = (_abi.ptr(saved), _abi.ptr(dsr), _abi.ptr(tw_y), _abi.ptr(ti_y), _abi.ptr(tw_x), _abi.ptr(ti_x), _abi.ptr(g), float(scale_host),

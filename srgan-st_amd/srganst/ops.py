@@ -480,17 +480,20 @@ def clamp_bwd(g, pre, dbias=None, accumulate=False):
     return out
 
 
-def reduction_ws(ws, key, n_partials, prefix=""):
+def reduction_ws(ws, key, n_partials, prefix="", **extras):
     """The workspace of a last-arriver reduction, kept in the caller's cache dict `ws` under prefix + "key" / "partials" / "counter":
     fp32 partials [n_partials] and a zeroed int32 counter on key[0] (the device), rebuilt only when `key` changes - so a warm-up
     call allocates what a later graph capture touches.  n_partials may be a callable; it is asked on a rebuild only.
-    -> (partials, counter)"""
+    extras (name=floats, e.g. scratch=n): fp32 buffers that live and die with the key, kept under prefix + name.
+    -> (partials, counter, *extras)"""
     if ws.get(prefix + "key") != key:
         n = n_partials() if callable(n_partials) else n_partials
+        for name, floats in extras.items():
+            ws[prefix + name] = torch.empty(floats, device=key[0], dtype=torch.float32)
         ws[prefix + "key"] = key
         ws[prefix + "partials"] = torch.empty(n, device=key[0], dtype=torch.float32)
         ws[prefix + "counter"] = torch.zeros(1, device=key[0], dtype=torch.int32)
-    return ws[prefix + "partials"], ws[prefix + "counter"]
+    return (ws[prefix + "partials"], ws[prefix + "counter"], *(ws[prefix + name] for name in extras))
 
 
 def pixel_loss_fwd(x, gt, mode, ws):

@@ -26,7 +26,7 @@ for p in (ROOT, os.path.join(ROOT, "srgan-st_amd")):
         sys.path.insert(0, p)
 OUT = os.path.join(HERE, "loss_calls.json")
 
-PREFIXES = ("sst_st_", "sst_ssim_", "sst_pixel_loss_", "sst_feat_loss_", "sst_bb", "sst_bicubic", "sst_weighted_sum")
+PREFIXES = ("sst_st_", "sst_ssim_", "sst_freq_", "sst_bp_", "sst_pixel_loss_", "sst_feat_loss_", "sst_bb", "sst_bicubic", "sst_weighted_sum")
 # two 32-px tiles in each direction, both partial in the last row and column, above SSIM's 11-px minimum
 B, H, W = 2, 40, 36
 SEED = 20
@@ -96,13 +96,16 @@ def _hex(t):
     return float(t.detach()).hex()
 
 
-def step(fn, shape=(B, H, W), mode="grad", fuse=True, force_general=False, extra=None):
+def step(fn, shape=(B, H, W), mode="grad", fuse=True, force_general=False, extra=None, second=None):
     """One recorded call of fn(sr, gt) -> total or (total, {name: value} / [values]).  mode: "grad", "no_grad" (under
-    torch.no_grad()) or "no_requires" (sr does not require a gradient)."""
+    torch.no_grad()) or "no_requires" (sr does not require a gradient).  second: gt on the device -> what fn gets in gt's place (made
+    before the recording starts); extra may take (sr, that second argument)."""
     import torch
     sr, gt = images(*shape)
     sr = sr.cuda().requires_grad_(mode != "no_requires")
     gt = gt.cuda()
+    if second is not None:
+        gt = second(gt)
     calls = []
     with _recording(calls, fuse, force_general):
         with torch.no_grad() if mode == "no_grad" else contextlib.nullcontext():
@@ -118,7 +121,7 @@ def step(fn, shape=(B, H, W), mode="grad", fuse=True, force_general=False, extra
         values = [_hex(v) for v in values]
     rec = {"calls": calls, "loss": _hex(total), "values": values, "grad": _sha(sr.grad) if mode == "grad" else None}
     if extra is not None:
-        rec.update(extra())
+        rec.update(extra(sr.detach(), gt) if second is not None else extra())
     return rec
 
 
@@ -212,7 +215,78 @@ def cases():
     out["BestBuddyLoss 42 px (table path)"] = patch(L.BestBuddyLoss, 42)
     out["GramLoss 48 px"] = patch(L.GramLoss, 48)
     out["PatchwiseStructureTensorLoss 48 px"] = patch(L.PatchwiseStructureTensorLoss, 48)
+
+    # --- the Fourier-domain and the back-projection criteria (recorded before their reduction epilogue moved into csrc/common.h)
+    Freq, BP = L.FocalFrequencyLoss, L.BackProjectionLoss
+
+    def modes(make):
+        def run():
+            crit = make()
+            return [step(crit, mode=m) for m in ("grad", "no_grad", "no_requires")]
+        return run
+    out["Frequency(1.0): grad, no_grad, no requires_grad"] = modes(lambda: Freq(1.0))
+    out["Frequency(0.0): grad, no_grad, no requires_grad"] = modes(lambda: Freq(0.0))
+    for scale in L.BP_SCALES:                                                  # 40 x 36 is not a multiple of 8
+        for crit in ("l1", "mse"):
+            alone(f"BP({scale},{crit})", lambda scale=scale, crit=crit: BP(scale, crit))
+    alone("BP(4,l1) round_target=False", lambda: BP(4, "l1", round_target=False))
+
+    def lr_of(scale):
+        from srganst.bicubic import Bicubic
+        return lambda gt: Bicubic()(gt, 1.0 / scale)
+
+    def lr_consistency(sr, lr):
+        from srganst import metrics
+        return {"lr_consistency": _sha(metrics.lr_consistency(sr, lr, 4))}
+    out["BP(4,l1) target=lr, metrics.lr_consistency"] = lambda: [step(BP(4, "l1", target="lr"), second=lr_of(4), extra=lr_consistency)]
+
+    def total_new():
+        crits = OrderedDict([("Pixel", L.MSELoss()), ("Frequency", Freq()), ("BackProjection", BP(4))])
+        weights = {"Pixel": 1.0, "Frequency": 1.0, "BackProjection": 0.1}
+        return [step(lambda sr, gt: engine._criterion_total(sr, gt, crits, weights))]
+    out["engine._criterion_total{MSE, Frequency, BackProjection}"] = total_new
+
+    def reused_alone(make):
+        """reused() for a criterion outside criterion_sum: the B = 1 call re-keys its workspace and its scratch."""
+        def run():
+            crit = make()
+            return [step(crit, shape=s) for s in ((B, H, W), (B, H, W), (1, H, W), (B, H, W))]
+        return run
+    out["SSIM(y) x2, B=1, B=2"] = reused_alone(lambda: L.SSIMLoss("y"))
+    out["Frequency(1.0) x2, B=1, B=2"] = reused_alone(Freq)
+    out["BP(4,l1) x2, B=1, B=2"] = reused_alone(lambda: BP(4))
+
+    # more workgroups than the last arriver has threads (256), and no multiple of them: its strided loop over the partials runs a
+    # second, ragged pass.  The counts are the entries' own (sst_*_workspace: partial floats / 2).
+    for name, make, shape in MANY_PARTIALS:
+        alone(f"{name} at {shape}: {many_partials(name)} partials", make, shape=(shape[0], shape[2], shape[3]))
     return out
+
+
+MANY_PARTIALS = [("SSIM(rgb)", lambda: _loss().SSIMLoss("rgb"), (16, 3, 43, 75)),
+                 ("Frequency(1.0)", lambda: _loss().FocalFrequencyLoss(), (43, 3, 48, 48)),
+                 ("BP(4,l1)", lambda: _loss().BackProjectionLoss(4), (16, 3, 38, 262))]
+
+
+def _loss():
+    from srganst import loss
+    return loss
+
+
+def many_partials(name):
+    """Workgroups of the forward kernel of a MANY_PARTIALS case, asked of the library on the host (no GPU)."""
+    from srganst import _abi
+    lib, n = _abi.lib(), [ctypes.c_int64() for _ in range(3)]
+    r = [ctypes.byref(v) for v in n]
+    (b, _, h, w), = [s for k, _, s in MANY_PARTIALS if k == name]
+    if name.startswith("SSIM"):
+        rc, part = lib.sst_ssim_loss_workspace(b, h, w, 3, r[0], r[1]), n[1]
+    elif name.startswith("Frequency"):
+        rc, part = lib.sst_freq_loss_workspace(b, h, w, r[0], r[1], r[2]), n[2]
+    else:
+        rc, part = lib.sst_bp_loss_workspace(b, h, w, 4, r[0], r[1]), n[1]
+    assert rc == 0 and part.value % 2 == 0 and part.value // 2 > 256 and (part.value // 2) % 256, (name, rc, part.value)
+    return part.value // 2
 
 
 def record():

@@ -7,24 +7,13 @@ import pytest
 import torch
 
 import bp_refs as refs
-from test_abi_symbols import header_decls
+from abi_checks import exported_and_declared, lib as _lib, refused as _refused
 
 NAMES = ("sst_bp_loss_workspace", "sst_bp_loss_fwd", "sst_bp_loss_bwd")
 
 
-def _lib():
-    from srganst import _abi
-    return _abi.lib()
-
-
 def test_symbols_are_exported_and_declared():
-    from srganst import _abi
-    decls = header_decls()
-    lib = ctypes.CDLL(_abi.LIB_PATH)
-    for name in NAMES:
-        assert name in decls and name in _abi.SIGNATURES, name
-        assert hasattr(lib, name), f"{name} not exported by libsrganst.so"
-        assert len(_abi.SIGNATURES[name][1]) == decls[name], name
+    exported_and_declared(NAMES)
     from srganst.loss import BackProjectionLoss
     assert repr(BackProjectionLoss()) == "BackProjectionLoss(scale=4, criterion='l1', round_target=True)"
     assert repr(BackProjectionLoss(2, "mse", False, target="lr")) == "BackProjectionLoss(scale=2, criterion='mse', round_target=False, target='lr')"
@@ -39,13 +28,6 @@ def test_workspace_sizes(B, H, W, s):
     # one fp64 partial (two floats) per workgroup = per band of 8 LR rows, tile of 32 LR columns (16 at x8) and image plane
     tile = 16 if s == 8 else 32
     assert parts.value == 2 * B * 3 * (-(-oh // 8)) * (-(-ow // tile))
-
-
-def _refused(rc, *needles):
-    msg = _lib().sst_last_error().decode()
-    assert rc != 0 and msg, (rc, msg)
-    for n in needles:
-        assert n in msg, msg
 
 
 def test_bad_arguments_are_refused_with_a_message():

@@ -22,10 +22,10 @@ import ctypes
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 import bp_refs as refs
-from conftest import assert_fp64_truth, oracle_grads, rel_err
+import term_checks
+from conftest import assert_fp64_truth, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -249,86 +249,30 @@ def test_per_image_and_loss_come_from_the_same_partials():
 
 # ------------------------------------------------------------------------------------------------ F. determinism and capture
 def test_two_eager_calls_give_equal_bits():
-    for criterion in ("l1", "mse"):
-        x, gt, *_ = refs.case("crop", criterion)
-        a, b = _hip_bits(x, gt, _crit(4, criterion)), _hip_bits(x, gt, _crit(4, criterion))
-        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    cases = [(*refs.case("crop", criterion)[:2], criterion) for criterion in ("l1", "mse")]
+    term_checks.two_calls_give_equal_bits([lambda c=c: _hip_bits(c[0], c[1], _crit(4, c[2])) for c in cases])
 
 
 @pytest.mark.parametrize("criterion", ["l1", "mse"])
 def test_graph_replay_matches_eager(criterion):
-    """Forward + backward captured after one warm-up call on a side stream (which builds the criterion's tables and workspace) and
-    replayed on three inputs copied into the static tensors: loss and gradient bits equal the eager calls' each time, so the ticket
-    counter re-arms inside the graph; nothing is re-allocated."""
+    """The warm-up call builds the criterion's tables as well: they do not move either, and there is one set of them."""
     B, H, W = 2, 48, 40
     inputs = [refs.ssim_refs.images(seed, B, H, W) for seed in (501, 502, 503)]
 
-    def run(crit, xs, gs):
-        loss = crit(xs, gs)
-        (gx,) = torch.autograd.grad(loss, xs)
-        return loss, gx
-
-    eager = []
-    for x, gt in inputs:
-        loss, gx = run(_crit(4, criterion), x.cuda().requires_grad_(True), gt.cuda())
-        eager.append((loss.detach().clone(), gx.clone()))
-    torch.cuda.synchronize()
-    assert not torch.equal(eager[1][0], eager[2][0])
-
-    crit = _crit(4, criterion)
-    xs = inputs[0][0].cuda().requires_grad_(True)
-    gs = inputs[0][1].cuda()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        run(crit, xs, gs)                                                # warm-up: builds the tables, allocates the workspace
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    ptrs = (crit._ws["partials"].data_ptr(), crit._ws["counter"].data_ptr(), *(t.data_ptr() for t in crit._tab[(xs.device, H, W, 4)]))
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        loss, gx = run(crit, xs, gs)
-    assert (crit._ws["partials"].data_ptr(), crit._ws["counter"].data_ptr(), *(t.data_ptr() for t in crit._tab[(xs.device, H, W, 4)])) == ptrs
+    def pointers(crit, xs):
+        return (*term_checks.ws_ptrs(crit, ("partials", "counter")), *(t.data_ptr() for t in crit._tab[(xs.device, H, W, 4)]))
+    crit = term_checks.graph_replay_matches_eager(lambda: _crit(4, criterion), inputs, pointers)
     assert len(crit._tab) == 1
-    for k in (1, 2, 0):
-        with torch.no_grad():
-            xs.copy_(inputs[k][0])
-            gs.copy_(inputs[k][1])
-        graph.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(loss, eager[k][0]), (k, loss, eager[k][0])
-        assert torch.equal(gx, eager[k][1]), k
-    del graph
 
 
 # ------------------------------------------------------------------------------------------------ G. no_grad
 @pytest.mark.parametrize("criterion", ["l1", "mse"])
 def test_no_grad_allocates_and_writes_no_saved_map(criterion, monkeypatch):
-    from srganst import ops
     x, gt, T, s, *_ = refs.case("crop", criterion)
-    xd, gd = x.cuda(), gt.cuda()
-    saved_bytes = 2 * 3 * 24 * 24 * 4
     crit = _crit(s, criterion)
-    xg = xd.clone().requires_grad_(True)
-    with_grad = crit(xg, gd)                                            # also builds the tables and the workspace
-    monkeypatch.setattr(ops, "TRACE_HBM", {})
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    with torch.no_grad():
-        quiet = crit(xg, gd)
-    plain = crit(xd, gd)                                                # grad mode on, sr does not require grad
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    assert torch.equal(quiet, with_grad) and torch.equal(plain, with_grad)
-    assert not quiet.requires_grad and not plain.requires_grad
-    calls = ops.TRACE_HBM["bp_loss_fwd_kernel"]
-    assert len(calls) == 2 and all(keep[3] is None for _, _, keep in calls)        # keep = (x, target, loss, saved, ws, ...)
-    assert all(nbytes == 2.0 * x.numel() * 4 for _, nbytes, _ in calls)            # algorithmic bytes: sr + gt
-    assert peak < saved_bytes, (peak, saved_bytes)                      # only the two 0-dim results were allocated
-    # and through the ABI: a null saved pointer gives the same loss bits
-    raw_loss, _, _, _ = _raw(crit, xd, gt=gd, want_saved=False)
-    assert torch.equal(raw_loss, with_grad.detach())
+    term_checks.no_grad_allocates_and_writes_nothing_saved(
+        monkeypatch, crit, x, gt, saved_bytes=2 * 3 * 24 * 24 * 4, kernel="bp_loss_fwd_kernel",
+        raw_loss=lambda xd, gd: _raw(crit, xd, gt=gd, want_saved=False)[0])
 
 
 # ------------------------------------------------------------------------------------------------ H. NaN
@@ -353,140 +297,31 @@ def test_nan_in_sr(criterion):
 
 
 # ------------------------------------------------------------------------------------------------ I. in the engines
-def _reduced_cfg(rcb=2):
-    from srganst.config import Config
-    cfg = Config()
-    cfg.MODEL.G_N_RCB = rcb
-    return cfg
-
-
 def test_warmup_engine_step_vs_oracle():
-    """One eager warm-up step with Pixel (MSE) + 0.1 BackProjection (mse: the network's 1e-3 on sr would flip L1 signs), B = 4,
-    96 -> 24 px, two residual blocks: SR, the logged values and every parameter gradient against the CPU oracle of
-    mse + 0.1 * restatement (fp64-truth rule)."""
-    from oracle import model as om
-    from srganst.engine import WarmupEngine
-    from srganst.loss import MSELoss
-    from srganst.model import Generator
-    cfg = _reduced_cfg()
-    torch.manual_seed(41)
-    G = Generator(cfg)
-    sd0 = {k: v.clone() for k, v in G.state_dict().items()}
-    gen = torch.Generator().manual_seed(42)
-    gt = torch.rand(4, 3, 96, 96, generator=gen)
-    lr = torch.rand(4, 3, 24, 24, generator=gen)
-    T = refs.on_grid(refs.down(gt, 4))
-
-    def fl(sdx, lr_, gt_):
-        sr_ = om.generator_forward(sdx, lr_, True, {})
-        mse, bp = F.mse_loss(sr_, gt_), refs.bp_loss(sr_, T, 4, "mse")
-        return mse + 0.1 * bp, sr_, mse, bp
-    ins = ((lr, False), (gt, False))
-    _, g32, _, (sr_ref, mse32, bp32) = oracle_grads(fl, sd0, torch.float32, ins)
-    _, g64, _, (_, mse64, bp64) = oracle_grads(fl, sd0, torch.float64, ins)
-    G.cuda().train()
-    eng = WarmupEngine(cfg, G, {"Pixel": MSELoss(), "BackProjection": _crit(4, "mse")}, {"Pixel": 1.0, "BackProjection": 0.1}, use_graph=False)
-    vals = eng.step(gt.cuda(), lr.cuda())
-    assert rel_err(eng.sr.cpu(), sr_ref) < 1e-3
-    assert list(vals) == ["Pixel", "BackProjection"]
-    assert abs(vals["Pixel"].item() - mse64.item()) <= 1e-3 * mse64.item()
-    e = abs(vals["BackProjection"].item() - 0.1 * bp64.item())
-    print(f"[I warm-up] BackProjection term {vals['BackProjection'].item():.7f} oracle fp64 {0.1 * bp64.item():.7f} (fp32 {0.1 * bp32.item():.7f})")
-    assert e <= 1e-3 * 0.1 * bp64.item()                                # SR itself carries 1e-3: the term is not held tighter
-    report = []
-    for n, p in G.named_parameters():
-        assert_fp64_truth(n, p.grad.cpu(), g32[n], g64[n], report)
-    print(f"[I warm-up] worst parameter-gradient error {max(r[1] for r in report):.3e}")
-    eng.close()
+    """mse: the network's 1e-3 on sr would flip L1 signs.  The oracle's target is down(gt) on the 1/255 grid, fp32 at either precision."""
+    term_checks.warmup_engine_step_vs_oracle(lambda: _crit(4, "mse"), "BackProjection", 0.1,
+                                             lambda sr, gt: refs.bp_loss(sr, refs.on_grid(refs.down(gt.float(), 4)), 4, "mse"))
 
 
 def test_warmup_engine_graph_equals_eager():
-    from srganst.engine import WarmupEngine
-    from srganst.loss import MSELoss
-    from srganst.model import Generator
-
-    def run(use_graph):
-        cfg = _reduced_cfg()
-        torch.manual_seed(43)
-        G = Generator(cfg).cuda().train()
-        eng = WarmupEngine(cfg, G, {"Pixel": MSELoss(), "BackProjection": _crit()}, {"Pixel": 1.0, "BackProjection": 0.1},
-                           use_graph=use_graph, adam_capturable=True)
-        gen = torch.Generator().manual_seed(44)
-        logged = []
-        for _ in range(3):
-            gt = torch.rand(4, 3, 96, 96, generator=gen).cuda()
-            lr = torch.rand(4, 3, 24, 24, generator=gen).cuda()
-            logged.append({k: v.item() for k, v in eng.step(gt, lr).items()})
-        torch.cuda.synchronize()
-        assert eng.graph_active == use_graph
-        sd = {k: v.clone() for k, v in G.state_dict().items()}
-        eng.close()
-        return sd, logged
-
-    s1, l1 = run(False)
-    s2, l2 = run(True)
-    for k in s1:
-        assert torch.equal(s1[k], s2[k]), k
-    assert l1 == l2 and all(set(v) == {"Pixel", "BackProjection"} for v in l1)
+    term_checks.warmup_engine_graph_equals_eager(_crit, "BackProjection", 0.1)
 
 
 def test_train_engine_graph_equals_eager():
-    """Adversarial + Pixel + BackProjection ("l1") in a reduced TrainEngine: the criterion sits in the two-branch graph beside the
-    discriminator; replayed and eager steps leave the same bits (the pattern of tests/test_discriminator_gpu.py)."""
-    from srganst.config import Config
-    from srganst.engine import TrainEngine
-    from srganst.loss import MSELoss
-    from srganst.model import Discriminator, Generator
-
-    def run(use_graph):
-        cfg = Config()
-        cfg.MODEL.G_N_CHANNEL, cfg.MODEL.G_N_RCB, cfg.MODEL.D_N_CHANNEL = 16, 2, 8
-        torch.manual_seed(1)
-        D, G = Discriminator(cfg).cuda().train(), Generator(cfg).cuda().train()
-        cfg.add_g_criterion("Pixel", MSELoss(), 1.0)
-        cfg.add_g_criterion("BackProjection", _crit(4, "l1"), 0.1)
-        cfg.SOLVER.D_UPDATE_INTERVAL = 1
-        eng = TrainEngine(cfg, G, D, use_graph=use_graph, adam_capturable=True)
-        gen = torch.Generator().manual_seed(2)
-        for _ in range(4):
-            gt = torch.rand(4, 3, 96, 96, generator=gen).cuda()
-            lr = torch.rand(4, 3, 24, 24, generator=gen).cuda()
-            eng.step(gt, lr)
-        torch.cuda.synchronize()
-        assert eng.graph_active == use_graph
-        return G.state_dict(), D.state_dict(), {k: v.item() for k, v in eng.loss_values.items()}
-
-    g1, d1, l1 = run(False)
-    g2, d2, l2 = run(True)
-    for k in g1:
-        assert torch.equal(g1[k], g2[k]), k
-    for k in d1:
-        assert torch.equal(d1[k], d2[k]), k
-    assert l1 == l2 and set(l1) == {"Adversarial", "Pixel", "BackProjection"}
+    term_checks.train_engine_graph_equals_eager(lambda: _crit(4, "l1"), "BackProjection", 0.1)
 
 
 # ------------------------------------------------------------------------------------------------ J. refusals
 def test_refusals_launch_nothing(monkeypatch):
-    from srganst import ops
-    from srganst._abi import HipPathError
     x, gt = refs.ssim_refs.images(81, 2, 24, 24)
     xd, gd = x.cuda(), gt.cuda()
     crit, crit_lr = _crit(), _crit(target="lr")
     lr = torch.rand(2, 3, 6, 6).cuda()
-    monkeypatch.setattr(ops, "TRACE_HBM", {})
     bad = {"cpu sr": (x, gd), "cpu gt": (xd, gt), "fp64": (xd.double(), gd.double()), "one channel": (xd[:, :1], gd[:, :1]),
-           "H = 3": (xd[:, :, :3], gd[:, :, :3]), "W = 3": (xd[:, :, :, :3], gd[:, :, :, :3]), "shapes differ": (xd, gd[:1])}
-    for name, (a, b) in bad.items():
-        with pytest.raises(HipPathError):
-            crit(a, b)
-    with pytest.raises(HipPathError, match="3x24"):                     # the size is named
-        crit(xd[:, :, :, :3], gd[:, :, :, :3])
+           "H = 3": (xd[:, :, :3], gd[:, :, :3]), "W = 3": (xd[:, :, :, :3], gd[:, :, :, :3], "3x24"),      # the size is named
+           "shapes differ": (xd, gd[:1])}
     bad_lr = {"gt as lr": (xd, gd), "lr 6 x 5": (xd, lr[:, :, :, :5]), "lr batch": (xd, lr[:1]), "cpu lr": (xd, lr.cpu()),
               "fp64 lr": (xd, lr.double()), "H = 3": (xd[:, :, :3], lr[:, :, :0]), "one channel": (xd, lr[:, :1])}
-    for name, (a, b) in bad_lr.items():
-        with pytest.raises(HipPathError):
-            crit_lr(a, b)
-    assert ops.TRACE_HBM == {} and crit._ws == {} and crit_lr._ws == {} and crit._tab == {} and crit_lr._tab == {}
-    assert torch.isfinite(crit(xd[:, :, :4, :4], gd[:, :, :4, :4]))    # the smallest accepted size, non-contiguous views
-    assert torch.isfinite(crit_lr(xd[:, :, :4, :4], lr[:, :, :1, :1]))
-    assert list(ops.TRACE_HBM) == ["bp_loss_fwd_kernel"] and len(ops.TRACE_HBM["bp_loss_fwd_kernel"]) == 2
+    term_checks.refusals_launch_nothing(                                 # accepted: the smallest size, non-contiguous views
+        monkeypatch, [(crit, *pair) for pair in bad.values()] + [(crit_lr, *pair) for pair in bad_lr.values()],
+        [(crit, xd[:, :, :4, :4], gd[:, :, :4, :4]), (crit_lr, xd[:, :, :4, :4], lr[:, :, :1, :1])], "bp_loss_fwd_kernel")

@@ -5,24 +5,13 @@ import ctypes
 
 import pytest
 
-from test_abi_symbols import header_decls
+from abi_checks import exported_and_declared, lib as _lib, refused as _refused
 
 NAMES = ("sst_freq_loss_workspace", "sst_freq_loss_fwd", "sst_freq_loss_bwd")
 
 
-def _lib():
-    from srganst import _abi
-    return _abi.lib()
-
-
 def test_symbols_are_exported_and_declared():
-    from srganst import _abi
-    decls = header_decls()
-    lib = ctypes.CDLL(_abi.LIB_PATH)
-    for name in NAMES:
-        assert name in decls and name in _abi.SIGNATURES, name
-        assert hasattr(lib, name), f"{name} not exported by libsrganst.so"
-        assert len(_abi.SIGNATURES[name][1]) == decls[name], name
+    exported_and_declared(NAMES)
     from srganst.loss import FocalFrequencyLoss, fusable
     assert repr(FocalFrequencyLoss()) == "FocalFrequencyLoss(alpha=1.0)" and repr(FocalFrequencyLoss(2)) == "FocalFrequencyLoss(alpha=2.0)"
     assert not fusable(FocalFrequencyLoss())
@@ -37,13 +26,6 @@ def test_workspace_sizes(B, H, W):
     assert saved.value == S
     assert scratch.value == 2 * S + B * 3 * (-(-Wh // 32)) * (-(-H // 32))
     assert parts.value == 2 * B * 3 * (-(-(H * Wh) // 1024))
-
-
-def _refused(rc, *needles):
-    msg = _lib().sst_last_error().decode()
-    assert rc != 0 and msg, (rc, msg)
-    for n in needles:
-        assert n in msg, msg
 
 
 def test_bad_arguments_are_refused_with_a_message():

@@ -27,10 +27,10 @@ import ctypes
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 import freq_refs as refs
-from conftest import assert_fp64_truth, oracle_grads, rel_err
+import term_checks
+from conftest import assert_fp64_truth, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -212,84 +212,21 @@ def test_scale_and_accumulate(name):
 
 
 def test_two_eager_calls_give_equal_bits():
-    for name in ("ragged", "crop"):
-        x, gt = refs.case_images(name)
-        a, b = _hip(x, gt), _hip(x, gt)
-        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    term_checks.two_calls_give_equal_bits([lambda n=name: _hip(*refs.case_images(n)) for name in ("ragged", "crop")])
 
 
 def test_graph_replay_matches_eager():
-    """Forward + backward captured after one warm-up call on a side stream (which allocates the criterion's workspace) and replayed
-    on three inputs copied into the static tensors: loss and gradient bits equal the eager calls' each time, so the ticket counter
-    re-arms inside the graph; no workspace is re-allocated."""
     from srganst.loss import FocalFrequencyLoss
-    B, H, W = 2, 48, 37
-    inputs = [refs.images(seed, B, H, W) for seed in (501, 502, 503)]
-
-    def run(crit, xs, gs):
-        loss = crit(xs, gs)
-        (gx,) = torch.autograd.grad(loss, xs)
-        return loss, gx
-
-    eager = []
-    for x, gt in inputs:
-        loss, gx = run(FocalFrequencyLoss(), x.cuda().requires_grad_(True), gt.cuda())
-        eager.append((loss.detach().clone(), gx.clone()))
-    torch.cuda.synchronize()
-    assert not torch.equal(eager[1][0], eager[2][0])
-
-    crit = FocalFrequencyLoss()
-    xs = inputs[0][0].cuda().requires_grad_(True)
-    gs = inputs[0][1].cuda()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        run(crit, xs, gs)                                                # warm-up: allocates the workspace
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    ptrs = tuple(crit._ws[k].data_ptr() for k in ("scratch", "partials", "counter"))
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        loss, gx = run(crit, xs, gs)
-    assert tuple(crit._ws[k].data_ptr() for k in ("scratch", "partials", "counter")) == ptrs
-    for k in (1, 2, 0):
-        with torch.no_grad():
-            xs.copy_(inputs[k][0])
-            gs.copy_(inputs[k][1])
-        graph.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(loss, eager[k][0]), (k, loss, eager[k][0])
-        assert torch.equal(gx, eager[k][1]), k
-    del graph
+    inputs = [refs.images(seed, 2, 48, 37) for seed in (501, 502, 503)]
+    term_checks.graph_replay_matches_eager(FocalFrequencyLoss, inputs,
+                                           lambda crit, xs: term_checks.ws_ptrs(crit, ("scratch", "partials", "counter")))
 
 
 def test_no_grad_allocates_and_writes_no_spectrum(monkeypatch):
-    from srganst import ops
     from srganst.loss import FocalFrequencyLoss
-    x, gt = refs.images(61, 2, 96, 96)
-    xd, gd = x.cuda(), gt.cuda()
-    saved_bytes = 2 * 3 * 96 * 49 * 2 * 4
-    crit = FocalFrequencyLoss()
-    xg = xd.clone().requires_grad_(True)
-    with_grad = crit(xg, gd)                                            # also allocates the workspace
-    monkeypatch.setattr(ops, "TRACE_HBM", {})
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    with torch.no_grad():
-        quiet = crit(xg, gd)
-    plain = crit(xd, gd)                                                # grad mode on, sr does not require grad
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    assert torch.equal(quiet, with_grad) and torch.equal(plain, with_grad)
-    assert not quiet.requires_grad and not plain.requires_grad
-    assert list(ops.TRACE_HBM) == ["freq_weight_kernel"]               # two forward entries, no backward
-    calls = ops.TRACE_HBM["freq_weight_kernel"]
-    assert len(calls) == 2 and all(keep[3] is None for _, _, keep in calls)        # keep = (x, gt, loss, saved, ws)
-    assert peak < saved_bytes, (peak, saved_bytes)                      # only the two 0-dim results were allocated
-    # and through the ABI: a null pointer for the saved spectrum gives the same loss bits
-    raw_loss, _, _, _ = _raw(xd, gd, want_saved=False)
-    assert torch.equal(raw_loss, with_grad.detach())
+    term_checks.no_grad_allocates_and_writes_nothing_saved(
+        monkeypatch, FocalFrequencyLoss(), *refs.images(61, 2, 96, 96), saved_bytes=2 * 3 * 96 * 49 * 2 * 4, kernel="freq_weight_kernel",
+        raw_loss=lambda xd, gd: _raw(xd, gd, want_saved=False)[0])
 
 
 def test_nan_in_sr():
@@ -305,134 +242,32 @@ def test_nan_in_sr():
 
 
 # ------------------------------------------------------------------------------------------------ E. in the engines
-def _reduced_cfg(rcb=2):
-    from srganst.config import Config
-    cfg = Config()
-    cfg.MODEL.G_N_RCB = rcb
-    return cfg
+def _freq():
+    from srganst.loss import FocalFrequencyLoss
+    return FocalFrequencyLoss()
 
 
 def test_warmup_engine_step_vs_oracle():
-    """One eager warm-up step with Pixel (MSE) + 1.0 Frequency, B = 4, 96 -> 24 px, two residual blocks: SR, the logged values and
-    every parameter gradient against the CPU oracle of mse + restatement (fp64-truth rule)."""
-    from oracle import model as om
-    from srganst.engine import WarmupEngine
-    from srganst.loss import FocalFrequencyLoss, MSELoss
-    from srganst.model import Generator
-    cfg = _reduced_cfg()
-    torch.manual_seed(41)
-    G = Generator(cfg)
-    sd0 = {k: v.clone() for k, v in G.state_dict().items()}
-    gen = torch.Generator().manual_seed(42)
-    gt = torch.rand(4, 3, 96, 96, generator=gen)
-    lr = torch.rand(4, 3, 24, 24, generator=gen)
-
-    def fl(sdx, lr_, gt_):
-        sr_ = om.generator_forward(sdx, lr_, True, {})
-        mse, fq = F.mse_loss(sr_, gt_), refs.freq_loss(sr_, gt_)
-        return mse + 1.0 * fq, sr_, mse, fq
-    ins = ((lr, False), (gt, False))
-    _, g32, _, (sr_ref, mse32, fq32) = oracle_grads(fl, sd0, torch.float32, ins)
-    _, g64, _, (_, mse64, fq64) = oracle_grads(fl, sd0, torch.float64, ins)
-    G.cuda().train()
-    eng = WarmupEngine(cfg, G, {"Pixel": MSELoss(), "Frequency": FocalFrequencyLoss()}, {"Pixel": 1.0, "Frequency": 1.0}, use_graph=False)
-    vals = eng.step(gt.cuda(), lr.cuda())
-    assert rel_err(eng.sr.cpu(), sr_ref) < 1e-3
-    assert list(vals) == ["Pixel", "Frequency"]
-    assert abs(vals["Pixel"].item() - mse64.item()) <= 1e-3 * mse64.item()
-    e = abs(vals["Frequency"].item() - fq64.item())
-    print(f"[E warm-up] Frequency term {vals['Frequency'].item():.7e} oracle fp64 {fq64.item():.7e} (fp32 {fq32.item():.7e})")
-    assert e <= 1e-3 * fq64.item()
-    report = []
-    for n, p in G.named_parameters():
-        assert_fp64_truth(n, p.grad.cpu(), g32[n], g64[n], report)
-    print(f"[E warm-up] worst parameter-gradient error {max(r[1] for r in report):.3e}")
-    eng.close()
+    term_checks.warmup_engine_step_vs_oracle(_freq, "Frequency", 1.0, refs.freq_loss)
 
 
 def test_warmup_engine_graph_equals_eager():
-    from srganst.engine import WarmupEngine
-    from srganst.loss import FocalFrequencyLoss, MSELoss
-    from srganst.model import Generator
-
-    def run(use_graph):
-        cfg = _reduced_cfg()
-        torch.manual_seed(43)
-        G = Generator(cfg).cuda().train()
-        eng = WarmupEngine(cfg, G, {"Pixel": MSELoss(), "Frequency": FocalFrequencyLoss()}, {"Pixel": 1.0, "Frequency": 1.0},
-                           use_graph=use_graph, adam_capturable=True)
-        gen = torch.Generator().manual_seed(44)
-        logged = []
-        for _ in range(3):
-            gt = torch.rand(4, 3, 96, 96, generator=gen).cuda()
-            lr = torch.rand(4, 3, 24, 24, generator=gen).cuda()
-            logged.append({k: v.item() for k, v in eng.step(gt, lr).items()})
-        torch.cuda.synchronize()
-        assert eng.graph_active == use_graph
-        sd = {k: v.clone() for k, v in G.state_dict().items()}
-        eng.close()
-        return sd, logged
-
-    s1, l1 = run(False)
-    s2, l2 = run(True)
-    for k in s1:
-        assert torch.equal(s1[k], s2[k]), k
-    assert l1 == l2 and all(set(v) == {"Pixel", "Frequency"} for v in l1)
+    term_checks.warmup_engine_graph_equals_eager(_freq, "Frequency", 1.0)
 
 
 def test_train_engine_graph_equals_eager():
-    """Adversarial + Pixel + Frequency in a reduced TrainEngine: the criterion sits in the two-branch graph beside the discriminator;
-    replayed and eager steps leave the same bits (the pattern of tests/test_discriminator_gpu.py)."""
-    from srganst.config import Config
-    from srganst.engine import TrainEngine
-    from srganst.loss import FocalFrequencyLoss, MSELoss
-    from srganst.model import Discriminator, Generator
-
-    def run(use_graph):
-        cfg = Config()
-        cfg.MODEL.G_N_CHANNEL, cfg.MODEL.G_N_RCB, cfg.MODEL.D_N_CHANNEL = 16, 2, 8
-        torch.manual_seed(1)
-        D, G = Discriminator(cfg).cuda().train(), Generator(cfg).cuda().train()
-        cfg.add_g_criterion("Pixel", MSELoss(), 1.0)
-        cfg.add_g_criterion("Frequency", FocalFrequencyLoss(), 1.0)
-        cfg.SOLVER.D_UPDATE_INTERVAL = 1
-        eng = TrainEngine(cfg, G, D, use_graph=use_graph, adam_capturable=True)
-        gen = torch.Generator().manual_seed(2)
-        for _ in range(4):
-            gt = torch.rand(4, 3, 96, 96, generator=gen).cuda()
-            lr = torch.rand(4, 3, 24, 24, generator=gen).cuda()
-            eng.step(gt, lr)
-        torch.cuda.synchronize()
-        assert eng.graph_active == use_graph
-        return G.state_dict(), D.state_dict(), {k: v.item() for k, v in eng.loss_values.items()}
-
-    g1, d1, l1 = run(False)
-    g2, d2, l2 = run(True)
-    for k in g1:
-        assert torch.equal(g1[k], g2[k]), k
-    for k in d1:
-        assert torch.equal(d1[k], d2[k]), k
-    assert l1 == l2 and set(l1) == {"Adversarial", "Pixel", "Frequency"}
+    term_checks.train_engine_graph_equals_eager(_freq, "Frequency", 1.0)
 
 
 # ------------------------------------------------------------------------------------------------ F. refusals
 def test_refusals_launch_nothing(monkeypatch):
-    from srganst import ops
-    from srganst._abi import HipPathError
-    from srganst.loss import FocalFrequencyLoss
     x, gt = refs.images(81, 2, 24, 24)
     xd, gd = x.cuda(), gt.cuda()
     tall, wide = torch.zeros(1, 3, 513, 4, device="cuda"), torch.zeros(1, 3, 4, 513, device="cuda")
-    crit = FocalFrequencyLoss()
-    monkeypatch.setattr(ops, "TRACE_HBM", {})
+    crit = _freq()
     bad = {"cpu sr": (x, gd), "cpu gt": (xd, gt), "fp64": (xd.double(), gd.double()), "one channel": (xd[:, :1], gd[:, :1]),
-           "shapes differ": (xd, gd[:1]), "H = 513": (tall, tall.clone()), "W = 513": (wide, wide.clone())}
-    for name, (a, b) in bad.items():
-        with pytest.raises(HipPathError) as info:
-            crit(a, b)
-        if "513" in name:
-            assert ("size 513x4 not built" if name[0] == "H" else "size 4x513 not built") in str(info.value)
-    assert ops.TRACE_HBM == {} and crit._ws == {}
-    assert torch.isfinite(crit(xd[:, :, :1, :1], gd[:, :, :1, :1]))        # the smallest accepted size, non-contiguous views
-    assert torch.isfinite(crit(xd[:, :, 3:20, 1:24:2], gd[:, :, 3:20, 1:24:2]))
-    assert list(ops.TRACE_HBM) == ["freq_weight_kernel"]
+           "shapes differ": (xd, gd[:1]), "H = 513": (tall, tall.clone(), "size 513x4 not built"),
+           "W = 513": (wide, wide.clone(), "size 4x513 not built")}
+    term_checks.refusals_launch_nothing(                                 # accepted: the smallest size, non-contiguous views
+        monkeypatch, [(crit, *pair) for pair in bad.values()],
+        [(crit, xd[:, :, :1, :1], gd[:, :, :1, :1]), (crit, xd[:, :, 3:20, 1:24:2], gd[:, :, 3:20, 1:24:2])], "freq_weight_kernel")

@@ -1,7 +1,8 @@
 """What the criteria ask of the library, against the record taken from the commit before the pixel-space criteria were gathered
 behind one term protocol (tests/golden/loss_calls.json, written by tests/golden/make_golden_loss_calls.py): per case the same calls
-with the same arguments in the same order, the same loss and weighted values bit for bit, and the same bytes in sr.grad.  Then, with
-no fixture: each of the ten loss entries is called from exactly one place in the package."""
+with the same arguments in the same order, the same loss and weighted values bit for bit, and the same bytes in sr.grad; the
+Fourier-domain and the back-projection criteria against the record taken before their reduction epilogue moved into csrc/common.h.
+Then, with no fixture: each of the fourteen loss entries is called from exactly one place in the package."""
 import importlib.util
 import json
 import os
@@ -18,7 +19,8 @@ _spec.loader.exec_module(mglc)
 with open(os.path.join(GOLDEN, "loss_calls.json")) as _f:
     RECORDED = json.load(_f)
 PACKAGE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "srgan-st_amd", "srganst")
-ONE_SITE = [f"sst_{name}_{d}" for name in ("st_loss", "st_pixel_loss", "st_general", "ssim_loss", "pixel_loss") for d in ("fwd", "bwd")]
+ONE_SITE = [f"sst_{name}_{d}" for name in ("st_loss", "st_pixel_loss", "st_general", "ssim_loss", "freq_loss", "bp_loss", "pixel_loss")
+            for d in ("fwd", "bwd")]
 
 
 def test_the_fixture_holds_the_cases_of_the_generator():

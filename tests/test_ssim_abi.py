@@ -4,24 +4,13 @@ import ctypes
 
 import pytest
 
-from test_abi_symbols import header_decls
+from abi_checks import exported_and_declared, lib as _lib, refused as _refused
 
 NAMES = ("sst_ssim_loss_workspace", "sst_ssim_loss_fwd", "sst_ssim_loss_bwd")
 
 
-def _lib():
-    from srganst import _abi
-    return _abi.lib()
-
-
 def test_symbols_are_exported_and_declared():
-    from srganst import _abi
-    decls = header_decls()
-    lib = ctypes.CDLL(_abi.LIB_PATH)
-    for name in NAMES:
-        assert name in decls and name in _abi.SIGNATURES, name
-        assert hasattr(lib, name), f"{name} not exported by libsrganst.so"
-        assert len(_abi.SIGNATURES[name][1]) == decls[name], name
+    exported_and_declared(NAMES)
     from srganst.loss import SSIMLoss
     assert repr(SSIMLoss()) == "SSIMLoss(channel='y', k1=0.01, k2=0.03)"
 
@@ -34,13 +23,6 @@ def test_workspace_sizes(B, H, W, planes):
     assert maps.value == B * planes * (H - 10) * (W - 10) * 3
     # one fp64 partial (two floats) per workgroup = per 32 x 32 tile of outputs, plane and image
     assert parts.value == 2 * B * planes * (-(-(H - 10) // 32)) * (-(-(W - 10) // 32))
-
-
-def _refused(rc, *needles):
-    msg = _lib().sst_last_error().decode()
-    assert rc != 0 and msg, (rc, msg)
-    for n in needles:
-        assert n in msg, msg
 
 
 def test_bad_arguments_are_refused_with_a_message():

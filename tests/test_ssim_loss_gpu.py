@@ -18,10 +18,10 @@ import ctypes
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 import ssim_refs as refs
-from conftest import assert_fp64_truth, oracle_grads, rel_err
+import term_checks
+from conftest import assert_fp64_truth, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -169,86 +169,25 @@ def test_scale_and_accumulate(planes):
 
 # ------------------------------------------------------------------------------------------------ E. determinism and capture
 def test_two_eager_calls_give_equal_bits():
-    for channel in ("y", "rgb"):
-        x, gt, *_ = refs.case("ragged", channel)
-        a, b = _hip(x, gt, channel), _hip(x, gt, channel)
-        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    cases = [(*refs.case("ragged", channel)[:2], channel) for channel in ("y", "rgb")]
+    term_checks.two_calls_give_equal_bits([lambda c=c: _hip(*c) for c in cases])
 
 
 @pytest.mark.parametrize("channel", ["y", "rgb"])
 def test_graph_replay_matches_eager(channel):
-    """Forward + backward captured after one warm-up call on a side stream (which allocates the criterion's workspace) and replayed
-    on three inputs copied into the static tensors: loss and gradient bits equal the eager calls' each time, so the ticket counter
-    re-arms inside the graph; no workspace is re-allocated."""
     from srganst.loss import SSIMLoss
-    B, H, W = 2, 48, 40
-    inputs = [refs.images(seed, B, H, W) for seed in (501, 502, 503)]
-
-    def run(crit, xs, gs):
-        loss = crit(xs, gs)
-        (gx,) = torch.autograd.grad(loss, xs)
-        return loss, gx
-
-    eager = []
-    for x, gt in inputs:
-        loss, gx = run(SSIMLoss(channel), x.cuda().requires_grad_(True), gt.cuda())
-        eager.append((loss.detach().clone(), gx.clone()))
-    torch.cuda.synchronize()
-    assert not torch.equal(eager[1][0], eager[2][0])
-
-    crit = SSIMLoss(channel)
-    xs = inputs[0][0].cuda().requires_grad_(True)
-    gs = inputs[0][1].cuda()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        run(crit, xs, gs)                                                # warm-up: allocates the workspace
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    ptrs = (crit._ws["partials"].data_ptr(), crit._ws["counter"].data_ptr())
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        loss, gx = run(crit, xs, gs)
-    assert (crit._ws["partials"].data_ptr(), crit._ws["counter"].data_ptr()) == ptrs
-    for k in (1, 2, 0):
-        with torch.no_grad():
-            xs.copy_(inputs[k][0])
-            gs.copy_(inputs[k][1])
-        graph.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(loss, eager[k][0]), (k, loss, eager[k][0])
-        assert torch.equal(gx, eager[k][1]), k
-    del graph
+    inputs = [refs.images(seed, 2, 48, 40) for seed in (501, 502, 503)]
+    term_checks.graph_replay_matches_eager(lambda: SSIMLoss(channel), inputs, lambda crit, xs: term_checks.ws_ptrs(crit, ("partials", "counter")))
 
 
 # ------------------------------------------------------------------------------------------------ F. no_grad
 @pytest.mark.parametrize("channel", ["y", "rgb"])
 def test_no_grad_allocates_and_writes_no_maps(channel, monkeypatch):
-    from srganst import ops
     from srganst.loss import SSIMLoss
-    x, gt = refs.images(61, 2, 96, 96)
-    xd, gd = x.cuda(), gt.cuda()
-    map_bytes = 2 * (1 if channel == "y" else 3) * 86 * 86 * 3 * 4
-    crit = SSIMLoss(channel)
-    xg = xd.clone().requires_grad_(True)
-    with_grad = crit(xg, gd)                                            # also allocates the workspace
-    monkeypatch.setattr(ops, "TRACE_HBM", {})
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    base = torch.cuda.memory_allocated()
-    with torch.no_grad():
-        quiet = crit(xg, gd)
-    plain = crit(xd, gd)                                                # grad mode on, sr does not require grad
-    torch.cuda.synchronize()
-    peak = torch.cuda.max_memory_allocated() - base
-    assert torch.equal(quiet, with_grad) and torch.equal(plain, with_grad)
-    assert not quiet.requires_grad and not plain.requires_grad
-    calls = ops.TRACE_HBM["ssim_loss_fwd_kernel"]
-    assert len(calls) == 2 and all(keep[3] is None for _, _, keep in calls)        # keep = (x, gt, loss, maps, ws)
-    assert peak < map_bytes, (peak, map_bytes)                          # only the two 0-dim results were allocated
-    # and through the ABI: a null maps pointer gives the same loss bits
-    raw_loss, _, _ = _raw(xd, gd, 1 if channel == "y" else 3, want_maps=False)
-    assert torch.equal(raw_loss, with_grad.detach())
+    planes = 1 if channel == "y" else 3
+    term_checks.no_grad_allocates_and_writes_nothing_saved(
+        monkeypatch, SSIMLoss(channel), *refs.images(61, 2, 96, 96), saved_bytes=2 * planes * 86 * 86 * 3 * 4, kernel="ssim_loss_fwd_kernel",
+        raw_loss=lambda xd, gd: _raw(xd, gd, planes, want_maps=False)[0])
 
 
 # ------------------------------------------------------------------------------------------------ G. NaN
@@ -268,130 +207,29 @@ def test_nan_in_sr(channel):
 
 
 # ------------------------------------------------------------------------------------------------ H. in the engines
-def _reduced_cfg(rcb=2):
-    from srganst.config import Config
-    cfg = Config()
-    cfg.MODEL.G_N_RCB = rcb
-    return cfg
+def _ssim():
+    from srganst.loss import SSIMLoss
+    return SSIMLoss()
 
 
 def test_warmup_engine_step_vs_oracle():
-    """One eager warm-up step with Pixel (MSE) + 0.1 SSIM, B = 4, 96 -> 24 px, two residual blocks: SR, the logged values and every
-    parameter gradient against the CPU oracle of mse + 0.1 * restatement (fp64-truth rule)."""
-    from oracle import model as om
-    from srganst.engine import WarmupEngine
-    from srganst.loss import MSELoss, SSIMLoss
-    from srganst.model import Generator
-    cfg = _reduced_cfg()
-    torch.manual_seed(41)
-    G = Generator(cfg)
-    sd0 = {k: v.clone() for k, v in G.state_dict().items()}
-    gen = torch.Generator().manual_seed(42)
-    gt = torch.rand(4, 3, 96, 96, generator=gen)
-    lr = torch.rand(4, 3, 24, 24, generator=gen)
-
-    def fl(sdx, lr_, gt_):
-        sr_ = om.generator_forward(sdx, lr_, True, {})
-        mse, ssim = F.mse_loss(sr_, gt_), refs.ssim_loss(sr_, gt_, "y")
-        return mse + 0.1 * ssim, sr_, mse, ssim
-    ins = ((lr, False), (gt, False))
-    _, g32, _, (sr_ref, mse32, ssim32) = oracle_grads(fl, sd0, torch.float32, ins)
-    _, g64, _, (_, mse64, ssim64) = oracle_grads(fl, sd0, torch.float64, ins)
-    G.cuda().train()
-    eng = WarmupEngine(cfg, G, {"Pixel": MSELoss(), "SSIM": SSIMLoss()}, {"Pixel": 1.0, "SSIM": 0.1}, use_graph=False)
-    vals = eng.step(gt.cuda(), lr.cuda())
-    assert rel_err(eng.sr.cpu(), sr_ref) < 1e-3
-    assert list(vals) == ["Pixel", "SSIM"]
-    assert abs(vals["Pixel"].item() - mse64.item()) <= 1e-3 * mse64.item()
-    e = abs(vals["SSIM"].item() - 0.1 * ssim64.item())
-    print(f"[H warm-up] SSIM term {vals['SSIM'].item():.7f} oracle fp64 {0.1 * ssim64.item():.7f} (fp32 {0.1 * ssim32.item():.7f})")
-    assert e <= 1e-3 * 0.1 * ssim64.item()                              # SR itself carries 1e-3: the term is not held tighter
-    report = []
-    for n, p in G.named_parameters():
-        assert_fp64_truth(n, p.grad.cpu(), g32[n], g64[n], report)
-    print(f"[H warm-up] worst parameter-gradient error {max(r[1] for r in report):.3e}")
-    eng.close()
+    term_checks.warmup_engine_step_vs_oracle(_ssim, "SSIM", 0.1, lambda sr, gt: refs.ssim_loss(sr, gt, "y"))
 
 
 def test_warmup_engine_graph_equals_eager():
-    from srganst.engine import WarmupEngine
-    from srganst.loss import MSELoss, SSIMLoss
-    from srganst.model import Generator
-
-    def run(use_graph):
-        cfg = _reduced_cfg()
-        torch.manual_seed(43)
-        G = Generator(cfg).cuda().train()
-        eng = WarmupEngine(cfg, G, {"Pixel": MSELoss(), "SSIM": SSIMLoss()}, {"Pixel": 1.0, "SSIM": 0.1}, use_graph=use_graph,
-                           adam_capturable=True)
-        gen = torch.Generator().manual_seed(44)
-        logged = []
-        for _ in range(3):
-            gt = torch.rand(4, 3, 96, 96, generator=gen).cuda()
-            lr = torch.rand(4, 3, 24, 24, generator=gen).cuda()
-            logged.append({k: v.item() for k, v in eng.step(gt, lr).items()})
-        torch.cuda.synchronize()
-        assert eng.graph_active == use_graph
-        sd = {k: v.clone() for k, v in G.state_dict().items()}
-        eng.close()
-        return sd, logged
-
-    s1, l1 = run(False)
-    s2, l2 = run(True)
-    for k in s1:
-        assert torch.equal(s1[k], s2[k]), k
-    assert l1 == l2 and all(set(v) == {"Pixel", "SSIM"} for v in l1)
+    term_checks.warmup_engine_graph_equals_eager(_ssim, "SSIM", 0.1)
 
 
 def test_train_engine_graph_equals_eager():
-    """Adversarial + Pixel + SSIM in a reduced TrainEngine: the criterion sits in the two-branch graph beside the discriminator;
-    replayed and eager steps leave the same bits (the pattern of tests/test_discriminator_gpu.py)."""
-    from srganst.config import Config
-    from srganst.engine import TrainEngine
-    from srganst.loss import MSELoss, SSIMLoss
-    from srganst.model import Discriminator, Generator
-
-    def run(use_graph):
-        cfg = Config()
-        cfg.MODEL.G_N_CHANNEL, cfg.MODEL.G_N_RCB, cfg.MODEL.D_N_CHANNEL = 16, 2, 8
-        torch.manual_seed(1)
-        D, G = Discriminator(cfg).cuda().train(), Generator(cfg).cuda().train()
-        cfg.add_g_criterion("Pixel", MSELoss(), 1.0)
-        cfg.add_g_criterion("SSIM", SSIMLoss(), 0.1)
-        cfg.SOLVER.D_UPDATE_INTERVAL = 1
-        eng = TrainEngine(cfg, G, D, use_graph=use_graph, adam_capturable=True)
-        gen = torch.Generator().manual_seed(2)
-        for _ in range(4):
-            gt = torch.rand(4, 3, 96, 96, generator=gen).cuda()
-            lr = torch.rand(4, 3, 24, 24, generator=gen).cuda()
-            eng.step(gt, lr)
-        torch.cuda.synchronize()
-        assert eng.graph_active == use_graph
-        return G.state_dict(), D.state_dict(), {k: v.item() for k, v in eng.loss_values.items()}
-
-    g1, d1, l1 = run(False)
-    g2, d2, l2 = run(True)
-    for k in g1:
-        assert torch.equal(g1[k], g2[k]), k
-    for k in d1:
-        assert torch.equal(d1[k], d2[k]), k
-    assert l1 == l2 and set(l1) == {"Adversarial", "Pixel", "SSIM"}
+    term_checks.train_engine_graph_equals_eager(_ssim, "SSIM", 0.1)
 
 
 # ------------------------------------------------------------------------------------------------ I. refusals
 def test_refusals_launch_nothing(monkeypatch):
-    from srganst import ops
-    from srganst._abi import HipPathError
-    from srganst.loss import SSIMLoss
     x, gt = refs.images(81, 2, 24, 24)
     xd, gd = x.cuda(), gt.cuda()
-    crit = SSIMLoss()
-    monkeypatch.setattr(ops, "TRACE_HBM", {})
+    crit = _ssim()
     bad = {"cpu sr": (x, gd), "cpu gt": (xd, gt), "fp64": (xd.double(), gd.double()), "one channel": (xd[:, :1], gd[:, :1]),
            "H = 10": (xd[:, :, :10], gd[:, :, :10]), "W = 10": (xd[:, :, :, :10], gd[:, :, :, :10]), "shapes differ": (xd, gd[:1])}
-    for name, (a, b) in bad.items():
-        with pytest.raises(HipPathError):
-            crit(a, b)
-    assert ops.TRACE_HBM == {} and crit._ws == {}
-    assert torch.isfinite(crit(xd[:, :, :11, :11], gd[:, :, :11, :11]))    # the smallest accepted size, non-contiguous views
-    assert list(ops.TRACE_HBM) == ["ssim_loss_fwd_kernel"]
+    term_checks.refusals_launch_nothing(monkeypatch, [(crit, a, b) for a, b in bad.values()],
+                                        [(crit, xd[:, :, :11, :11], gd[:, :, :11, :11])], "ssim_loss_fwd_kernel")

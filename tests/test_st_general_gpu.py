@@ -17,6 +17,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import term_checks
 from conftest import rel_err, truth_bound
 
 pytestmark = pytest.mark.gpu
@@ -388,47 +389,15 @@ def test_graph_replay_matches_eager():
     the ticket counter re-arms inside the graph.  Everything is launched on the capturing stream: one chain, no side streams."""
     from srganst import loss as sl
     sigma, rho = 1.5, 3.0
-    B, H, W = 2, 48, 40
-    inputs = [_images(seed, B, H, W) for seed in (501, 502, 503)]
+    inputs = [_images(seed, 2, 48, 40) for seed in (501, 502, 503)]
     assert all(_frac_l2_above_1(x, gt, sigma, rho, True) >= 0.1 for x, gt in inputs)
-    weights = [1 / 3, 1.0]
 
     def run(terms, xs, gs):
-        total, weighted = sl.criterion_sum(xs, gs, terms, weights)
+        total, weighted = sl.criterion_sum(xs, gs, terms, [1 / 3, 1.0])
         (gx,) = torch.autograd.grad(total, xs)
         return total, weighted, gx
-
-    eager = []
-    for x, gt in inputs:
-        terms = [sl.StructureTensorLoss(sigma, rho), sl.MSELoss()]
-        total, weighted, gx = run(terms, x.cuda().requires_grad_(True), gt.cuda())
-        eager.append((total.detach().clone(), weighted.clone(), gx.clone()))
-    torch.cuda.synchronize()
-    assert not torch.equal(eager[1][0], eager[2][0])
-
-    terms = [sl.StructureTensorLoss(sigma, rho), sl.MSELoss()]
-    xs = inputs[0][0].cuda().requires_grad_(True)
-    gs = inputs[0][1].cuda()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        run(terms, xs, gs)                                               # warm-up: allocates the workspace
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    ws_ptr = terms[0]._ws["general_scratch"].data_ptr()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        total, weighted, gx = run(terms, xs, gs)
-    assert terms[0]._ws["general_scratch"].data_ptr() == ws_ptr          # nothing of the workspace was re-allocated in the capture
-    for k in (1, 2, 1):
-        with torch.no_grad():
-            xs.copy_(inputs[k][0])
-            gs.copy_(inputs[k][1])
-        graph.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(total, eager[k][0]) and torch.equal(weighted, eager[k][1]), (k, total, eager[k][0])
-        assert torch.equal(gx, eager[k][2]), k
-    del graph
+    term_checks.graph_replay_matches_eager(lambda: [sl.StructureTensorLoss(sigma, rho), sl.MSELoss()], inputs,
+                                           lambda terms, xs: term_checks.ws_ptrs(terms[0], ("general_scratch",)), run, order=(1, 2, 1))
 
 
 # ------------------------------------------------------------------------------------------------ J. beyond the bound
