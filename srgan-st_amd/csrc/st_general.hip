@@ -27,12 +27,11 @@
 
 namespace {
 
-constexpr int GT = 32;                   // output tile edge of every pass
 constexpr int GNT = 256;                 // threads per workgroup
-constexpr int GPP = GT * GT / GNT;       // outputs per thread
+constexpr int GPP = T * T / GNT;       // outputs per thread
 constexpr int MAXR1 = 8, MAXR2 = 20;     // the bound of this path
-constexpr int S1 = GT * (GT + 2 * MAXR1);   // floats of one staged strip, derivative / integration radius
-constexpr int S2 = GT * (GT + 2 * MAXR2);
+constexpr int S1 = T * (T + 2 * MAXR1);   // floats of one staged strip, derivative / integration radius
+constexpr int S2 = T * (T + 2 * MAXR2);
 
 struct StgTaps {
   float g[2 * MAXR1 + 1];
@@ -50,17 +49,17 @@ __device__ __forceinline__ float* part(const Split& s, int n, size_t per) {
   return n < s.nb ? s.a + (size_t)n * per : s.b + (size_t)(n - s.nb) * per;
 }
 
-// Strip for a pass along H: s[GT + 2r][GT] = plane rows y0 - r .., columns x0 ..; zero outside the image.
+// Strip for a pass along H: s[T + 2r][T] = plane rows y0 - r .., columns x0 ..; zero outside the image.
 __device__ __forceinline__ void stage_cols(const float* __restrict__ p, int H, int W, int y0, int x0, int r, float* s) {
-  const int n = (GT + 2 * r) * GT;
+  const int n = (T + 2 * r) * T;
   for (int i = threadIdx.x; i < n; i += GNT) {
     const int y = y0 - r + (i >> 5), x = x0 + (i & 31);
     s[i] = ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) ? p[(size_t)y * W + x] : 0.f;
   }
 }
-// Strip for a pass along W: s[GT][GT + 2r] = plane rows y0 .., columns x0 - r ..; zero outside the image.
+// Strip for a pass along W: s[T][T + 2r] = plane rows y0 .., columns x0 - r ..; zero outside the image.
 __device__ __forceinline__ void stage_rows(const float* __restrict__ p, int H, int W, int y0, int x0, int r, float* s) {
-  const int rs = GT + 2 * r, n = GT * rs;
+  const int rs = T + 2 * r, n = T * rs;
   for (int i = threadIdx.x; i < n; i += GNT) {
     const int pr = i / rs, pc = i - pr * rs;
     const int y = y0 + pr, x = x0 - r + pc;
@@ -79,10 +78,10 @@ __global__ __launch_bounds__(GNT) void stg_gray_hpass_kernel(const float* __rest
                                                              float* __restrict__ A1, float* __restrict__ A2, int H, int W, int r1,
                                                              StgTaps tp) {
   __shared__ float s[S1];
-  const int n = blockIdx.z, y0 = blockIdx.y * GT, x0 = blockIdx.x * GT;
+  const int n = blockIdx.z, y0 = blockIdx.y * T, x0 = blockIdx.x * T;
   const size_t hw = (size_t)H * W;
   const float* img = n < B ? x + (size_t)n * 3 * hw : gt + (size_t)(n - B) * 3 * hw;
-  const int ns = (GT + 2 * r1) * GT;
+  const int ns = (T + 2 * r1) * T;
   for (int i = threadIdx.x; i < ns; i += GNT) s[i] = gray_at(img, H, W, y0 - r1 + (i >> 5), x0 + (i & 31));
   __syncthreads();
 #pragma unroll
@@ -90,7 +89,7 @@ __global__ __launch_bounds__(GNT) void stg_gray_hpass_kernel(const float* __rest
     const int p = threadIdx.x + j * GNT, row = p >> 5, col = p & 31;
     float a1 = 0.f, a2 = 0.f;
     STG_TAPS(MAXR1, r1, t) {
-      const float v = s[(row + t) * GT + col];
+      const float v = s[(row + t) * T + col];
       a1 = fmaf(tp.dg[t], v, a1);
       a2 = fmaf(tp.g[t], v, a2);
     }
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(GNT) void stg_gray_hpass_kernel(const float* __rest
 __global__ __launch_bounds__(GNT) void stg_wpass_grad_kernel(const float* __restrict__ A1, const float* __restrict__ A2, Split Ix,
                                                              Split Iy, int H, int W, int r1, StgTaps tp) {
   __shared__ float s1[S1], s2[S1];
-  const int n = blockIdx.z, y0 = blockIdx.y * GT, x0 = blockIdx.x * GT, rs = GT + 2 * r1;
+  const int n = blockIdx.z, y0 = blockIdx.y * T, x0 = blockIdx.x * T, rs = T + 2 * r1;
   const size_t hw = (size_t)H * W;
   stage_rows(A1 + (size_t)n * hw, H, W, y0, x0, r1, s1);
   stage_rows(A2 + (size_t)n * hw, H, W, y0, x0, r1, s2);
@@ -136,7 +135,7 @@ __global__ __launch_bounds__(GNT) void stg_wpass_grad_kernel(const float* __rest
 __global__ __launch_bounds__(GNT) void stg_hpass_products_kernel(Split Ix, Split Iy, float* __restrict__ Q, int H, int W, int r2,
                                                                  StgTaps tp) {
   __shared__ float s1[S2], s2[S2];
-  const int n = blockIdx.z, y0 = blockIdx.y * GT, x0 = blockIdx.x * GT;
+  const int n = blockIdx.z, y0 = blockIdx.y * T, x0 = blockIdx.x * T;
   const size_t hw = (size_t)H * W;
   stage_cols(part(Ix, n, hw), H, W, y0, x0, r2, s1);
   stage_cols(part(Iy, n, hw), H, W, y0, x0, r2, s2);
@@ -146,7 +145,7 @@ __global__ __launch_bounds__(GNT) void stg_hpass_products_kernel(Split Ix, Split
     const int p = threadIdx.x + j * GNT, row = p >> 5, col = p & 31;
     float q0 = 0.f, q1 = 0.f, q2 = 0.f;
     STG_TAPS(MAXR2, r2, t) {
-      const float ix = s1[(row + t) * GT + col], iy = s2[(row + t) * GT + col];
+      const float ix = s1[(row + t) * T + col], iy = s2[(row + t) * T + col];
       q0 = fmaf(tp.k[t], ix * ix, q0);
       q1 = fmaf(tp.k[t], iy * iy, q1);
       q2 = fmaf(tp.k[t], ix * iy, q2);
@@ -154,9 +153,7 @@ __global__ __launch_bounds__(GNT) void stg_hpass_products_kernel(Split Ix, Split
     const int y = y0 + row, xx = x0 + col;
     if (y < H && xx < W) {
       const size_t o = (size_t)n * 3 * hw + (size_t)y * W + xx;
-      Q[o] = q0;
-      Q[o + hw] = q1;
-      Q[o + 2 * hw] = q2;
+      store_planes(Q, o, hw, q0, q1, q2);
     }
   }
 }
@@ -165,7 +162,7 @@ __global__ __launch_bounds__(GNT) void stg_hpass_products_kernel(Split Ix, Split
 __device__ __forceinline__ void wpass_three(const float* __restrict__ src, int H, int W, int y0, int x0, int r2, const StgTaps& tp,
                                             float* s, float (&J)[GPP][3]) {
   const size_t hw = (size_t)H * W;
-  const int rs = GT + 2 * r2;
+  const int rs = T + 2 * r2;
   __syncthreads();  // previous user of the LDS is done
 #pragma unroll
   for (int c = 0; c < 3; ++c) stage_rows(src + c * hw, H, W, y0, x0, r2, s + c * S2);
@@ -187,16 +184,15 @@ __device__ __forceinline__ void wpass_three(const float* __restrict__ src, int H
 }
 
 // ---------------------------------------------------------------------------------------------- d
-// Q: [2B][3][H][W], image b of sr at b, of gt at B + b.  The gradient-of-d block is st_loss_fwd_kernel's, restated (moving it into
-// st_tile.h would have to be proven bit-neutral for the two tile builds) with its eigenvalue half on a discriminant that does not
-// cancel (below).
+// Q: [2B][3][H][W], image b of sr at b, of gt at B + b.  The gradient of d is st_loss_fwd_kernel's (st_tile.h) with its eigenvalue
+// half on a discriminant that does not cancel (below).
 __global__ __launch_bounds__(GNT) void stg_loss_fwd_kernel(const float* __restrict__ Q, float* __restrict__ gS, float* __restrict__ loss,
                                                            float* __restrict__ partials, unsigned* __restrict__ counter, int B, int H,
                                                            int W, int r2, int normalize, StgTaps tp) {
   __shared__ float s[3 * S2];
   __shared__ float red[GNT / 64];
   __shared__ unsigned s_flag;
-  const int b = blockIdx.z, y0 = blockIdx.y * GT, x0 = blockIdx.x * GT;
+  const int b = blockIdx.z, y0 = blockIdx.y * T, x0 = blockIdx.x * T;
   const size_t hw = (size_t)H * W, img_off = (size_t)b * 3 * hw;
   float J1[GPP][3], J2[GPP][3];
   wpass_three(Q + img_off, H, W, y0, x0, r2, tp, s, J1);
@@ -210,47 +206,27 @@ __global__ __launch_bounds__(GNT) void stg_loss_fwd_kernel(const float* __restri
     if (y >= H || x >= W) continue;
     const float a1 = J1[j][0], b1 = J1[j][1], c1 = J1[j][2];
     const StPoint pt = st_pointwise(a1, b1, c1, J2[j][0], J2[j][1], J2[j][2], normalize);
-    const float n1 = pt.n1, ah2 = pt.ah2, bh2 = pt.bh2, ch2 = pt.ch2, A = pt.A, Bm = pt.Bm, C = pt.C, D = pt.D;
-    const float ApB = pt.ApB;
     lsum += pt.d;
 
-    // ---- analytic gradient of d wrt (a1,b1,c1), unit upstream.  The tile block differentiates the forward's own values; here the
+    // ---- analytic gradient of d wrt (a1,b1,c1), unit upstream.  The tile kernel differentiates the forward's own values; here the
     // eigenvalue half is re-evaluated from disc = (A - Bm)^2 + 4 C D, the same discriminant as ApB^2 - 4 (A Bm - C D) without
     // its cancellation.  Wide kernels smooth sr and gt towards each other, both eigenvalues approach 1, ApB^2 and 4 det agree to
     // ~1e-7 and their fp32 difference keeps few or no correct digits: harmless for d (the loss keeps pt.d), but d has a square
     // root's singularity at disc = 0, its derivative goes with 1 / r, and the clamp's gate flips on that noise.
-    const float AmB = A - Bm;
-    const float disc = AmB * AmB + 4.f * C * D;
+    const float AmB = pt.A - pt.Bm;
+    const float disc = AmB * AmB + 4.f * pt.C * pt.D;
     const float r = sqrtf(disc < eps ? eps : disc);
-    const float l1 = 0.5f * (ApB - r), l2 = 0.5f * (ApB + r);
+    const float l1 = 0.5f * (pt.ApB - r), l2 = 0.5f * (pt.ApB + r);
     const float L1 = l1 < 1.f ? 1.f : l1, L2 = l2 < 1.f ? 1.f : l2;     // NaN stays NaN, as in st_pointwise
     const float g1 = logf(L1), g2 = logf(L2);
     const float d = sqrtf(g1 * g1 + g2 * g2 + eps);
-    const float dq = 0.5f / d;
-    const float dl1 = (l1 >= 1.f) ? dq * 2.f * g1 / L1 : 0.f;
-    const float dl2 = (l2 >= 1.f) ? dq * 2.f * g2 / L2 : 0.f;
-    const float dApB = 0.5f * (dl1 + dl2);
-    const float dr = 0.5f * (dl2 - dl1);
-    const float ddisc = (disc >= eps) ? dr / (2.f * r) : 0.f;
-    const float dA = dApB + ddisc * 2.f * AmB;      // = dApB + ddisc * (2 ApB - 4 Bm), the tile block's form
-    const float dB = dApB - ddisc * 2.f * AmB;
-    const float dC = 4.f * ddisc * D;
-    const float dD = 4.f * ddisc * C;
-    const float dah = dB * bh2 + dD * ch2;
-    const float dbh = dA * ah2 + dC * ch2;
-    const float dch = -(dA + dB) * ch2 - dC * bh2 - dD * ah2;
-    float ga = dah * n1, gb = dbh * n1, gc = dch * n1;
-    if (normalize) {
-      const float dn = a1 * dah + b1 * dbh + c1 * dch;
-      const float ddet = dn * (-0.5f * n1 * n1 * n1);
-      ga += ddet * b1;
-      gb += ddet * a1;
-      gc -= 2.f * ddet * c1;
-    }
-    const size_t o = img_off + (size_t)y * W + x;
-    gS[o] = ga;
-    gS[o + hw] = gb;
-    gS[o + 2 * hw] = gc;
+    const StEigGrad e = st_grad_eigen(d, l1, l2, L1, L2, g1, g2, disc, r);
+    const float dApB = 0.5f * e.dl12;
+    const float dA = dApB + e.ddisc * 2.f * AmB;        // = dApB + ddisc * (2 ApB - 4 Bm), the tile kernel's form
+    const float dB = dApB - e.ddisc * 2.f * AmB;
+    const float dC = 4.f * e.ddisc * pt.D;
+    const float dD = 4.f * e.ddisc * pt.C;
+    st_grad_store(gS, img_off + (size_t)y * W + x, hw, dA, dB, dC, dD, pt, a1, b1, c1, normalize);
   }
   const float bsum = block_sum<GNT>(lsum, red);
   const unsigned nblk = gridDim.x * gridDim.y * gridDim.z;
@@ -267,7 +243,7 @@ __global__ __launch_bounds__(GNT) void stg_loss_fwd_kernel(const float* __restri
 __global__ __launch_bounds__(GNT) void stg_wpass_tensor_kernel(const float* __restrict__ Q, float* __restrict__ S, int H, int W, int r2,
                                                                StgTaps tp) {
   __shared__ float s[3 * S2];
-  const int n = blockIdx.z, y0 = blockIdx.y * GT, x0 = blockIdx.x * GT;
+  const int n = blockIdx.z, y0 = blockIdx.y * T, x0 = blockIdx.x * T;
   const size_t hw = (size_t)H * W, img_off = (size_t)n * 3 * hw;
   float J[GPP][3];
   wpass_three(Q + img_off, H, W, y0, x0, r2, tp, s, J);
@@ -276,66 +252,31 @@ __global__ __launch_bounds__(GNT) void stg_wpass_tensor_kernel(const float* __re
     const int p = threadIdx.x + j * GNT, y = y0 + (p >> 5), x = x0 + (p & 31);
     if (y >= H || x >= W) continue;
     const size_t o = img_off + (size_t)y * W + x;
-    S[o] = J[j][0];
-    S[o + hw] = J[j][1];
-    S[o + 2 * hw] = J[j][2];
+    store_planes(S, o, hw, J[j][0], J[j][1], J[j][2]);
   }
 }
 
-struct StgMapsOut {
-  float* Sx;
-  float* Sgt;
-  float* Fx;
-  float* Fgt;
-  float* d;
-  float* tile_sums;
-};
-
-__device__ __forceinline__ void stg_store_planes(float* __restrict__ out, size_t o, size_t hw, float v0, float v1, float v2) {
-  out[o] = v0;
-  out[o + hw] = v1;
-  out[o + 2 * hw] = v2;
-}
-// (t, c2, s2) of one structure tensor: st_maps.hip's store_features
-__device__ __forceinline__ void stg_store_features(float* __restrict__ out, size_t o, size_t hw, float jxx, float jyy, float jxy) {
-  const float t = jxx + jyy;
-  const float den = t + 1e-12f;
-  stg_store_planes(out, o, hw, t, (jxx - jyy) / den, 2.f * jxy / den);
-}
-
 // S: [B (+ B)][3][H][W] (gt's images behind x's; absent when has_gt is 0) -> the outputs of sst_st_maps, same layouts
-__global__ __launch_bounds__(GNT) void stg_maps_point_kernel(const float* __restrict__ S, StgMapsOut out, int B, int H, int W,
+__global__ __launch_bounds__(GNT) void stg_maps_point_kernel(const float* __restrict__ S, StMapsOut out, int B, int H, int W,
                                                              int has_gt, int normalize) {
   __shared__ float red[GNT / 64];
-  const int b = blockIdx.z, y0 = blockIdx.y * GT, x0 = blockIdx.x * GT;
-  const size_t hw = (size_t)H * W, img_off = (size_t)b * 3 * hw;
-  const bool want_d = out.d || out.tile_sums;
+  const int b = blockIdx.z, y0 = blockIdx.y * T, x0 = blockIdx.x * T;
+  const size_t hw = (size_t)H * W;
   float lsum = 0.f;
 #pragma unroll
   for (int j = 0; j < GPP; ++j) {
     const int p = threadIdx.x + j * GNT, y = y0 + (p >> 5), xx = x0 + (p & 31);
     if (y >= H || xx >= W) continue;                    // outside the image: neither stored nor summed
-    const size_t px = (size_t)y * W + xx, o = img_off + px;
-    const float a1 = S[o], b1 = S[o + hw], c1 = S[o + 2 * hw];
-    float a2 = 0.f, b2 = 0.f, c2 = 0.f;
+    const size_t px = (size_t)y * W + xx, o = (size_t)b * 3 * hw + px;
+    const float J1[3] = {S[o], S[o + hw], S[o + 2 * hw]};
+    float J2[3] = {0.f, 0.f, 0.f};
     if (has_gt) {
       const size_t o2 = (size_t)(B + b) * 3 * hw + px;
-      a2 = S[o2], b2 = S[o2 + hw], c2 = S[o2 + 2 * hw];
+      J2[0] = S[o2], J2[1] = S[o2 + hw], J2[2] = S[o2 + 2 * hw];
     }
-    if (out.Sx) stg_store_planes(out.Sx, o, hw, a1, b1, c1);
-    if (out.Sgt) stg_store_planes(out.Sgt, o, hw, a2, b2, c2);
-    if (out.Fx) stg_store_features(out.Fx, o, hw, a1, b1, c1);
-    if (out.Fgt) stg_store_features(out.Fgt, o, hw, a2, b2, c2);
-    if (want_d) {
-      const float d = st_pointwise(a1, b1, c1, a2, b2, c2, normalize).d;
-      if (out.d) out.d[(size_t)b * hw + px] = d;
-      lsum += d;
-    }
+    maps_pixel(out, b, px, hw, J1, J2, normalize, lsum);
   }
-  if (out.tile_sums) {                                  // uniform: every thread of every workgroup takes the same side
-    const float bsum = block_sum<GNT>(lsum, red);
-    if (threadIdx.x == 0) out.tile_sums[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = bsum;
-  }
+  maps_tile_sum<GNT>(out, b, lsum, red);
 }
 
 // ---------------------------------------------------------------------------------------------- e
@@ -343,7 +284,7 @@ __global__ __launch_bounds__(GNT) void stg_maps_point_kernel(const float* __rest
 __global__ __launch_bounds__(GNT) void stg_hpass_three_kernel(const float* __restrict__ gS, float* __restrict__ U, int H, int W, int r2,
                                                               StgTaps tp) {
   __shared__ float s[3 * S2];
-  const int b = blockIdx.z, y0 = blockIdx.y * GT, x0 = blockIdx.x * GT;
+  const int b = blockIdx.z, y0 = blockIdx.y * T, x0 = blockIdx.x * T;
   const size_t hw = (size_t)H * W, img_off = (size_t)b * 3 * hw;
 #pragma unroll
   for (int c = 0; c < 3; ++c) stage_cols(gS + img_off + c * hw, H, W, y0, x0, r2, s + c * S2);
@@ -354,16 +295,14 @@ __global__ __launch_bounds__(GNT) void stg_hpass_three_kernel(const float* __res
     float u0 = 0.f, u1 = 0.f, u2 = 0.f;
     STG_TAPS(MAXR2, r2, t) {
       const float kk = tp.k[t];
-      u0 = fmaf(kk, s[(row + t) * GT + col], u0);
-      u1 = fmaf(kk, s[S2 + (row + t) * GT + col], u1);
-      u2 = fmaf(kk, s[2 * S2 + (row + t) * GT + col], u2);
+      u0 = fmaf(kk, s[(row + t) * T + col], u0);
+      u1 = fmaf(kk, s[S2 + (row + t) * T + col], u1);
+      u2 = fmaf(kk, s[2 * S2 + (row + t) * T + col], u2);
     }
     const int y = y0 + row, xx = x0 + col;
     if (y < H && xx < W) {
       const size_t o = img_off + (size_t)y * W + xx;
-      U[o] = u0;
-      U[o + hw] = u1;
-      U[o + 2 * hw] = u2;
+      store_planes(U, o, hw, u0, u1, u2);
     }
   }
 }
@@ -374,7 +313,7 @@ __global__ __launch_bounds__(GNT) void stg_wpass_dgrad_kernel(const float* __res
                                                               float* __restrict__ dIx, float* __restrict__ dIy, int B, int H, int W,
                                                               int r2, StgTaps tp) {
   __shared__ float s[3 * S2];
-  const int b = blockIdx.z, y0 = blockIdx.y * GT, x0 = blockIdx.x * GT;
+  const int b = blockIdx.z, y0 = blockIdx.y * T, x0 = blockIdx.x * T;
   const size_t hw = (size_t)H * W;
   float V[GPP][3];
   wpass_three(U + (size_t)b * 3 * hw, H, W, y0, x0, r2, tp, s, V);
@@ -395,7 +334,7 @@ __global__ __launch_bounds__(GNT) void stg_wadj_kernel(const float* __restrict__
                                                        float* __restrict__ dA1, float* __restrict__ dA2, int H, int W, int r1,
                                                        StgTaps tp) {
   __shared__ float s1[S1], s2[S1];
-  const int b = blockIdx.z, y0 = blockIdx.y * GT, x0 = blockIdx.x * GT, rs = GT + 2 * r1;
+  const int b = blockIdx.z, y0 = blockIdx.y * T, x0 = blockIdx.x * T, rs = T + 2 * r1;
   const size_t hw = (size_t)H * W;
   stage_rows(dIx + (size_t)b * hw, H, W, y0, x0, r1, s1);
   stage_rows(dIy + (size_t)b * hw, H, W, y0, x0, r1, s2);
@@ -424,7 +363,7 @@ __global__ __launch_bounds__(GNT) void stg_hadj_out_kernel(const float* __restri
                                                            float* __restrict__ dsr, const float* __restrict__ scale_dev,
                                                            float scale_host, int accumulate, int H, int W, int r1, StgTaps tp) {
   __shared__ float s1[S1], s2[S1];
-  const int b = blockIdx.z, y0 = blockIdx.y * GT, x0 = blockIdx.x * GT;
+  const int b = blockIdx.z, y0 = blockIdx.y * T, x0 = blockIdx.x * T;
   const size_t hw = (size_t)H * W;
   stage_cols(dA1 + (size_t)b * hw, H, W, y0, x0, r1, s1);
   stage_cols(dA2 + (size_t)b * hw, H, W, y0, x0, r1, s2);
@@ -436,47 +375,22 @@ __global__ __launch_bounds__(GNT) void stg_hadj_out_kernel(const float* __restri
     const int p = threadIdx.x + j * GNT, row = p >> 5, col = p & 31;
     float dg_ = 0.f;
     STG_TAPS(MAXR1, r1, t) {
-      dg_ = fmaf(-tp.dg[t], s1[(row + t) * GT + col], dg_);
-      dg_ = fmaf(tp.g[t], s2[(row + t) * GT + col], dg_);
+      dg_ = fmaf(-tp.dg[t], s1[(row + t) * T + col], dg_);
+      dg_ = fmaf(tp.g[t], s2[(row + t) * T + col], dg_);
     }
     const int y = y0 + row, xx = x0 + col;
     if (y < H && xx < W) {
       const size_t o = (size_t)b * 3 * hw + (size_t)y * W + xx;
-      const float v = dg_ * scale;
-      if (accumulate) {
-        dsr[o] += 0.2989f * v;
-        dsr[o + hw] += 0.587f * v;
-        dsr[o + 2 * hw] += 0.114f * v;
-      } else {
-        dsr[o] = 0.2989f * v;
-        dsr[o + hw] = 0.587f * v;
-        dsr[o + 2 * hw] = 0.114f * v;
-      }
+      store_gray_grad(dsr, o, hw, dg_ * scale, accumulate, nullptr);
     }
   }
 }
 
 // ---------------------------------------------------------------------------------------------- host
-// gaussian_taps<R> of st_tile.h with the radius as a value: utils.py:194-208 (fp32 exp, fp32 normalisation)
-void gaussian_taps_rt(float sigma, int R, float* g, float* dg) {
-  const float sigma2 = (float)((double)sigma * (double)sigma + 1e-12);
-  const float c = (float)(-0.5 / ((double)sigma * (double)sigma + 1e-12));
-  float s = 0.f;
-  for (int i = 0; i <= 2 * R; ++i) {
-    const float x = (float)(i - R);
-    g[i] = expf(c * (x * x));
-    s += g[i];
-  }
-  for (int i = 0; i <= 2 * R; ++i) {
-    g[i] /= s;
-    if (dg) dg[i] = g[i] * -(float)(i - R) / sigma2;
-  }
-}
-
 StgTaps make_taps_rt(float sigma, float rho, int r1, int r2) {
   StgTaps tp = {};
-  gaussian_taps_rt(sigma, r1, tp.g, tp.dg);
-  gaussian_taps_rt(rho, r2, tp.k, nullptr);
+  gaussian_taps(sigma, r1, tp.g, tp.dg);
+  gaussian_taps(rho, r2, tp.k, nullptr);
   return tp;
 }
 
@@ -484,16 +398,13 @@ StgTaps make_taps_rt(float sigma, float rho, int r1, int r2) {
 int st_route(const char* who, float sigma, float rho, int* r1, int* r2) {
   if (!(fabsf(sigma) < 1e6f && fabsf(rho) < 1e6f)) return sst_set_error(SST_ERR_ARG, "%s: sigma / rho must be finite", who);
   *r1 = radius_of(sigma), *r2 = radius_of(rho);
-  if ((*r1 == 2 && *r2 == 8) || (*r1 == 4 && *r2 == 10)) return 0;
+  if (with_tile_build(*r1, *r2, [](auto, auto) {})) return 0;
   if (*r1 <= MAXR1 && *r2 <= MAXR2) return 1;
   return sst_set_error(SST_ERR_UNSUPPORTED, "%s: (sigma,rho)=(%g,%g) -> radii (%d,%d) not built", who, sigma, rho, *r1, *r2);
 }
 
-bool shape_ok(int B, int H, int W) {
-  return B > 0 && H > 0 && W > 0 && B <= 32767 && (H + GT - 1) / GT <= 65535 && (int64_t)B * H * W <= (int64_t)1 << 40;
-}
-
-dim3 tiles_grid(int H, int W, int z) { return dim3((W + GT - 1) / GT, (H + GT - 1) / GT, z); }
+// B up to 32767: the grid's z carries 2 B images; the 14 B H W floats of the scratch are kept to 2^40 elements
+bool general_shape_ok(int B, int H, int W) { return shape_ok(B, H, W, 32767) && (int64_t)B * H * W <= (int64_t)1 << 40; }
 
 // passes a, b, c for nimg images (x's B, then gt's when gt != null): Q at `Q`
 void launch_abc(const float* x, const float* gt, int B, int nimg, float* A1, float* A2, Split Ix, Split Iy, float* Q, int H, int W, int r1,
@@ -516,18 +427,18 @@ SST_API int sst_st_route(float sigma, float rho, int* r1, int* r2) {
 // Floats of the general path's buffers with N = B*H*W: scratch 14 N (forward 12 N, backward 7 N, maps 14 N: one buffer serves all),
 // saved 2 N (Ix, Iy of sr: written by the forward, read by the backward), partials B * ceil(H/32) * ceil(W/32).
 SST_API int sst_st_general_workspace(int B, int H, int W, int64_t* scratch_floats, int64_t* saved_floats, int64_t* partial_floats) {
-  SST_REQUIRE(shape_ok(B, H, W) && scratch_floats && saved_floats && partial_floats, "sst_st_general_workspace: bad shape");
+  SST_REQUIRE(general_shape_ok(B, H, W) && scratch_floats && saved_floats && partial_floats, "sst_st_general_workspace: bad shape");
   const int64_t n = (int64_t)B * H * W;
   *scratch_floats = 14 * n;
   *saved_floats = 2 * n;
-  *partial_floats = (int64_t)B * ((H + GT - 1) / GT) * ((W + GT - 1) / GT);
+  *partial_floats = tiles_of(B, H, W);
   return SST_OK;
 }
 
 SST_API int sst_st_general_fwd(const float* sr, const float* gt, float* loss, float* gS, float* saved, float* scratch, float* partials,
                                unsigned* counter, int B, int H, int W, float sigma, float rho, int normalize, void* stream) {
   SST_REQUIRE(sr && gt && loss && gS && saved && scratch && partials && counter, "sst_st_general_fwd: null pointer");
-  SST_REQUIRE(shape_ok(B, H, W), "sst_st_general_fwd: bad shape B=%d H=%d W=%d", B, H, W);
+  SST_REQUIRE(general_shape_ok(B, H, W), "sst_st_general_fwd: bad shape B=%d H=%d W=%d", B, H, W);
   int r1, r2;
   const int route = st_route("sst_st_general_fwd", sigma, rho, &r1, &r2);
   if (route < 0) return route;
@@ -545,7 +456,7 @@ SST_API int sst_st_general_fwd(const float* sr, const float* gt, float* loss, fl
 SST_API int sst_st_general_bwd(const float* saved, const float* gS, float* dsr, float* scratch, const float* scale_dev, float scale_host,
                                int accumulate, int B, int H, int W, float sigma, float rho, void* stream) {
   SST_REQUIRE(saved && gS && dsr && scratch, "sst_st_general_bwd: null pointer");
-  SST_REQUIRE(shape_ok(B, H, W), "sst_st_general_bwd: bad shape B=%d H=%d W=%d", B, H, W);
+  SST_REQUIRE(general_shape_ok(B, H, W), "sst_st_general_bwd: bad shape B=%d H=%d W=%d", B, H, W);
   int r1, r2;
   const int route = st_route("sst_st_general_bwd", sigma, rho, &r1, &r2);
   if (route < 0) return route;
@@ -567,12 +478,8 @@ SST_API int sst_st_general_bwd(const float* saved, const float* gS, float* dsr, 
 SST_API int sst_st_general_maps(const float* x, const float* gt, float* Sx, float* Sgt, float* Fx, float* Fgt, float* d, float* tile_sums,
                                 float* scratch, int B, int H, int W, float sigma, float rho, int normalize, void* stream) {
   SST_REQUIRE(x && scratch, "sst_st_general_maps: null pointer (x / scratch)");
-  SST_REQUIRE(shape_ok(B, H, W), "sst_st_general_maps: bad shape B=%d H=%d W=%d", B, H, W);
-  SST_REQUIRE(Sx || Sgt || Fx || Fgt || d || tile_sums, "sst_st_general_maps: no output requested");
-  SST_REQUIRE(gt || !Sgt, "sst_st_general_maps: Sgt needs gt");
-  SST_REQUIRE(gt || !Fgt, "sst_st_general_maps: Fgt needs gt");
-  SST_REQUIRE(gt || !d, "sst_st_general_maps: d needs gt (the distance is between two images)");
-  SST_REQUIRE(gt || !tile_sums, "sst_st_general_maps: tile_sums cannot be computed without gt (they are sums of d)");
+  const StMapsOut out{Sx, Sgt, Fx, Fgt, d, tile_sums};
+  if (const int rc = maps_args_ok("sst_st_general_maps", general_shape_ok(B, H, W), B, H, W, gt, out)) return rc;
   int r1, r2;
   const int route = st_route("sst_st_general_maps", sigma, rho, &r1, &r2);
   if (route < 0) return route;
@@ -584,7 +491,7 @@ SST_API int sst_st_general_maps(const float* x, const float* gt, float* Sx, floa
   float* S = scratch;                                                                                             // over A / I: dead by then
   launch_abc(x, gt, B, nimg, A1, A2, Split{Ix, Ix + n, B}, Split{Iy, Iy + n, B}, Q, H, W, r1, r2, tp, st);
   stg_wpass_tensor_kernel<<<tiles_grid(H, W, nimg), GNT, 0, st>>>(Q, S, H, W, r2, tp);
-  stg_maps_point_kernel<<<tiles_grid(H, W, B), GNT, 0, st>>>(S, StgMapsOut{Sx, Sgt, Fx, Fgt, d, tile_sums}, B, H, W, gt ? 1 : 0, normalize);
+  stg_maps_point_kernel<<<tiles_grid(H, W, B), GNT, 0, st>>>(S, out, B, H, W, gt ? 1 : 0, normalize);
   SST_LAUNCH_CHECK("stg_maps_point_kernel");
   return SST_OK;
 }

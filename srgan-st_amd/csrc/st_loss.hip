@@ -36,7 +36,6 @@ __global__ __launch_bounds__(NT) void st_loss_fwd_kernel(const float* __restrict
   tile_structure_tensor<R1, R2>(sr + img_off, H, W, y0, x0, tp, lds, J1);
   tile_structure_tensor<R1, R2>(gt + img_off, H, W, y0, x0, tp, lds, J2);
 
-  const float eps = 1e-12f;
   float lsum = 0.f, psum = 0.f;
 #pragma unroll
   for (int j = 0; j < PPT; ++j) {
@@ -53,39 +52,18 @@ __global__ __launch_bounds__(NT) void st_loss_fwd_kernel(const float* __restrict
     const float a1 = J1[j][0], b1 = J1[j][1], c1 = J1[j][2];
     const float a2 = J2[j][0], b2 = J2[j][1], c2 = J2[j][2];
     const StPoint pt = st_pointwise(a1, b1, c1, a2, b2, c2, normalize);
-    const float n1 = pt.n1, ah2 = pt.ah2, bh2 = pt.bh2, ch2 = pt.ch2, A = pt.A, Bm = pt.Bm, C = pt.C, D = pt.D;
-    const float ApB = pt.ApB, disc = pt.disc, r = pt.r, l1 = pt.l1, l2 = pt.l2, L1 = pt.L1, L2 = pt.L2, g1 = pt.g1, g2 = pt.g2;
-    const float d = pt.d;
-    lsum += d;
+    lsum += pt.d;
 
-    // ---- analytic gradient of d wrt (a1,b1,c1), unit upstream
-    const float dq = 0.5f / d;
-    const float dl1 = (l1 >= 1.f) ? dq * 2.f * g1 / L1 : 0.f;
-    const float dl2 = (l2 >= 1.f) ? dq * 2.f * g2 / L2 : 0.f;
-    float dApB = 0.5f * (dl1 + dl2);
-    const float dr = 0.5f * (dl2 - dl1);
-    const float ddisc = (disc >= eps) ? dr / (2.f * r) : 0.f;
-    dApB += ddisc * 2.f * ApB;
-    const float dt = -4.f * ddisc;  // d wrt (A*Bm - C*D)
-    const float dA = dApB + dt * Bm;
-    const float dB = dApB + dt * A;
-    const float dC = -dt * D;
-    const float dD = -dt * C;
-    const float dah = dB * bh2 + dD * ch2;
-    const float dbh = dA * ah2 + dC * ch2;
-    const float dch = -(dA + dB) * ch2 - dC * bh2 - dD * ah2;
-    float ga = dah * n1, gb = dbh * n1, gc = dch * n1;
-    if (normalize) {
-      const float dn = a1 * dah + b1 * dbh + c1 * dch;
-      const float ddet = dn * (-0.5f * n1 * n1 * n1);
-      ga += ddet * b1;
-      gb += ddet * a1;
-      gc -= 2.f * ddet * c1;
-    }
-    const size_t o = img_off + (size_t)y * W + x, hw = (size_t)H * W;
-    gS[o] = ga;
-    gS[o + hw] = gb;
-    gS[o + 2 * hw] = gc;
+    // ---- analytic gradient of d wrt (a1,b1,c1), unit upstream: the forward's own values differentiated
+    const StEigGrad e = st_grad_eigen(pt.d, pt.l1, pt.l2, pt.L1, pt.L2, pt.g1, pt.g2, pt.disc, pt.r);
+    // (the fma is spelled out: halving is exact, and the product beside it rounds on its own whatever the compiler would contract)
+    const float dApB = fmaf(0.5f, e.dl12, e.ddisc * 2.f * pt.ApB);
+    const float dt = -4.f * e.ddisc;  // d wrt (A*Bm - C*D)
+    const float dA = dApB + dt * pt.Bm;
+    const float dB = dApB + dt * pt.A;
+    const float dC = -dt * pt.D;
+    const float dD = -dt * pt.C;
+    st_grad_store(gS, img_off + (size_t)y * W + x, (size_t)H * W, dA, dB, dC, dD, pt, a1, b1, c1, normalize);
   }
   const float bsum = block_sum<NT>(lsum, red);
   __shared__ unsigned s_flag;
@@ -232,7 +210,6 @@ __global__ __launch_bounds__(NT) void st_loss_bwd_kernel(const float* __restrict
     }
     if (y < H && x < W) {
       const size_t o = img_off + (size_t)y * W + x;
-      const float v = dg_ * scale;
       float pv[3] = {0.f, 0.f, 0.f};
       if (pix_gt) {
         float psc = pix_scale;
@@ -243,15 +220,7 @@ __global__ __launch_bounds__(NT) void st_loss_bwd_kernel(const float* __restrict
           pv[c] = pix_mode == 0 ? 2.f * d * psc : (d > 0.f ? psc : (d < 0.f ? -psc : 0.f));
         }
       }
-      if (accumulate) {
-        dsr[o] += 0.2989f * v + pv[0];
-        dsr[o + hw] += 0.587f * v + pv[1];
-        dsr[o + 2 * hw] += 0.114f * v + pv[2];
-      } else {
-        dsr[o] = 0.2989f * v + pv[0];
-        dsr[o + hw] = 0.587f * v + pv[1];
-        dsr[o + 2 * hw] = 0.114f * v + pv[2];
-      }
+      store_gray_grad(dsr, o, hw, dg_ * scale, accumulate, pv);
     }
   }
 }
@@ -261,26 +230,22 @@ __global__ __launch_bounds__(NT) void st_loss_bwd_kernel(const float* __restrict
 // ------------------------------------------------------------------------------------------ C ABI
 SST_API int sst_st_loss_workspace(int B, int H, int W, int64_t* partial_floats) {
   SST_REQUIRE(B > 0 && H > 0 && W > 0 && partial_floats, "sst_st_loss_workspace: bad shape");
-  *partial_floats = (int64_t)B * ((H + T - 1) / T) * ((W + T - 1) / T);
+  *partial_floats = tiles_of(B, H, W);
   return SST_OK;
 }
 
 static int st_loss_fwd_impl(const float* sr, const float* gt, float* loss, float* gS, float* partials, unsigned* counter, int B, int H,
                             int W, float sigma, float rho, int normalize, StPix pix, void* stream) {
   SST_REQUIRE(sr && gt && loss && gS && partials && counter, "sst_st_loss_fwd: null pointer");
+  // (the loss entries have never bounded the tile rows as shape_ok does: a taller image than 65535 tiles fails at the launch)
   SST_REQUIRE(B > 0 && H > 0 && W > 0 && B <= 65535, "sst_st_loss_fwd: bad shape B=%d H=%d W=%d", B, H, W);
   const int r1 = radius_of(sigma), r2 = radius_of(rho);
-  dim3 grid((W + T - 1) / T, (H + T - 1) / T, B);
-  if (r1 == 2 && r2 == 8) {
-    st_loss_fwd_kernel<2, 8><<<grid, NT, 0, sst_stream(stream)>>>(sr, gt, gS, loss, partials, counter, B, H, W,
-                                                                    normalize, make_taps<2, 8>(sigma, rho), pix);
-  } else if (r1 == 4 && r2 == 10) {
-    st_loss_fwd_kernel<4, 10><<<grid, NT, 0, sst_stream(stream)>>>(sr, gt, gS, loss, partials, counter, B, H, W,
-                                                                     normalize, make_taps<4, 10>(sigma, rho), pix);
-  } else {
-    return sst_set_error(SST_ERR_UNSUPPORTED, "sst_st_loss_fwd: (sigma,rho)=(%g,%g) -> radii (%d,%d) not built", sigma,
-                         rho, r1, r2);
-  }
+  const bool built = with_tile_build(r1, r2, [&](auto R1, auto R2) {
+    st_loss_fwd_kernel<R1(), R2()><<<tiles_grid(H, W, B), NT, 0, sst_stream(stream)>>>(sr, gt, gS, loss, partials, counter, B, H, W, normalize,
+                                                                                       make_taps<R1(), R2()>(sigma, rho), pix);
+  });
+  if (!built)
+    return sst_set_error(SST_ERR_UNSUPPORTED, "sst_st_loss_fwd: (sigma,rho)=(%g,%g) -> radii (%d,%d) not built", sigma, rho, r1, r2);
   SST_LAUNCH_CHECK("st_loss_fwd_kernel");
   return SST_OK;
 }
@@ -305,18 +270,12 @@ static int st_loss_bwd_impl(const float* sr, const float* gS, float* dsr, const 
                             int H, int W, float sigma, float rho, const float* pix_gt, float pix_scale, int pix_mode, void* stream) {
   SST_REQUIRE(sr && gS && dsr, "sst_st_loss_bwd: null pointer");
   SST_REQUIRE(B > 0 && H > 0 && W > 0 && B <= 65535, "sst_st_loss_bwd: bad shape");
-  const int r1 = radius_of(sigma), r2 = radius_of(rho);
-  dim3 grid((W + T - 1) / T, (H + T - 1) / T, B);
   const float s = scale_host / ((float)B * (float)H * (float)W);
-  if (r1 == 2 && r2 == 8) {
-    st_loss_bwd_kernel<2, 8><<<grid, NT, 0, sst_stream(stream)>>>(sr, gS, dsr, scale_dev, s, accumulate, B, H, W,
-                                                                    make_taps<2, 8>(sigma, rho), pix_gt, pix_scale, pix_mode);
-  } else if (r1 == 4 && r2 == 10) {
-    st_loss_bwd_kernel<4, 10><<<grid, NT, 0, sst_stream(stream)>>>(sr, gS, dsr, scale_dev, s, accumulate, B, H, W,
-                                                                     make_taps<4, 10>(sigma, rho), pix_gt, pix_scale, pix_mode);
-  } else {
-    return sst_set_error(SST_ERR_UNSUPPORTED, "sst_st_loss_bwd: (sigma,rho)=(%g,%g) not built", sigma, rho);
-  }
+  const bool built = with_tile_build(radius_of(sigma), radius_of(rho), [&](auto R1, auto R2) {
+    st_loss_bwd_kernel<R1(), R2()><<<tiles_grid(H, W, B), NT, 0, sst_stream(stream)>>>(sr, gS, dsr, scale_dev, s, accumulate, B, H, W,
+                                                                                       make_taps<R1(), R2()>(sigma, rho), pix_gt, pix_scale, pix_mode);
+  });
+  if (!built) return sst_set_error(SST_ERR_UNSUPPORTED, "sst_st_loss_bwd: (sigma,rho)=(%g,%g) not built", sigma, rho);
   SST_LAUNCH_CHECK("st_loss_bwd_kernel");
   return SST_OK;
 }

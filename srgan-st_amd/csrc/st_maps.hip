@@ -24,28 +24,6 @@
 
 namespace {
 
-struct StMapsOut {
-  float* Sx;
-  float* Sgt;
-  float* Fx;
-  float* Fgt;
-  float* d;
-  float* tile_sums;
-};
-
-__device__ __forceinline__ void store_planes(float* __restrict__ out, size_t o, size_t hw, float v0, float v1, float v2) {
-  out[o] = v0;
-  out[o + hw] = v1;
-  out[o + 2 * hw] = v2;
-}
-
-// (t, c2, s2) of one structure tensor
-__device__ __forceinline__ void store_features(float* __restrict__ out, size_t o, size_t hw, float jxx, float jyy, float jxy) {
-  const float t = jxx + jyy;
-  const float den = t + 1e-12f;
-  store_planes(out, o, hw, t, (jxx - jyy) / den, 2.f * jxy / den);
-}
-
 template <int R1, int R2>
 __global__ __launch_bounds__(NT) void st_maps_kernel(const float* __restrict__ x, const float* __restrict__ gt, StMapsOut out, int H,
                                                      int W, int normalize, StTaps<R1, R2> tp) {
@@ -53,8 +31,7 @@ __global__ __launch_bounds__(NT) void st_maps_kernel(const float* __restrict__ x
   __shared__ float red[NT / 64];
   const int b = blockIdx.z, y0 = blockIdx.y * T, x0 = blockIdx.x * T;
   const size_t hw = (size_t)H * W, img_off = (size_t)b * 3 * hw;
-  const bool want_d = out.d || out.tile_sums;
-  const bool need1 = out.Sx || out.Fx || want_d, need2 = out.Sgt || out.Fgt || want_d;
+  const bool need1 = out.Sx || out.Fx || out.want_d(), need2 = out.Sgt || out.Fgt || out.want_d();
   float J1[PPT][3] = {}, J2[PPT][3] = {};
   if (need1) tile_structure_tensor<R1, R2>(x + img_off, H, W, y0, x0, tp, lds, J1);
   if (need2) tile_structure_tensor<R1, R2>(gt + img_off, H, W, y0, x0, tp, lds, J2);
@@ -64,21 +41,9 @@ __global__ __launch_bounds__(NT) void st_maps_kernel(const float* __restrict__ x
   for (int j = 0; j < PPT; ++j) {
     const int p = threadIdx.x + j * NT, y = y0 + (p >> 5), xx = x0 + (p & 31);
     if (y >= H || xx >= W) continue;                    // outside the image: neither stored nor summed
-    const size_t px = (size_t)y * W + xx, o = img_off + px;
-    if (out.Sx) store_planes(out.Sx, o, hw, J1[j][0], J1[j][1], J1[j][2]);
-    if (out.Sgt) store_planes(out.Sgt, o, hw, J2[j][0], J2[j][1], J2[j][2]);
-    if (out.Fx) store_features(out.Fx, o, hw, J1[j][0], J1[j][1], J1[j][2]);
-    if (out.Fgt) store_features(out.Fgt, o, hw, J2[j][0], J2[j][1], J2[j][2]);
-    if (want_d) {
-      const float d = st_pointwise(J1[j][0], J1[j][1], J1[j][2], J2[j][0], J2[j][1], J2[j][2], normalize).d;
-      if (out.d) out.d[(size_t)b * hw + px] = d;
-      lsum += d;
-    }
+    maps_pixel(out, b, (size_t)y * W + xx, hw, J1[j], J2[j], normalize, lsum);
   }
-  if (out.tile_sums) {                                  // uniform: every thread of every workgroup takes the same side
-    const float bsum = block_sum<NT>(lsum, red);
-    if (threadIdx.x == 0) out.tile_sums[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = bsum;
-  }
+  maps_tile_sum<NT>(out, b, lsum, red);
 }
 
 }  // namespace
@@ -86,29 +51,20 @@ __global__ __launch_bounds__(NT) void st_maps_kernel(const float* __restrict__ x
 // ------------------------------------------------------------------------------------------ C ABI
 SST_API int sst_st_maps_workspace(int B, int H, int W, int64_t* tile_floats) {
   SST_REQUIRE(B > 0 && H > 0 && W > 0 && tile_floats, "sst_st_maps_workspace: bad shape");
-  *tile_floats = (int64_t)B * ((H + T - 1) / T) * ((W + T - 1) / T);
+  *tile_floats = tiles_of(B, H, W);
   return SST_OK;
 }
 
 SST_API int sst_st_maps(const float* x, const float* gt, float* Sx, float* Sgt, float* Fx, float* Fgt, float* d, float* tile_sums,
                         int B, int H, int W, float sigma, float rho, int normalize, void* stream) {
   SST_REQUIRE(x, "sst_st_maps: null pointer (x)");
-  SST_REQUIRE(B > 0 && H > 0 && W > 0 && B <= 65535 && (H + T - 1) / T <= 65535, "sst_st_maps: bad shape B=%d H=%d W=%d", B, H, W);
-  SST_REQUIRE(Sx || Sgt || Fx || Fgt || d || tile_sums, "sst_st_maps: no output requested");
-  SST_REQUIRE(gt || !Sgt, "sst_st_maps: Sgt needs gt");
-  SST_REQUIRE(gt || !Fgt, "sst_st_maps: Fgt needs gt");
-  SST_REQUIRE(gt || !d, "sst_st_maps: d needs gt (the distance is between two images)");
-  SST_REQUIRE(gt || !tile_sums, "sst_st_maps: tile_sums cannot be computed without gt (they are sums of d)");
-  const int r1 = radius_of(sigma), r2 = radius_of(rho);
-  const dim3 grid((W + T - 1) / T, (H + T - 1) / T, B);
   const StMapsOut out{Sx, Sgt, Fx, Fgt, d, tile_sums};
-  if (r1 == 2 && r2 == 8) {
-    st_maps_kernel<2, 8><<<grid, NT, 0, sst_stream(stream)>>>(x, gt, out, H, W, normalize, make_taps<2, 8>(sigma, rho));
-  } else if (r1 == 4 && r2 == 10) {
-    st_maps_kernel<4, 10><<<grid, NT, 0, sst_stream(stream)>>>(x, gt, out, H, W, normalize, make_taps<4, 10>(sigma, rho));
-  } else {
-    return sst_set_error(SST_ERR_UNSUPPORTED, "sst_st_maps: (sigma,rho)=(%g,%g) -> radii (%d,%d) not built", sigma, rho, r1, r2);
-  }
+  if (const int rc = maps_args_ok("sst_st_maps", shape_ok(B, H, W, 65535), B, H, W, gt, out)) return rc;
+  const int r1 = radius_of(sigma), r2 = radius_of(rho);
+  const bool built = with_tile_build(r1, r2, [&](auto R1, auto R2) {
+    st_maps_kernel<R1(), R2()><<<tiles_grid(H, W, B), NT, 0, sst_stream(stream)>>>(x, gt, out, H, W, normalize, make_taps<R1(), R2()>(sigma, rho));
+  });
+  if (!built) return sst_set_error(SST_ERR_UNSUPPORTED, "sst_st_maps: (sigma,rho)=(%g,%g) -> radii (%d,%d) not built", sigma, rho, r1, r2);
   SST_LAUNCH_CHECK("st_maps_kernel");
   return SST_OK;
 }

@@ -1,5 +1,7 @@
-// Structure tensor of one 32x32 tile and the pointwise distance chain: the code st_loss.hip (the criterion) and st_maps.hip (the
-// analysis maps) both run.  Every translation unit that includes this gets its own copy (unnamed namespace).
+// What the structure-tensor family shares: the structure tensor of one 32x32 tile (st_loss.hip, st_maps.hip), and for those two and
+// the separable path (st_general.hip) the pointwise distance chain, the two shared parts of its gradient, the stores of the maps
+// and of d(sr), the host's taps, the list of tile builds and the grid.  Every translation unit that includes this gets its own
+// copy (unnamed namespace).
 //
 // Replaces (reference file:line)
 //   structure_tensor                                utils.py:212-233   (10 separable 'same' zero-padded correlations)
@@ -11,11 +13,13 @@
 // the HEIGHT axis (dim -2) and "y" the width axis.  Plane 0 (Jxx) carries the energy of an image that varies only from row to row,
 // plane 1 (Jyy) that of an image that varies only from column to column, plane 2 is Jxy.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
 
-constexpr int T = 32;     // output tile edge
+constexpr int T = 32;     // output tile edge, of the tile kernels and of every pass of the general path
 constexpr int NT = 1024;  // threads per workgroup (measured fwd+bwd at 96 px, B = 16: 256 -> 50 us, 512 -> 35 us, 1024 -> 29 us: the passes are latency-bound and there are only 144 tiles)
 constexpr int PPT = T * T / NT;   // output pixels per thread
 
@@ -177,9 +181,128 @@ __device__ __forceinline__ StPoint st_pointwise(float a1, float b1, float c1, fl
   return p;
 }
 
-// host: taps exactly like utils.py:194-208 (fp32 exp, fp32 normalisation)
-template <int R>
-void gaussian_taps(float sigma, float* g, float* dg) {
+// ---------------------------------------------------------------------------------------------
+// The analytic gradient of d wrt (a1,b1,c1), unit upstream, in the two parts every forward shares.  Between them each kernel forms
+// dA, dB, dC, dD = d d / d (A, Bm, C, D) itself, from its own discriminant (st_general.hip says why its differs).
+struct StEigGrad { float dl12, ddisc; };   // d d / d l1 + d d / d l2 (twice d d / d ApB through the eigenvalues' mean), d d / d disc
+
+// head: given the eigenvalue-side values the kernel uses (l before / L after the clamp at 1, g their logs, r = sqrt of the clamped disc)
+__device__ __forceinline__ StEigGrad st_grad_eigen(float d, float l1, float l2, float L1, float L2, float g1, float g2, float disc, float r) {
+  const float dq = 0.5f / d;
+  const float dl1 = (l1 >= 1.f) ? dq * 2.f * g1 / L1 : 0.f;
+  const float dl2 = (l2 >= 1.f) ? dq * 2.f * g2 / L2 : 0.f;
+  const float dr = 0.5f * (dl2 - dl1);
+  return {dl1 + dl2, (disc >= 1e-12f) ? dr / (2.f * r) : 0.f};
+}
+
+__device__ __forceinline__ void store_planes(float* __restrict__ out, size_t o, size_t hw, float v0, float v1, float v2) {
+  out[o] = v0;
+  out[o + hw] = v1;
+  out[o + 2 * hw] = v2;
+}
+
+// tail: (dA, dB, dC, dD) -> through inv(S1)*S2 and the normalize correction -> gS[o + {0,1,2} hw] = d d / d (a1, b1, c1)
+__device__ __forceinline__ void st_grad_store(float* __restrict__ gS, size_t o, size_t hw, float dA, float dB, float dC, float dD,
+                                              const StPoint& pt, float a1, float b1, float c1, int normalize) {
+  const float n1 = pt.n1, ah2 = pt.ah2, bh2 = pt.bh2, ch2 = pt.ch2;
+  const float dah = dB * bh2 + dD * ch2;
+  const float dbh = dA * ah2 + dC * ch2;
+  const float dch = -(dA + dB) * ch2 - dC * bh2 - dD * ah2;
+  float ga = dah * n1, gb = dbh * n1, gc = dch * n1;
+  if (normalize) {
+    const float dn = a1 * dah + b1 * dbh + c1 * dch;
+    const float ddet = dn * (-0.5f * n1 * n1 * n1);
+    ga += ddet * b1;
+    gb += ddet * a1;
+    gc -= 2.f * ddet * c1;
+  }
+  store_planes(gS, o, hw, ga, gb, gc);
+}
+
+// d(sr)[o + c hw] (+)= gray_w[c] * v (+ pv[c], a per-channel pixel term, where pv is not null): a gray image's gradient as RGB
+__device__ __forceinline__ void store_gray_grad(float* __restrict__ dsr, size_t o, size_t hw, float v, int accumulate, const float* pv) {
+  // formed inside each branch: the product of an accumulating store contracts with its sum, as it did before the stores were one
+  const auto rgb = [&](int c, float w) { return pv ? w * v + pv[c] : w * v; };
+  if (accumulate) {
+    dsr[o] += rgb(0, 0.2989f);
+    dsr[o + hw] += rgb(1, 0.587f);
+    dsr[o + 2 * hw] += rgb(2, 0.114f);
+  } else {
+    store_planes(dsr, o, hw, rgb(0, 0.2989f), rgb(1, 0.587f), rgb(2, 0.114f));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The maps (sst_st_maps, sst_st_general_maps): each output optional, a null pointer = neither computed nor stored.
+struct StMapsOut {
+  float* Sx;
+  float* Sgt;
+  float* Fx;
+  float* Fgt;
+  float* d;
+  float* tile_sums;
+  __device__ bool want_d() const { return d || tile_sums; }
+};
+
+// (t, c2, s2) of one structure tensor
+__device__ __forceinline__ void store_features(float* __restrict__ out, size_t o, size_t hw, float jxx, float jyy, float jxy) {
+  const float t = jxx + jyy;
+  const float den = t + 1e-12f;
+  store_planes(out, o, hw, t, (jxx - jyy) / den, 2.f * jxy / den);
+}
+
+// One pixel (px within image b's planes) of every map asked for, from J1 = S(x), J2 = S(gt); its d, where wanted, is added to lsum
+__device__ __forceinline__ void maps_pixel(const StMapsOut& out, int b, size_t px, size_t hw, const float (&J1)[3], const float (&J2)[3],
+                                           int normalize, float& lsum) {
+  const size_t o = (size_t)b * 3 * hw + px;
+  if (out.Sx) store_planes(out.Sx, o, hw, J1[0], J1[1], J1[2]);
+  if (out.Sgt) store_planes(out.Sgt, o, hw, J2[0], J2[1], J2[2]);
+  if (out.Fx) store_features(out.Fx, o, hw, J1[0], J1[1], J1[2]);
+  if (out.Fgt) store_features(out.Fgt, o, hw, J2[0], J2[1], J2[2]);
+  if (out.want_d()) {
+    const float d = st_pointwise(J1[0], J1[1], J1[2], J2[0], J2[1], J2[2], normalize).d;
+    if (out.d) out.d[(size_t)b * hw + px] = d;
+    lsum += d;
+  }
+}
+
+// tile_sums[b][tile] = the workgroup's sum of d; the branch is uniform: every thread of every workgroup takes the same side
+template <int NTHREADS>
+__device__ __forceinline__ void maps_tile_sum(const StMapsOut& out, int b, float lsum, float* red) {
+  if (!out.tile_sums) return;
+  const float bsum = block_sum<NTHREADS>(lsum, red);
+  if (threadIdx.x == 0) out.tile_sums[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = bsum;
+}
+
+// ------------------------------------------------------------------------------------------ host
+// What both maps entries ask of their arguments besides their own pointers; `who` is the entry's name.
+int maps_args_ok(const char* who, bool shape_ok, int B, int H, int W, const float* gt, const StMapsOut& out) {
+  SST_REQUIRE(shape_ok, "%s: bad shape B=%d H=%d W=%d", who, B, H, W);
+  SST_REQUIRE(out.Sx || out.Sgt || out.Fx || out.Fgt || out.d || out.tile_sums, "%s: no output requested", who);
+  SST_REQUIRE(gt || !out.Sgt, "%s: Sgt needs gt", who);
+  SST_REQUIRE(gt || !out.Fgt, "%s: Fgt needs gt", who);
+  SST_REQUIRE(gt || !out.d, "%s: d needs gt (the distance is between two images)", who);
+  SST_REQUIRE(gt || !out.tile_sums, "%s: tile_sums cannot be computed without gt (they are sums of d)", who);
+  return SST_OK;
+}
+
+// One workgroup per 32 x 32 tile, in every kernel of the family.  The grid's z carries the images (twice B on the general path, so
+// its entries bound B by 32767 where the tile entries take 65535), its y the tile rows.
+dim3 tiles_grid(int H, int W, int z) { return dim3((W + T - 1) / T, (H + T - 1) / T, z); }
+int64_t tiles_of(int B, int H, int W) { return (int64_t)B * ((H + T - 1) / T) * ((W + T - 1) / T); }
+bool shape_ok(int B, int H, int W, int max_b) { return B > 0 && H > 0 && W > 0 && B <= max_b && (H + T - 1) / T <= 65535; }
+
+// The tile builds: f(R1, R2) with the radii as compile-time values (std::integral_constant) for the build (r1, r2) selects ->
+// whether there is one.
+template <class F>
+bool with_tile_build(int r1, int r2, F&& f) {
+  if (r1 == 2 && r2 == 8) return f(std::integral_constant<int, 2>{}, std::integral_constant<int, 8>{}), true;
+  if (r1 == 4 && r2 == 10) return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 10>{}), true;
+  return false;
+}
+
+// taps exactly like utils.py:194-208 (fp32 exp, fp32 normalisation)
+void gaussian_taps(float sigma, int R, float* g, float* dg) {
   const float sigma2 = (float)((double)sigma * (double)sigma + 1e-12);
   const float c = (float)(-0.5 / ((double)sigma * (double)sigma + 1e-12));
   float s = 0.f;
@@ -202,8 +325,8 @@ int radius_of(float s) {
 template <int R1, int R2>
 StTaps<R1, R2> make_taps(float sigma, float rho) {
   StTaps<R1, R2> tp;
-  gaussian_taps<R1>(sigma, tp.g, tp.dg);
-  gaussian_taps<R2>(rho, tp.k, nullptr);
+  gaussian_taps(sigma, R1, tp.g, tp.dg);
+  gaussian_taps(rho, R2, tp.k, nullptr);
   return tp;
 }
 

@@ -17,13 +17,12 @@ double-angle features (t, c2, s2):
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch import Tensor
 
 from . import _abi
 from ._abi import HipPathError
+from .loss import _workspace, st_route
 
 OUTPUTS = ("Sx", "Sgt", "Fx", "Fgt", "d", "tile_sums", "distance")
 _NEED_GT = ("Sgt", "Fgt", "d", "tile_sums", "distance")
@@ -31,17 +30,12 @@ _NEED_GT = ("Sgt", "Fgt", "d", "tile_sums", "distance")
 
 def workspace_floats(B: int, H: int, W: int) -> int:
     """Number of 32 x 32 tiles of a [B,3,H,W] batch = floats of ``tile_sums``."""
-    n = ctypes.c_int64()
-    _abi.check(_abi.lib().sst_st_maps_workspace(B, H, W, ctypes.byref(n)), "sst_st_maps_workspace")
-    return n.value
+    return _workspace("st_maps", B, H, W, n=1)[0]
 
 
 def general_scratch_floats(B: int, H: int, W: int) -> int:
     """Floats of the plane workspace of the general path (csrc/st_general.hip: sst_st_general_maps) = 14 B H W."""
-    scratch, saved, partials = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
-    _abi.check(_abi.lib().sst_st_general_workspace(B, H, W, ctypes.byref(scratch), ctypes.byref(saved), ctypes.byref(partials)),
-               "sst_st_general_workspace")
-    return scratch.value
+    return _workspace("st_general", B, H, W, n=3)[0]
 
 
 def _checked(name: str, t) -> Tensor:
@@ -85,7 +79,6 @@ def st_maps(sr: Tensor, gt: Tensor | None = None, sigma: float = 0.5, rho: float
         if missing:
             raise HipPathError(f"st_maps: {missing} need gt")
     B, _, H, W = sr.shape
-    from .loss import st_route
     general, _ = st_route(sigma, rho, "st_maps")
     with torch.no_grad(), torch.cuda.device(sr.device):
         def new(*shape):

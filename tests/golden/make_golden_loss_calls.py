@@ -96,12 +96,15 @@ def _hex(t):
     return float(t.detach()).hex()
 
 
-def step(fn, shape=(B, H, W), mode="grad", fuse=True, force_general=False, extra=None, second=None):
+def step(fn, shape=(B, H, W), mode="grad", fuse=True, force_general=False, extra=None, second=None, scale=1.0):
     """One recorded call of fn(sr, gt) -> total or (total, {name: value} / [values]).  mode: "grad", "no_grad" (under
     torch.no_grad()) or "no_requires" (sr does not require a gradient).  second: gt on the device -> what fn gets in gt's place (made
-    before the recording starts); extra may take (sr, that second argument)."""
+    before the recording starts); extra may take (sr, that second argument).  scale: what the images are multiplied by (255: the
+    0..255 scale)."""
     import torch
     sr, gt = images(*shape)
+    if scale != 1.0:
+        sr, gt = sr * scale, gt * scale
     sr = sr.cuda().requires_grad_(mode != "no_requires")
     gt = gt.cuda()
     if second is not None:
@@ -260,9 +263,23 @@ def cases():
     # second, ragged pass.  The counts are the entries' own (sst_*_workspace: partial floats / 2).
     for name, make, shape in MANY_PARTIALS:
         alone(f"{name} at {shape}: {many_partials(name)} partials", make, shape=(shape[0], shape[2], shape[3]))
+
+    # --- the structure-tensor family (recorded before its three sources came to share csrc/st_tile.h): the <4,10> tile build, the
+    # general route at radii (4, 8) and at its bound (8, 20), normalize=False on 0..255 inputs on either route, the fused pair on
+    # the <4,10> build
+    for shape in ST_SHAPES:
+        at = f" at {list(shape)}"
+        alone("ST(1,2.5)" + at, lambda: ST(1.0, 2.5), shape=shape)
+        alone("ST(1,2)" + at, lambda: ST(1.0, 2.0), shape=shape)
+        alone("ST(2,5)" + at, lambda: ST(2.0, 5.0), shape=shape)
+        alone("ST(0.5,2) normalize=False on 0..255" + at, lambda: ST(0.5, 2.0, normalize=False), shape=shape, scale=255.0)
+        alone("ST(1,2) normalize=False on 0..255" + at, lambda: ST(1.0, 2.0, normalize=False), shape=shape, scale=255.0)
+        summed("sum[L1, ST(1,2.5)]" + at, lambda: [L.L1Loss(), ST(1.0, 2.5)], [1.0, 1 / 3], shape=shape)
     return out
 
 
+# partial tiles on both axes with W no multiple of 4; smaller than every halo; exactly one tile
+ST_SHAPES = ((2, 33, 31), (1, 5, 3), (2, 32, 32))
 MANY_PARTIALS = [("SSIM(rgb)", lambda: _loss().SSIMLoss("rgb"), (16, 3, 43, 75)),
                  ("Frequency(1.0)", lambda: _loss().FocalFrequencyLoss(), (43, 3, 48, 48)),
                  ("BP(4,l1)", lambda: _loss().BackProjectionLoss(4), (16, 3, 38, 262))]

@@ -8,20 +8,15 @@ import numpy as np
 import pytest
 import torch
 
+from abi_checks import FAKE, ST_MAPS_REFUSALS, st_maps_call, st_maps_refuses
+from abi_checks import lib as _lib
 from conftest import rel_err
-
-FAKE = 0x1000          # stands for a device pointer in calls that are refused on the host: never dereferenced
 
 # (sigma, rho) -> radii: the pairs of the GPU tests (tests/test_st_general_gpu.py)
 GENERAL = {(0.3, 0.3): (1, 1), (0.35, 0.6): (1, 2), (0.35, 5.0): (1, 20), (0.5, 1.0): (2, 4), (0.7, 1.4): (3, 6), (1.0, 2.0): (4, 8),
            (1.0, 0.6): (4, 2), (1.5, 3.0): (6, 12), (2.0, 1.0): (8, 4), (2.0, 5.0): (8, 20), (2.1, 5.1): (8, 20)}
 TILE = {(0.5, 2.0): (2, 8), (1.0, 2.5): (4, 10)}
 BEYOND = {(2.2, 2.0): (9, 8), (1.0, 5.2): (4, 21), (1.0, 10.0): (4, 40)}
-
-
-def _lib():
-    from srganst import _abi
-    return _abi.lib()
 
 
 def _route(sigma, rho):
@@ -109,10 +104,8 @@ def _bwd(ptrs=(FAKE,) * 4, scale_dev=None, shape=(2, 40, 40), sigma=1.0, rho=2.0
     return lib.sst_st_general_bwd(*ptrs, scale_dev, 1.0, 0, *shape, sigma, rho, None), lib.sst_last_error()
 
 
-def _maps(x=FAKE, gt=FAKE, Sx=None, Sgt=None, Fx=None, Fgt=None, d=None, tile_sums=None, scratch=FAKE, shape=(2, 40, 40), sigma=1.0,
-          rho=2.0):
-    lib = _lib()
-    return lib.sst_st_general_maps(x, gt, Sx, Sgt, Fx, Fgt, d, tile_sums, scratch, *shape, sigma, rho, 1, None), lib.sst_last_error()
+def _maps(sigma=1.0, rho=2.0, **kw):
+    return st_maps_call("sst_st_general_maps", sigma=sigma, rho=rho, **kw)
 
 
 BAD_SHAPES = [(0, 40, 40), (2, 0, 40), (2, 40, -3), (32768, 40, 40)]
@@ -148,19 +141,9 @@ def test_entries_refuse_radii_beyond_the_bound(pair):
         assert rc == -2 and err == name.encode() + tail, (rc, err)
 
 
-@pytest.mark.parametrize("kwargs, message", [
-    (dict(x=None, Sx=FAKE), b"null pointer"),
-    (dict(scratch=None, Sx=FAKE), b"null pointer"),
-    (dict(gt=None, Sgt=FAKE), b"Sgt needs gt"),
-    (dict(gt=None, Fgt=FAKE), b"Fgt needs gt"),
-    (dict(gt=None, d=FAKE), b"d needs gt"),
-    (dict(gt=None, tile_sums=FAKE), b"tile_sums cannot be computed without gt"),
-    (dict(), b"no output requested"),
-    (dict(gt=None), b"no output requested"),
-])
+@pytest.mark.parametrize("kwargs, message", ST_MAPS_REFUSALS[:1] + [(dict(scratch=None, Sx=FAKE), b"null pointer")] + ST_MAPS_REFUSALS[1:])
 def test_maps_host_side_refusals(kwargs, message):
-    rc, err = _maps(**kwargs)
-    assert rc == -1 and message in err, (rc, err)
+    st_maps_refuses("sst_st_general_maps", dict(sigma=1.0, rho=2.0, **kwargs), message)
 
 
 def test_the_tile_entries_keep_their_refusals():

@@ -10,58 +10,28 @@ radii) and l64 / g64 from the same oracle in fp64.  Every case proves from the f
 the measured errors."""
 import ctypes
 import functools
-import math
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import st_checks
 import term_checks
 from conftest import rel_err, truth_bound
+from st_checks import BUILDS, UP, radius_of
+from st_checks import check_loss as _check
+from st_checks import frac_l2_above_1 as _frac_l2_above_1
+from st_checks import images as _images
+from st_checks import loss_hip as _hip
+from st_checks import loss_oracle as _oracle
 
 pytestmark = pytest.mark.gpu
-
-UP = 0.7                                              # non-unit upstream gradient throughout
-
-
-def radius_of(s):
-    """csrc/st_tile.h radius_of: the kernel sees sigma / rho as fp32."""
-    return max(int(4.0 * float(np.float32(s)) + 0.5), 1)
-
 
 # (sigma, rho) -> radii, none of them a tile build: smallest radii, R2 < R1, the widest k next to the narrowest g, the bound, and the
 # largest values that still round into it
 PAIRS = {(0.3, 0.3): (1, 1), (0.35, 0.6): (1, 2), (0.35, 5.0): (1, 20), (0.5, 1.0): (2, 4), (0.7, 1.4): (3, 6), (1.0, 2.0): (4, 8),
          (1.0, 0.6): (4, 2), (1.5, 3.0): (6, 12), (2.0, 1.0): (8, 4), (2.0, 5.0): (8, 20), (2.1, 5.1): (8, 20)}
-BUILDS = {(2, 8): (0.5, 2.0), (4, 10): (1.0, 2.5)}   # the tile builds' pairs, for the forced runs
-
-
-def _images(seed, B, H, W, noise=0.08, scale=1.0):
-    """tests/test_st_loss_fp64_gpu.py:_images - smooth texture (bicubic-upsampled noise) for gt and gt + noise for sr, both in
-    [0, 1] x scale."""
-    gen = torch.Generator().manual_seed(seed)
-    base = torch.rand(B, 3, max(H // 6, 2), max(W // 6, 2), generator=gen)
-    gt = F.interpolate(base, size=(H, W), mode="bicubic", align_corners=False)
-    gt = (gt + 0.05 * torch.randn(gt.shape, generator=gen)).clamp(0, 1)
-    x = (gt + noise * torch.randn(gt.shape, generator=gen)).clamp(0, 1)
-    return x * scale, gt * scale
-
-
-def _hip(x, gt, sigma, rho, norm):
-    from srganst.loss import StructureTensorLoss
-    xg = x.cuda().requires_grad_(True)
-    loss = StructureTensorLoss(sigma, rho, norm)(xg, gt.cuda())
-    (gx,) = torch.autograd.grad(loss * UP, xg)
-    torch.cuda.synchronize()
-    return loss.detach().cpu().double(), gx.cpu().double() / UP
-
-
-def _oracle(x, gt, sigma, rho, norm):
-    from oracle import st as ost
-    l32, g32 = ost.st_loss_and_grad(x, gt, sigma, rho, norm)
-    l64, g64 = ost.st_loss_and_grad(x.double(), gt.double(), sigma, rho, norm)
-    return l32.double(), g32.double(), l64, g64
 
 
 @functools.lru_cache(maxsize=None)
@@ -69,23 +39,6 @@ def _case(seed, B, H, W, sigma, rho, norm):
     """Inputs, oracle results and the non-vacuity figure of one standard case, computed once and shared (never modified)."""
     x, gt = _images(seed, B, H, W, scale=1.0 if norm else 255.0)
     return x, gt, _oracle(x, gt, sigma, rho, norm), _frac_l2_above_1(x, gt, sigma, rho, norm)
-
-
-def _check(name, hip, ref, grad=True):
-    """Applies the fp64-truth rule to (loss, grad) and prints the measured errors."""
-    (lh, gh), (l32, g32, l64, g64) = hip, ref
-    e_l, b_l = abs(lh - l64).item(), max(1e-3 * abs(l64).item(), 3 * abs(l32 - l64).item())
-    e_g, b_g = rel_err(gh, g64), truth_bound(g32, g64)
-    print(f"[{name}] loss {lh.item():.6e} |hip-l64| {e_l:.3e} <= {b_l:.3e} | grad rel err {e_g:.3e} <= {b_g:.3e}")
-    assert torch.isfinite(lh) and bool(torch.isfinite(gh).all()), name
-    assert e_l <= b_l, f"{name}: loss |hip - fp64| = {e_l:.3e} > {b_l:.3e} (hip {lh.item():.9e}, fp64 {l64.item():.9e})"
-    if grad:
-        assert e_g <= b_g, f"{name}: grad rel err {e_g:.3e} > {b_g:.3e}"
-
-
-def _frac_l2_above_1(x, gt, sigma, rho, norm):
-    from oracle import st as ost
-    return float((ost.st_intermediates(x.double(), gt.double(), sigma, rho, norm)["L"][:, 1] > 1).double().mean())
 
 
 def test_pairs_are_off_the_tile_builds_and_inside_the_bound():
@@ -134,13 +87,6 @@ def test_gs_pointwise_vs_fp64(sigma, rho, norm):
     torch.cuda.synchronize()
     assert counter.item() == 0                                          # the ticket counter re-armed itself
 
-    def ref(dtype):
-        S1 = ost.structure_tensor(ost.grayscale(x.to(dtype)), sigma, rho).requires_grad_(True)
-        S2 = ost.structure_tensor(ost.grayscale(gt.to(dtype)), sigma, rho)
-        d = ost.pixel_distance(S1, S2, norm)
-        (g,) = torch.autograd.grad(d.sum(), S1)
-        return d.detach(), g.double()
-
     def grads(dtype):                                                    # Ix, Iy of sr: utils.py:219-222
         im = ost.grayscale(x.to(dtype))
         g, dg = ost.gaussian_kernel(sigma, also_dg=True, dtype=dtype)
@@ -148,17 +94,11 @@ def test_gs_pointwise_vs_fp64(sigma, rho, norm):
         iy = F.conv2d(F.conv2d(im, g.reshape(1, 1, -1, 1), padding="same"), dg.reshape(1, 1, 1, -1), padding="same")
         return torch.stack((ix[:, 0], iy[:, 0]))
 
-    (d32, gs32), (d64, gs64) = ref(torch.float32), ref(torch.float64)
-    frac = _frac_l2_above_1(x, gt, sigma, rho, norm)
-    assert frac >= 0.1 and float(gs64.abs().max()) > 0, frac
-    e, b = rel_err(gS.cpu(), gs64), truth_bound(gs32, gs64)
+    st_checks.check_gs(f"B gS sigma={sigma} rho={rho} normalize={norm}", x, gt, sigma, rho, norm, gS, loss)
     e_i, b_i = rel_err(saved.cpu().reshape(2, B, H, W), grads(torch.float64)), truth_bound(grads(torch.float32), grads(torch.float64))
-    print(f"[B gS sigma={sigma} rho={rho} normalize={norm}] rel err {e:.3e} <= {b:.3e}; saved Ix, Iy {e_i:.3e} <= {b_i:.3e}; "
-          f"loss {loss.item():.6e} vs fp64 {d64.mean().item():.6e}")
-    assert bool(torch.isfinite(gS).all()) and bool(torch.isfinite(saved).all())
-    assert e <= b, (e, b)
+    print(f"[B gS sigma={sigma} rho={rho} normalize={norm}] saved Ix, Iy {e_i:.3e} <= {b_i:.3e}")
+    assert bool(torch.isfinite(saved).all())
     assert e_i <= b_i, (e_i, b_i)
-    assert abs(loss.item() - d64.mean().item()) <= max(1e-3 * d64.mean().item(), 3 * abs(d32.double().mean() - d64.mean()).item())
 
 
 # ------------------------------------------------------------------------------------------------ C. geometry
@@ -182,22 +122,8 @@ def test_geometry(sigma, rho, H):
 def test_batch_independence():
     """Five distinct images: the batched loss is the mean of the five single-image losses, and permuting the batch permutes the
     gradient bit for bit (the plane index of every pass)."""
-    from srganst.loss import StructureTensorLoss
     sigma, rho = 1.0, 2.0
-    x, gt = _images(9, 5, 37, 70)
-    x[2] = x[2] * 0.5                                  # make the images differ in more than their noise
-    gt[4] = gt[4].flip(-1)
-    assert _frac_l2_above_1(x, gt, sigma, rho, True) >= 0.1
-    crit = StructureTensorLoss(sigma, rho)
-    lh, gh = _hip(x, gt, sigma, rho, True)
-    singles = [crit(x[i:i + 1].cuda(), gt[i:i + 1].cuda()).item() for i in range(5)]
-    assert len(set(singles)) == 5
-    assert abs(lh.item() - np.mean(singles)) <= 1e-6 * abs(lh.item()), (lh.item(), singles)
-    perm = torch.tensor([3, 0, 4, 1, 2])
-    lp, gp = _hip(x[perm].contiguous(), gt[perm].contiguous(), sigma, rho, True)
-    assert torch.equal(gp, gh[perm])
-    assert abs(lp - lh).item() <= 1e-6 * abs(lh.item())
-    _check("D batch", (lh, gh), _oracle(x, gt, sigma, rho, True))
+    st_checks.check_batch_independence("D batch", *_images(9, 5, 37, 70), sigma, rho)
 
 
 # ------------------------------------------------------------------------------------------------ E. forced onto the tile builds' pairs
@@ -284,58 +210,14 @@ def test_nan_in_sr(where):
     are bit-identical to a run without the bad value.  In the affected image the gradient is non-finite exactly where the oracle's
     is, and every pixel farther than 2 (R1 + R2) from the bad one (outside its receptive field through forward and backward) is
     bit-identical to the clean run."""
-    from oracle import st as ost
-    sigma, rho = 1.0, 2.0
-    R = radius_of(sigma) + radius_of(rho)
-    H, W = 64, 68
-    x, gt = _images(77 + len(where), 3, H, W)
+    x, gt = _images(77 + len(where), 3, 64, 68)
     yx = (0, 0) if where == "corner" else (30, 33)
     xb = x.clone()
     xb[1, 1, yx[0], yx[1]] = float("nan")
-    _, gh_clean = _hip(x, gt, sigma, rho, True)
-    lh, gh = _hip(xb, gt, sigma, rho, True)
-    l32, g32 = ost.st_loss_and_grad(xb, gt, sigma, rho, True)
-    print(f"[G {where}] loss {lh.item()} (oracle {l32.item()}), non-finite grads hip {int((~torch.isfinite(gh)).sum())} "
-          f"oracle {int((~torch.isfinite(g32)).sum())}")
-    assert not bool(torch.isfinite(l32))
-    assert bool(torch.isfinite(lh)) == bool(torch.isfinite(l32)), (lh.item(), l32.item())
-    for b in (0, 2):
-        assert torch.equal(gh[b], gh_clean[b]), b
-    bad = ~torch.isfinite(g32[1])
-    assert bool(bad.any())
-    assert torch.equal(~torch.isfinite(gh[1]), bad), "non-finite gradient pattern differs from the oracle's"
-    far = torch.ones(H, W, dtype=torch.bool)
-    far[max(yx[0] - 2 * R, 0):yx[0] + 2 * R + 1, max(yx[1] - 2 * R, 0):yx[1] + 2 * R + 1] = False
-    assert bool(far.any())
-    assert torch.equal(gh[1][:, far], gh_clean[1][:, far])
-    assert bool(torch.isfinite(g32[1][:, far]).all())
+    st_checks.check_non_finite(f"G {where}", x, gt, xb, gt, yx, 1.0, 2.0)
 
 
 # ------------------------------------------------------------------------------------------------ H. maps
-ALL = ("Sx", "Sgt", "Fx", "Fgt", "d", "tile_sums", "distance")
-
-
-def _features(S):
-    """(t, c2, s2) planes of S [B,3,H,W] in S's dtype: the definition in srganst/st.py."""
-    t = S[:, 0] + S[:, 1]
-    den = t + 1e-12
-    return torch.stack((t, (S[:, 0] - S[:, 1]) / den, 2 * S[:, 2] / den), dim=1)
-
-
-def _maps_oracle(x, gt, sigma, rho, norm, dtype):
-    from oracle import st as ost
-    it = ost.st_intermediates(x.to(dtype), gt.to(dtype), sigma, rho, norm)
-    return {"Sx": it["S1"], "Sgt": it["S2"], "Fx": _features(it["S1"]), "Fgt": _features(it["S2"]), "d": it["d"], "L": it["L"],
-            "distance": it["d"].mean(dim=(1, 2))}
-
-
-def _maps_hip(x, gt, sigma, rho, norm=True, want=ALL):
-    from srganst import st
-    out = st.st_maps(x.cuda(), None if gt is None else gt.cuda(), sigma, rho, norm, want=want)
-    torch.cuda.synchronize()
-    return {k: v.cpu() for k, v in out.items()}
-
-
 @pytest.mark.parametrize("norm", [True, False])
 @pytest.mark.parametrize("sigma, rho", [(1.0, 2.0), (2.0, 5.0)])
 def test_maps_vs_fp64(sigma, rho, norm):
@@ -344,42 +226,14 @@ def test_maps_vs_fp64(sigma, rho, norm):
     from srganst.loss import StructureTensorLoss
     B, H, W = 2, 70, 45
     x, gt = _images(300 + radius_of(sigma) + norm, B, H, W, scale=1.0 if norm else 255.0)
-    o32, o64 = _maps_oracle(x, gt, sigma, rho, norm, torch.float32), _maps_oracle(x, gt, sigma, rho, norm, torch.float64)
-    frac = float((o64["L"][:, 1] > 1).double().mean())
-    assert frac >= 0.1, f"vacuous case: only {frac:.1%} of the pixels have l2 > 1"
-    trace = min(float(o64["Fx"][:, 0].min()), float(o64["Fgt"][:, 0].min()))
-    assert trace >= 1.7e-5, f"trace {trace:.3e}: the 1e-12 guard of the features would take part"
-    got = _maps_hip(x, gt, sigma, rho, norm)
-    name = f"H sigma={sigma} rho={rho} normalize={norm} {B}x{H}x{W}"
-    for key in ("Sx", "Sgt", "d", "Fx", "Fgt"):
-        assert got[key].dtype == torch.float32 and got[key].shape == o64[key].shape, (key, got[key].shape)
-        assert bool(torch.isfinite(got[key]).all()), key
-        e, b = rel_err(got[key], o64[key]), truth_bound(o32[key], o64[key])
-        print(f"[{name}] {key}: rel err {e:.3e} <= {b:.3e}")
-        assert e <= b, f"{name} {key}: rel err {e:.3e} > {b:.3e}"
-    tiles = ((H + 31) // 32) * ((W + 31) // 32)
-    assert tuple(got["tile_sums"].shape) == (B, tiles) and got["distance"].dtype == torch.float64
-    l32, l64 = o32["distance"].double(), o64["distance"]
-    for b in range(B):
-        e, bound = abs(got["distance"][b].item() - l64[b].item()), max(1e-3 * abs(l64[b].item()), 3 * abs(l32[b].item() - l64[b].item()))
-        print(f"[{name}] image {b}: distance {got['distance'][b].item():.6e} |hip-l64| {e:.3e} <= {bound:.3e}")
-        assert math.isfinite(got["distance"][b].item()) and e <= bound, (b, e, bound)
+    got = st_checks.check_maps_vs_fp64(f"H sigma={sigma} rho={rho} normalize={norm} {B}x{H}x{W}", x, gt, sigma, rho, norm, min_trace=1.7e-5)
     loss = StructureTensorLoss(sigma, rho, norm)(x.cuda(), gt.cuda()).item()
     assert abs(got["distance"].mean().item() - loss) <= 1e-6 * abs(loss), (got["distance"].mean().item(), loss)
 
 
 @pytest.mark.parametrize("sigma, rho", [(1.0, 2.0), (2.0, 5.0)])
 def test_maps_optional_outputs_are_the_same_bits(sigma, rho):
-    x, gt = _images(51 + radius_of(sigma), 2, 33, 31)
-    full = _maps_hip(x, gt, sigma, rho)
-    for key in ALL:
-        alone = _maps_hip(x, gt, sigma, rho, want=(key,))
-        assert list(alone) == [key]
-        assert torch.equal(alone[key], full[key]), f"{key} requested alone differs from the all-outputs call"
-    x_only = _maps_hip(x, None, sigma, rho, want=("Sx", "Fx"))
-    assert torch.equal(x_only["Sx"], full["Sx"]) and torch.equal(x_only["Fx"], full["Fx"])
-    swapped = _maps_hip(gt, x, sigma, rho, want=("Sx", "Sgt"))             # both images run the same passes
-    assert torch.equal(swapped["Sx"], full["Sgt"]) and torch.equal(swapped["Sgt"], full["Sx"])
+    st_checks.check_optional_outputs_are_the_same_bits(*_images(51 + radius_of(sigma), 2, 33, 31), sigma, rho)
 
 
 # ------------------------------------------------------------------------------------------------ I. graph capture

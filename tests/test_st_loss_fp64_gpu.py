@@ -6,68 +6,22 @@ fp64-truth rule (conftest): loss   |hip - l64| <= max(1e-3 |l64|, 3 |l32 - l64|)
                             grads  rel_err(hip, g64) <= max(1e-3, 3 rel_err(g32, g64))
 where l32 / g32 come from the fp32 oracle (the reference's arithmetic) and l64 / g64 from the same oracle in fp64.  Every case proves
 from the fp64 oracle that it is not vacuous.  Run with -s for the measured errors."""
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import rel_err, truth_bound
+import st_checks
+from conftest import rel_err
+from st_checks import BUILDS, UP, radius_of
+from st_checks import check_loss as _check
+from st_checks import frac_l2_above_1 as _frac_l2_above_1
+from st_checks import images as _images
+from st_checks import loss_hip as _hip
+from st_checks import loss_oracle as _oracle
 
 pytestmark = pytest.mark.gpu
 
-UP = 0.7                                              # non-unit upstream gradient throughout
-
-
-def radius_of(s):
-    """csrc/st_loss.hip radius_of: the kernel sees sigma / rho as fp32."""
-    return max(int(4.0 * float(np.float32(s)) + 0.5), 1)
-
-
-BUILDS = {(2, 8): (0.5, 2.0), (4, 10): (1.0, 2.5)}   # the two instantiated <R1, R2> pairs -> a (sigma, rho) that selects each
 PARAMS = [(0.5, 2.0), (0.4, 1.9), (0.6, 2.1), (1.0, 2.5), (0.9, 2.4), (1.1, 2.6)]
-
-
-def _images(seed, B, H, W, noise=0.08, scale=1.0):
-    """Smooth texture (bicubic-upsampled noise) for gt and gt + noise for sr, both in [0, 1] x scale."""
-    gen = torch.Generator().manual_seed(seed)
-    base = torch.rand(B, 3, max(H // 6, 2), max(W // 6, 2), generator=gen)
-    gt = F.interpolate(base, size=(H, W), mode="bicubic", align_corners=False)
-    gt = (gt + 0.05 * torch.randn(gt.shape, generator=gen)).clamp(0, 1)
-    x = (gt + noise * torch.randn(gt.shape, generator=gen)).clamp(0, 1)
-    return x * scale, gt * scale
-
-
-def _hip(x, gt, sigma, rho, norm):
-    from srganst.loss import StructureTensorLoss
-    xg = x.cuda().requires_grad_(True)
-    loss = StructureTensorLoss(sigma, rho, norm)(xg, gt.cuda())
-    (gx,) = torch.autograd.grad(loss * UP, xg)
-    torch.cuda.synchronize()
-    return loss.detach().cpu().double(), gx.cpu().double() / UP
-
-
-def _oracle(x, gt, sigma, rho, norm):
-    from oracle import st as ost
-    l32, g32 = ost.st_loss_and_grad(x, gt, sigma, rho, norm)
-    l64, g64 = ost.st_loss_and_grad(x.double(), gt.double(), sigma, rho, norm)
-    return l32.double(), g32.double(), l64, g64
-
-
-def _check(name, hip, ref, grad=True):
-    """Applies the fp64-truth rule to (loss, grad) and prints the measured errors."""
-    (lh, gh), (l32, g32, l64, g64) = hip, ref
-    e_l, b_l = abs(lh - l64).item(), max(1e-3 * abs(l64).item(), 3 * abs(l32 - l64).item())
-    e_g, b_g = rel_err(gh, g64), truth_bound(g32, g64)
-    print(f"[{name}] loss {lh.item():.6e} |hip-l64| {e_l:.3e} <= {b_l:.3e} | grad rel err {e_g:.3e} <= {b_g:.3e}")
-    assert torch.isfinite(lh) and bool(torch.isfinite(gh).all()), name
-    assert e_l <= b_l, f"{name}: loss |hip - fp64| = {e_l:.3e} > {b_l:.3e} (hip {lh.item():.9e}, fp64 {l64.item():.9e})"
-    if grad:
-        assert e_g <= b_g, f"{name}: grad rel err {e_g:.3e} > {b_g:.3e}"
-
-
-def _frac_l2_above_1(x, gt, sigma, rho, norm):
-    from oracle import st as ost
-    return float((ost.st_intermediates(x.double(), gt.double(), sigma, rho, norm)["L"][:, 1] > 1).double().mean())
 
 
 def test_param_grid_covers_both_builds():
@@ -131,13 +85,12 @@ def test_criterion_sum_fused_pair(monkeypatch, pix, sigma, rho, norm):
 def test_gs_pointwise_vs_fp64(radii, norm):
     """gS = d(per-pixel distance) / d(Jxx, Jyy, Jxy of sr) straight from sst_st_loss_fwd, against fp64 autograd of the oracle's
     pointwise math (normalize, inverse, eigenvalues, distance) on the fp64 structure tensors; yardstick: the same autograd in fp32."""
-    from oracle import st as ost
+    import ctypes
     from srganst import _abi
     sigma, rho = BUILDS[radii]
     B, H, W = 2, 45, 38
     x, gt = _images(23 + norm + radii[0], B, H, W, scale=1.0 if norm else 255.0)
     lib = _abi.lib()
-    import ctypes
     n = ctypes.c_int64()
     _abi.check(lib.sst_st_loss_workspace(B, H, W, ctypes.byref(n)), "sst_st_loss_workspace")
     xd, gd = x.cuda(), gt.cuda()
@@ -148,22 +101,7 @@ def test_gs_pointwise_vs_fp64(radii, norm):
     _abi.check(lib.sst_st_loss_fwd(_abi.ptr(xd), _abi.ptr(gd), _abi.ptr(loss), _abi.ptr(gS), _abi.ptr(partials), _abi.ptr(counter),
                                    B, H, W, sigma, rho, int(norm), _abi.stream_ptr()), "sst_st_loss_fwd")
     torch.cuda.synchronize()
-
-    def ref(dtype):
-        S1 = ost.structure_tensor(ost.grayscale(x.to(dtype)), sigma, rho).requires_grad_(True)
-        S2 = ost.structure_tensor(ost.grayscale(gt.to(dtype)), sigma, rho)
-        d = ost.pixel_distance(S1, S2, norm)
-        (g,) = torch.autograd.grad(d.sum(), S1)
-        return d.detach(), g.double()
-
-    (d32, gs32), (d64, gs64) = ref(torch.float32), ref(torch.float64)
-    frac = _frac_l2_above_1(x, gt, sigma, rho, norm)
-    assert frac >= 0.1 and float(gs64.abs().max()) > 0, frac
-    e, b = rel_err(gS.cpu(), gs64), truth_bound(gs32, gs64)
-    print(f"[C gS radii={radii} normalize={norm}] rel err {e:.3e} <= {b:.3e}; loss {loss.item():.6e} vs fp64 {d64.mean().item():.6e}")
-    assert bool(torch.isfinite(gS).all())
-    assert e <= b, (e, b)
-    assert abs(loss.item() - d64.mean().item()) <= max(1e-3 * d64.mean().item(), 3 * abs(d32.double().mean() - d64.mean()).item())
+    st_checks.check_gs(f"C gS radii={radii} normalize={norm}", x, gt, sigma, rho, norm, gS, loss)
 
 
 # ------------------------------------------------------------------------------------------------ D. geometry and batch
@@ -188,21 +126,8 @@ def test_geometry(radii, H):
 def test_batch_independence(radii):
     """Five distinct images: the batched loss is the mean of the five single-image losses, and permuting the batch permutes the
     gradient bit for bit (img_off / blockIdx.z)."""
-    from srganst.loss import StructureTensorLoss
     sigma, rho = BUILDS[radii]
-    x, gt = _images(5 + radii[0], 5, 37, 70)
-    x[2] = x[2] * 0.5                                  # make the images differ in more than their noise
-    gt[4] = gt[4].flip(-1)
-    crit = StructureTensorLoss(sigma, rho)
-    lh, gh = _hip(x, gt, sigma, rho, True)
-    singles = [crit(x[i:i + 1].cuda(), gt[i:i + 1].cuda()).item() for i in range(5)]
-    assert len(set(singles)) == 5
-    assert abs(lh.item() - np.mean(singles)) <= 1e-6 * abs(lh.item()), (lh.item(), singles)
-    perm = torch.tensor([3, 0, 4, 1, 2])
-    lp, gp = _hip(x[perm].contiguous(), gt[perm].contiguous(), sigma, rho, True)
-    assert torch.equal(gp, gh[perm])
-    assert abs(lp - lh).item() <= 1e-6 * abs(lh.item())
-    _check(f"D batch radii={radii}", (lh, gh), _oracle(x, gt, sigma, rho, True))
+    st_checks.check_batch_independence(f"D batch radii={radii}", *_images(5 + radii[0], 5, 37, 70), sigma, rho)
 
 
 # ------------------------------------------------------------------------------------------------ E. numerical regimes
@@ -271,30 +196,12 @@ def test_non_finite_inputs(kind, where):
     value.  In the affected image the gradient is non-finite exactly where the oracle's is (the kernel's masked branches multiply
     0 x NaN as autograd does), and every pixel farther than 2 (R1 + R2) from the bad one (outside its receptive field through forward
     and backward) is bit-identical to the clean run."""
-    sigma, rho = 0.5, 2.0
-    R = radius_of(sigma) + radius_of(rho)
     x, gt = _images(77 + len(kind) + len(where), 3, 40, 44)
     yx = (0, 0) if where == "corner" else (17, 23)
     v = {"nan": float("nan"), "posinf": float("inf"), "neginf": float("-inf")}[kind.split("-")[1]]
     xb, gtb = x.clone(), gt.clone()
     (xb if kind.startswith("sr") else gtb)[1, 1, yx[0], yx[1]] = v
-    _, gh_clean = _hip(x, gt, sigma, rho, True)
-    lh, gh = _hip(xb, gtb, sigma, rho, True)
-    from oracle import st as ost
-    l32, g32 = ost.st_loss_and_grad(xb, gtb, sigma, rho, True)
-    print(f"[F {kind} {where}] loss {lh.item()} (oracle {l32.item()}), non-finite grads hip {int((~torch.isfinite(gh)).sum())} "
-          f"oracle {int((~torch.isfinite(g32)).sum())}")
-    assert not bool(torch.isfinite(l32))
-    assert bool(torch.isfinite(lh)) == bool(torch.isfinite(l32)), (lh.item(), l32.item())
-    for b in (0, 2):
-        assert torch.equal(gh[b], gh_clean[b]), b
-    bad = ~torch.isfinite(g32[1])
-    assert bool(bad.any())
-    assert torch.equal(~torch.isfinite(gh[1]), bad), "non-finite gradient pattern differs from the oracle's"
-    far = torch.ones(40, 44, dtype=torch.bool)
-    far[max(yx[0] - 2 * R, 0):yx[0] + 2 * R + 1, max(yx[1] - 2 * R, 0):yx[1] + 2 * R + 1] = False
-    assert torch.equal(gh[1][:, far], gh_clean[1][:, far])
-    assert bool(torch.isfinite(g32[1][:, far]).all())
+    st_checks.check_non_finite(f"F {kind} {where}", x, gt, xb, gtb, yx, 0.5, 2.0)
 
 
 # ------------------------------------------------------------------------------------------------ G. unsupported radii

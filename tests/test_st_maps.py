@@ -8,14 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+from abi_checks import FAKE, ST_MAPS_REFUSALS, st_maps_call, st_maps_refuses
+from abi_checks import lib as _lib
 from conftest import rel_err
-
-FAKE = 0x1000          # stands for a device pointer in calls that are refused on the host: never dereferenced
-
-
-def _lib():
-    from srganst import _abi
-    return _abi.lib()
 
 
 def test_symbols_and_workspace():
@@ -31,34 +26,22 @@ def test_symbols_and_workspace():
     assert lib.sst_st_maps_workspace(1, 8, 8, None) != 0
 
 
-def _call(x=FAKE, gt=FAKE, Sx=None, Sgt=None, Fx=None, Fgt=None, d=None, tile_sums=None, shape=(2, 40, 40), sigma=0.5, rho=2.0):
-    lib = _lib()
-    rc = lib.sst_st_maps(x, gt, Sx, Sgt, Fx, Fgt, d, tile_sums, *shape, sigma, rho, 1, None)
-    return rc, lib.sst_last_error()
-
-
-@pytest.mark.parametrize("kwargs, message", [
-    (dict(x=None, Sx=FAKE), b"null pointer"),
+# the ids are positional: the order of the cases is kept
+@pytest.mark.parametrize("kwargs, message", ST_MAPS_REFUSALS[:1] + [
     (dict(Sx=FAKE, shape=(0, 40, 40)), b"bad shape"),
     (dict(Sx=FAKE, shape=(2, 0, 40)), b"bad shape"),
     (dict(Sx=FAKE, shape=(2, 40, -3)), b"bad shape"),
     (dict(Sx=FAKE, shape=(65536, 40, 40)), b"bad shape"),
-    (dict(gt=None, Sgt=FAKE), b"Sgt needs gt"),
-    (dict(gt=None, Fgt=FAKE), b"Fgt needs gt"),
-    (dict(gt=None, d=FAKE), b"d needs gt"),
-    (dict(gt=None, tile_sums=FAKE), b"tile_sums cannot be computed without gt"),
+] + ST_MAPS_REFUSALS[1:5] + [
     (dict(gt=None, Sx=FAKE, Fx=FAKE, tile_sums=FAKE), b"tile_sums cannot be computed without gt"),
-    (dict(), b"no output requested"),
-    (dict(gt=None), b"no output requested"),
-])
+] + ST_MAPS_REFUSALS[5:])
 def test_host_side_refusals(kwargs, message):
-    rc, err = _call(**kwargs)
-    assert rc == -1 and message in err, (rc, err)
+    st_maps_refuses("sst_st_maps", kwargs, message)
 
 
 def test_unbuilt_radii_are_unsupported_with_the_loss_message_form():
     """sigma 1 / rho 10 (the reference's structure_tensor defaults) -> radii (4, 40): not built, same wording as sst_st_loss_fwd."""
-    rc, err = _call(Sx=FAKE, d=FAKE, sigma=1.0, rho=10.0)
+    rc, err = st_maps_call("sst_st_maps", Sx=FAKE, d=FAKE, sigma=1.0, rho=10.0)
     assert rc == -2 and err == b"sst_st_maps: (sigma,rho)=(1,10) -> radii (4,40) not built", (rc, err)
     lib = _lib()
     rc = lib.sst_st_loss_fwd(FAKE, FAKE, FAKE, FAKE, FAKE, FAKE, 2, 40, 40, 1.0, 10.0, 1, None)

@@ -10,63 +10,26 @@ captured.  Run with -s for the measured errors."""
 import math
 import os
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 from torch.utils.data import DataLoader, Dataset
 
-from conftest import rel_err, truth_bound
+import st_checks
+from st_checks import ALL, BUILDS
+from st_checks import check_distance as _check_distance
+from st_checks import features as _features
+from st_checks import images as _images
+from st_checks import maps_hip as _hip
+from st_checks import maps_oracle as _oracle
 
 pytestmark = pytest.mark.gpu
 
-BUILDS = {(2, 8): (0.5, 2.0), (4, 10): (1.0, 2.5)}   # the two instantiated <R1, R2> pairs -> a (sigma, rho) that selects each
-ALL = ("Sx", "Sgt", "Fx", "Fgt", "d", "tile_sums", "distance")
 SHAPES = [(2, 32, 32),      # exactly one tile
           (2, 33, 31),      # partial tiles on both axes, W not a multiple of 4
           (2, 70, 45),      # 3 x 2 tiles, ragged
           (3, 8, 8),        # smaller than the 10 / 14 px halo
           (2, 5, 3)]
-
-
-def _images(seed, B, H, W, noise=0.08, scale=1.0):
-    """tests/test_st_loss_fp64_gpu.py:_images - smooth texture (bicubic-upsampled noise) for gt and gt + noise for sr, both in
-    [0, 1] x scale."""
-    gen = torch.Generator().manual_seed(seed)
-    base = torch.rand(B, 3, max(H // 6, 2), max(W // 6, 2), generator=gen)
-    gt = F.interpolate(base, size=(H, W), mode="bicubic", align_corners=False)
-    gt = (gt + 0.05 * torch.randn(gt.shape, generator=gen)).clamp(0, 1)
-    x = (gt + noise * torch.randn(gt.shape, generator=gen)).clamp(0, 1)
-    return x * scale, gt * scale
-
-
-def _features(S):
-    """(t, c2, s2) planes of S [B,3,H,W] in S's dtype: the definition in srganst/st.py."""
-    t = S[:, 0] + S[:, 1]
-    den = t + 1e-12
-    return torch.stack((t, (S[:, 0] - S[:, 1]) / den, 2 * S[:, 2] / den), dim=1)
-
-
-def _oracle(x, gt, sigma, rho, norm, dtype):
-    from oracle import st as ost
-    it = ost.st_intermediates(x.to(dtype), gt.to(dtype), sigma, rho, norm)
-    return {"Sx": it["S1"], "Sgt": it["S2"], "Fx": _features(it["S1"]), "Fgt": _features(it["S2"]), "d": it["d"], "L": it["L"],
-            "distance": it["d"].mean(dim=(1, 2))}
-
-
-def _hip(x, gt, sigma, rho, norm=True, want=ALL):
-    from srganst import st
-    out = st.st_maps(x.cuda(), None if gt is None else gt.cuda(), sigma, rho, norm, want=want)
-    torch.cuda.synchronize()
-    return {k: v.cpu() for k, v in out.items()}
-
-
-def _check_distance(name, hip, l32, l64):
-    """The loss rule, per image."""
-    for b in range(l64.numel()):
-        e, bound = abs(hip[b].item() - l64[b].item()), max(1e-3 * abs(l64[b].item()), 3 * abs(l32[b].item() - l64[b].item()))
-        print(f"[{name}] image {b}: distance {hip[b].item():.6e} |hip-l64| {e:.3e} <= {bound:.3e}")
-        assert math.isfinite(hip[b].item()) and e <= bound, (name, b, hip[b].item(), l64[b].item(), e, bound)
 
 
 # ------------------------------------------------------------------------------------------------ 1. maps against fp64
@@ -79,22 +42,7 @@ def test_maps_vs_fp64(radii, norm, k):
     sigma, rho = BUILDS[radii]
     B, H, W = SHAPES[k]
     x, gt = _images(300 + 10 * k + radii[0] + norm, B, H, W, scale=1.0 if norm else 255.0)
-    o32, o64 = _oracle(x, gt, sigma, rho, norm, torch.float32), _oracle(x, gt, sigma, rho, norm, torch.float64)
-    frac = float((o64["L"][:, 1] > 1).double().mean())
-    assert frac >= 0.1, f"vacuous case: only {frac:.1%} of the pixels have l2 > 1"
-    trace = min(float(o64["Fx"][:, 0].min()), float(o64["Fgt"][:, 0].min()))
-    assert trace >= 5e-4, f"trace {trace:.3e}: the 1e-12 guard of the features would take part"
-    got = _hip(x, gt, sigma, rho, norm)
-    name = f"1 radii={radii} normalize={norm} {B}x{H}x{W}"
-    for key in ("Sx", "Sgt", "d", "Fx", "Fgt"):
-        assert got[key].dtype == torch.float32 and got[key].shape == o64[key].shape, (key, got[key].shape)
-        assert bool(torch.isfinite(got[key]).all()), key
-        e, b = rel_err(got[key], o64[key]), truth_bound(o32[key], o64[key])
-        print(f"[{name}] {key}: rel err {e:.3e} <= {b:.3e}")
-        assert e <= b, f"{name} {key}: rel err {e:.3e} > {b:.3e}"
-    tiles = ((H + 31) // 32) * ((W + 31) // 32)
-    assert tuple(got["tile_sums"].shape) == (B, tiles) and got["distance"].dtype == torch.float64
-    _check_distance(name, got["distance"], o32["distance"].double(), o64["distance"])
+    st_checks.check_maps_vs_fp64(f"1 radii={radii} normalize={norm} {B}x{H}x{W}", x, gt, sigma, rho, norm, min_trace=5e-4)
 
 
 # ------------------------------------------------------------------------------------------------ 2. 1 x 1 image
@@ -177,16 +125,8 @@ def test_axis_convention_known_answers(radii):
 @pytest.mark.parametrize("radii", list(BUILDS))
 def test_optional_outputs_are_the_same_bits(radii):
     sigma, rho = BUILDS[radii]
-    x, gt = _images(51 + radii[0], 2, 33, 31)
-    full = _hip(x, gt, sigma, rho)
-    for key in ALL:
-        alone = _hip(x, gt, sigma, rho, want=(key,))
-        assert list(alone) == [key]
-        assert torch.equal(alone[key], full[key]), f"{key} requested alone differs from the all-outputs call"
-    x_only = _hip(x, None, sigma, rho, want=("Sx", "Fx"))
-    assert torch.equal(x_only["Sx"], full["Sx"]) and torch.equal(x_only["Fx"], full["Fx"])
-    swapped = _hip(gt, x, sigma, rho, want=("Sx", "Sgt"))                  # both images run the same tile code
-    assert torch.equal(swapped["Sx"], full["Sgt"]) and torch.equal(swapped["Sgt"], full["Sx"])
+    st_checks.check_optional_outputs_are_the_same_bits(*_images(51 + radii[0], 2, 33, 31), sigma, rho)
+
 
 
 def test_python_surface_on_the_device():
