@@ -142,6 +142,40 @@ int sst_bp_loss_fwd(const float* sr, const float* gt, const float* lr, float* lo
 int sst_bp_loss_bwd(const float* saved, float* dsr, const float* tw_y, const int* ti_y, const float* tw_x, const int* ti_x,
                     const float* scale_dev, float scale_host, int accumulate, int B, int H, int W, int scale, int Ny, int Nx,
                     void* stream);
+/* ---- gradient-magnitude and gradient-variance losses (loss.py: GradientLoss, GradientVarianceLoss; csrc/grad_loss.hip, DESIGN.md
+ * section 19).  sr, gt, dsr: NCHW fp32 [B,3,H,W].  Gv, Gh: the zero-padded 3x3 correlations (F.conv2d, padding 1) with the vertical
+ * operator - op 0 "central" [[0,-1,0],[0,0,0],[0,1,0]], op 1 "sobel" [[-1,-2,-1],[0,0,0],[1,2,1]] - and with its transpose.
+ * Gradient loss, per image and RGB plane: M(I) = sqrt(Gv(I)^2 + Gh(I)^2 + eps); loss[0] = mean over B*3*H*W of |M(sr) - M(gt)|
+ *   (crit 0) or of its square (crit 1).  Any H, W >= 1; 1 <= B <= 21845; eps finite and > 0.
+ * sst_grad_loss_workspace: partial_floats = 2 * B*3 * ceil(H/32) * ceil(W/32): one fp64 partial per workgroup, so `partials` must be
+ *   8-byte aligned.
+ * fwd: one launch, nothing is saved.  counter is one 32-bit word, 0 at the first call, and re-arms itself; the partials are summed in
+ *   index order by the last-arriving workgroup: the same bits in every run.
+ * bwd: one launch, a gather (no atomics): dsr (+)= scale_host * (scale_dev ? *scale_dev : 1) * d loss / d sr, recomputed from sr and
+ *   gt with the forward's op, crit and eps; gt is a constant; the derivative of |.| at a tie is 0.  scale_dev may be null.
+ * Gradient-variance loss, on gray = 0.2989 R + 0.587 G + 0.114 B with the Sobel operator: the two response maps are cut into
+ *   non-overlapping patch x patch blocks from the top-left corner, PH = H / patch by PW = W / patch of them (leftover rows and columns
+ *   belong to no patch); v = the unbiased variance of a block; loss[0] = mean((vv(sr) - vv(gt))^2) + mean((vh(sr) - vh(gt))^2), each
+ *   mean over B*PH*PW.  2 <= patch <= 32; H, W >= patch; 1 <= B <= 65535.
+ * sst_gv_loss_workspace: saved_floats = 4 * B * PH * PW (per patch: mean of sr's Gv, d loss / d vv, mean of sr's Gh, d loss / d vh, laid
+ *   out [B,PH,PW,4]: written by the forward, read by the backward, owned by the call); partial_floats = 2 * B * ceil(PH/n) * ceil(PW/n)
+ *   with n = 32 / patch (integer division) patches per tile side: one fp64 partial per workgroup, `partials` 8-byte aligned.
+ * fwd: one launch; saved may be null (no gradient wanted: nothing is written there); counter as above.
+ * bwd: one launch, a gather: dsr (+)= scale_host * (scale_dev ? *scale_dev : 1) * d loss / d sr from sr and `saved` of the forward of
+ *   the same sr; gt is not read.  Every pixel of dsr is written, leftover rows and columns included.  scale_dev may be null.
+ * Everything is validated on the host before any launch (null pointer, B < 1, H or W < 1 or below patch, op or crit not 0 / 1, eps not
+ * finite or <= 0, patch outside 2..32, grid limits: non-zero return, message in sst_last_error); no allocation, no sync, asynchronous
+ * on `stream`. */
+int sst_grad_loss_workspace(int B, int H, int W, int64_t* partial_floats);
+int sst_grad_loss_fwd(const float* sr, const float* gt, float* loss, float* partials, unsigned* counter, int B, int H, int W, int op,
+                      int crit, double eps, void* stream);
+int sst_grad_loss_bwd(const float* sr, const float* gt, float* dsr, const float* scale_dev, float scale_host, int accumulate, int B,
+                      int H, int W, int op, int crit, double eps, void* stream);
+int sst_gv_loss_workspace(int B, int H, int W, int patch, int64_t* saved_floats, int64_t* partial_floats);
+int sst_gv_loss_fwd(const float* sr, const float* gt, float* loss, float* saved, float* partials, unsigned* counter, int B, int H,
+                    int W, int patch, void* stream);
+int sst_gv_loss_bwd(const float* sr, const float* saved, float* dsr, const float* scale_dev, float scale_host, int accumulate, int B,
+                    int H, int W, int patch, void* stream);
 
 /* ---- convolution (fp32 MFMA implicit GEMM, NHWC) --------------------------------------------------
  * Replaces the cuDNN/oneDNN kernels behind nn.Conv2d fwd/bwd of model.py:32-56,101,113,127,159,173,176.

@@ -42,6 +42,12 @@ SIGNATURES = {
     "sst_bp_loss_workspace": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "sst_bp_loss_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_bp_loss_bwd": (c_int, [P, P, P, P, P, P, P, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "sst_grad_loss_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
+    "sst_grad_loss_fwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, P]),
+    "sst_grad_loss_bwd": (c_int, [P, P, P, P, c_float, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, P]),
+    "sst_gv_loss_workspace": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "sst_gv_loss_fwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "sst_gv_loss_bwd": (c_int, [P, P, P, P, c_float, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_conv_packed_floats": (c_int64, [c_int, c_int, c_int]),
     "sst_conv_pack": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "sst_conv_pack_multi": (c_int, [P, c_int, c_int, P]),

@@ -7,11 +7,15 @@ SSIMLoss             1 - mean SSIM, the criterion for the second number validate
 FocalFrequencyLoss   the focal frequency loss (Jiang et al., ICCV 2021): a 2-D DFT and its adjoint; kernels csrc/freq_loss.hip
 BackProjectionLoss   the back-projection (LR-consistency) loss of Best-Buddy GANs (Li et al., AAAI 2022): |down(sr) - lr|, the fused
                         antialiased bicubic downscale-and-compare and its adjoint; kernels csrc/bp_loss.hip
+GradientLoss         the gradient-magnitude loss of structure-preserving SR (Ma et al., CVPR 2020): |M(sr) - M(gt)| per RGB plane,
+                        central-difference or Sobel; kernels csrc/grad_loss.hip
+GradientVarianceLoss the gradient-variance loss (Abrahamyan et al., 2022): the MSE between the per-patch variances of the
+                        gray Sobel responses; kernels csrc/grad_loss.hip
 ContentLossVGG       <- reference loss.py:11-70, in vgg_loss.py (re-exported here)
 BestBuddyLoss / GramLoss / PatchwiseStructureTensorLoss <- reference loss.py:78-228, 292-375, kernels csrc/bb_loss.hip
 ContentLossDiscriminator <- reference loss.py:231-289, in disc_loss.py (re-exported here)
 
-The six pixel-space criteria speak one term protocol (_Term): stand-alone they run under one autograd node
+The eight pixel-space criteria speak one term protocol (_Term): stand-alone they run under one autograd node
 (_TermFn), summed under another (_CriterionSumFn, with the fused pixel + structure-tensor pair _StPixelPair as one more term), and
 each of their library entries is launched from one place.
 """
@@ -386,6 +390,107 @@ class BackProjectionLoss(_Term):
     def __repr__(self):
         extra = ", target='lr'" if self.target == "lr" else ""
         return f"BackProjectionLoss(scale={self.scale}, criterion={self.criterion!r}, round_target={self.round_target}{extra})"
+
+
+# ------------------------------------------------------------------------------------------------
+GRAD_OPERATORS = ("central", "sobel")     # sst_grad_loss_*: op 0, 1
+GRAD_CRITERIA = ("l1", "mse")             # crit 0, 1
+_NOTHING_SAVED = ()                        # what a forward that ran for a gradient keeps when its backward needs only sr and gt
+
+
+class GradientLoss(_Term):
+    """The pixel-wise gradient loss of structure-preserving SR (Ma et al., CVPR 2020): mean |M(sr) - M(gt)| ("l1") or its square
+    ("mse") over batch, RGB planes and pixels, M(I) = sqrt(Gv(I)^2 + Gh(I)^2 + eps) with Gv, Gh the zero-padded 3x3 correlations of a
+    plane with the vertical operator - "central" [[0,-1,0],[0,0,0],[0,1,0]] or "sobel" [[-1,-2,-1],[0,0,0],[1,2,1]] - and with its
+    transpose.  The derivative of |.| at a tie is 0.  fp32 [B,3,H,W] pairs of any size on one ROCm device; the gradient is taken with
+    respect to sr only.  Kernels: csrc/grad_loss.hip."""
+
+    def __init__(self, operator: str = "central", criterion: str = "l1", eps: float = 1e-6):
+        super().__init__()
+        if operator not in GRAD_OPERATORS:
+            raise ValueError(f"GradientLoss: operator must be one of {GRAD_OPERATORS}, got {operator!r}")
+        if criterion not in GRAD_CRITERIA:
+            raise ValueError(f"GradientLoss: criterion must be one of {GRAD_CRITERIA}, got {criterion!r}")
+        if isinstance(eps, bool) or not (isinstance(eps, (int, float)) and 0.0 < float(eps) < float("inf")):
+            raise ValueError(f"GradientLoss: eps must be a finite number > 0, got {eps!r}")
+        self.operator, self.criterion, self.eps = operator, criterion, float(eps)
+
+    def _modes(self):
+        return GRAD_OPERATORS.index(self.operator), GRAD_CRITERIA.index(self.criterion), self.eps
+
+    def _check(self, x, gt):
+        _check_pair("GradientLoss", x, gt, on_device=True)
+        B, _, H, W = x.shape
+        if B < 1 or H < 1 or W < 1:
+            raise _abi.HipPathError(f"GradientLoss: empty input {tuple(x.shape)}")
+
+    def _fwd(self, x, gt, want_grad, route):
+        """Nothing is saved: the backward recomputes from sr and gt.  A forward that ran for a gradient says so with a marker."""
+        B, _, H, W = x.shape
+        n_part, = _workspace("grad_loss", B, H, W, n=1)
+        partials, counter = ops.reduction_ws(self._ws, (x.device, B, H, W), n_part)
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(partials), _abi.ptr(counter), B, H, W, *self._modes())
+        # algorithmic bytes: the forward reads sr + gt, the backward writes d(sr)
+        ops._launch_hbm(_abi.lib().sst_grad_loss_fwd, args, "sst_grad_loss_fwd", "grad_loss_fwd_kernel", 2.0 * x.numel() * 4,
+                        (x, gt, loss, None, self._ws))
+        return loss, _NOTHING_SAVED if want_grad else None
+
+    def _bwd(self, x, gt, saved, dsr, g, scale_host, accumulate):
+        self._kept(saved)
+        B, _, H, W = x.shape
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(dsr), _abi.ptr(g), float(scale_host), int(accumulate), B, H, W, *self._modes())
+        ops._launch_hbm(_abi.lib().sst_grad_loss_bwd, args, "sst_grad_loss_bwd", "grad_loss_bwd_kernel", 1.0 * x.numel() * 4,
+                        (x, gt, dsr, g))
+
+    def __repr__(self):
+        return f"GradientLoss(operator={self.operator!r}, criterion={self.criterion!r}, eps={self.eps})"
+
+
+GV_MAX_PATCH = 32         # a workgroup of csrc/grad_loss.hip owns whole patches of a 32 x 32 tile
+
+
+class GradientVarianceLoss(_Term):
+    """The gradient-variance loss (Abrahamyan et al., 2022): the zero-padded Sobel responses Gv, Gh of gray = 0.2989 R + 0.587 G +
+    0.114 B are cut into non-overlapping patch_size x patch_size patches from the top-left corner (leftover rows and columns belong to
+    no patch, but still receive gradient through the taps of patch pixels next to them); with v the unbiased variance of a patch,
+    loss = mean((vv(sr) - vv(gt))^2) + mean((vh(sr) - vh(gt))^2) over batch and patches.  fp32 [B,3,H,W] pairs with H, W >= patch_size
+    on one ROCm device; the gradient is taken with respect to sr only.  Kernels: csrc/grad_loss.hip."""
+
+    def __init__(self, patch_size: int = 8):
+        super().__init__()
+        if isinstance(patch_size, bool) or not isinstance(patch_size, int) or not 2 <= patch_size <= GV_MAX_PATCH:
+            raise ValueError(f"GradientVarianceLoss: patch_size must be an int from 2 to {GV_MAX_PATCH}, got {patch_size!r}")
+        self.patch_size = patch_size
+
+    def _check(self, x, gt):
+        _check_pair("GradientVarianceLoss", x, gt, on_device=True)
+        B, _, H, W = x.shape
+        if B < 1 or H < self.patch_size or W < self.patch_size:
+            raise _abi.HipPathError(f"GradientVarianceLoss: images of {W}x{H} are below the patch size {self.patch_size}")
+
+    def _fwd(self, x, gt, want_grad, route):
+        """want_grad False (no_grad, or sr does not require grad): the per-patch values are neither allocated nor written."""
+        B, _, H, W = x.shape
+        n_saved, n_part = _workspace("gv_loss", B, H, W, self.patch_size, n=2)
+        partials, counter = ops.reduction_ws(self._ws, (x.device, B, H, W, self.patch_size), n_part)
+        saved = torch.empty(n_saved, device=x.device, dtype=torch.float32) if want_grad else None
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(loss), _abi.ptr(saved), _abi.ptr(partials), _abi.ptr(counter), B, H, W, self.patch_size)
+        # algorithmic bytes: the forward reads sr + gt, the backward writes d(sr)
+        ops._launch_hbm(_abi.lib().sst_gv_loss_fwd, args, "sst_gv_loss_fwd", "gv_loss_fwd_kernel", 2.0 * x.numel() * 4,
+                        (x, gt, loss, saved, self._ws))
+        return loss, saved
+
+    def _bwd(self, x, gt, saved, dsr, g, scale_host, accumulate):
+        saved = self._kept(saved)
+        B, _, H, W = x.shape
+        args = (_abi.ptr(x), _abi.ptr(saved), _abi.ptr(dsr), _abi.ptr(g), float(scale_host), int(accumulate), B, H, W, self.patch_size)
+        ops._launch_hbm(_abi.lib().sst_gv_loss_bwd, args, "sst_gv_loss_bwd", "gv_loss_bwd_kernel", 1.0 * x.numel() * 4,
+                        (x, saved, dsr, g))
+
+    def __repr__(self):
+        return f"GradientVarianceLoss(patch_size={self.patch_size})"
 
 
 # ------------------------------------------------------------------------------------------------

@@ -9,6 +9,10 @@ rate of the HIP path.
     freq   FocalFrequencyLoss (csrc/freq_loss.hip) against tests/freq_refs.py (torch.fft.fft2), which is timed eagerly first and
            then, if the vendor FFT can be captured, from a hipGraph as well (a failed capture is reported, not fatal; it is tried
            last); the FMA rate of the four transform passes (H Wh (2 W + 4 H) FMAs per plane and direction, Wh = W/2 + 1)
+    grad   GradientLoss (csrc/grad_loss.hip), both operators and both criteria, against tests/grad_refs.py (two grouped conv2d per
+           image, sqrt, autograd's backward); GB/s of the algorithmic bytes (read sr and gt, write d(sr))
+    gv     GradientVarianceLoss (csrc/grad_loss.hip) at patch_size 8 against tests/grad_refs.py (gray, two conv2d, unfold, var);
+           GB/s of the same algorithmic bytes
     bp     BackProjectionLoss x4 (csrc/bp_loss.hip), both criteria, against the tap-gather form of bicubic.Bicubic.forward without
            its rounding and autograd's backward; GB/s of the algorithmic bytes (forward: read sr and gt; backward: write d(sr))
 
@@ -95,8 +99,21 @@ def _ssim_variants(x, gt, size):
     return [({"channel": c}, SSIMLoss(c), lambda x, gt, c=c: ssim_refs.ssim_loss(x, gt, c)) for c in ("y", "rgb")]
 
 
-def _ssim_rate(hip, x, size):
+def _algorithmic_rate(hip, x, size):
     hip["algorithmic_GBps"] = round(3.0 * x.numel() * 4 / (hip["fwd_bwd_us"] * 1e-6) / 1e9, 1)
+
+
+def _grad_variants(x, gt, size):
+    import grad_refs
+    from srganst.loss import GradientLoss
+    return [({"operator": o, "criterion": c}, GradientLoss(o, c), lambda x, gt, o=o, c=c: grad_refs.gradient_loss(x, gt, o, c))
+            for o in ("central", "sobel") for c in ("l1", "mse")]
+
+
+def _gv_variants(x, gt, size):
+    import grad_refs
+    from srganst.loss import GradientVarianceLoss
+    return [({"patch_size": 8}, GradientVarianceLoss(8), lambda x, gt: grad_refs.gv_loss(x, gt, 8))]
 
 
 def _freq_variants(x, gt, size):
@@ -145,11 +162,18 @@ def _engine(key, name, cls, weight):
 
 NOTE = "fwd_us is measured under no_grad (the HIP forward then writes no %s); bwd_us = fwd_bwd_us - fwd_us and includes autograd's own launches"
 CRITERIA = {
-    "ssim": dict(variants=_ssim_variants, rate=_ssim_rate, torch=("torch", replay_us), clamp=True, engine=_engine("pixel_ssim", "SSIM", "SSIMLoss", 0.1),
+    "ssim": dict(variants=_ssim_variants, rate=_algorithmic_rate, torch=("torch", replay_us), clamp=True, engine=_engine("pixel_ssim", "SSIM", "SSIMLoss", 0.1),
                  note=NOTE % "maps" + "; algorithmic bytes = read sr + gt, write d(sr)"),
     "freq": dict(variants=_freq_variants, rate=_freq_rate, torch=("torch_eager", eager_us), clamp=False, capture_last=True,
                  engine=_engine("pixel_frequency", "Frequency", "FocalFrequencyLoss", 1.0),
                  note=NOTE % "spectrum" + "; GFMAps counts the four direct-DFT passes only"),
+    "grad": dict(variants=_grad_variants, rate=_algorithmic_rate, torch=("torch", replay_us), clamp=True,
+                 engine=_engine("pixel_gradient", "Gradient", "GradientLoss", 0.1),
+                 note="fwd_us is measured under no_grad (the HIP forward saves nothing either way); bwd_us = fwd_bwd_us - fwd_us and "
+                 "includes autograd's own launches; algorithmic bytes = read sr + gt, write d(sr)"),
+    "gv": dict(variants=_gv_variants, rate=_algorithmic_rate, torch=("torch", replay_us), clamp=True,
+               engine=_engine("pixel_gv", "GV", "GradientVarianceLoss", 0.1),
+               note=NOTE % "per-patch values" + "; algorithmic bytes = read sr + gt, write d(sr)"),
     "bp": dict(variants=_bp_variants, rate=_bp_rate, torch=("torch", replay_us), clamp=True, on_grid=True, head={"scale": BP_SCALE},
                engine=_engine("pixel_bp", "BackProjection", "BackProjectionLoss", 0.1),
                note=NOTE % "saved map" + " and, for the HIP path, the saved map's store; algorithmic bytes: forward = read sr + gt, "
