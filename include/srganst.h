@@ -176,6 +176,26 @@ int sst_gv_loss_fwd(const float* sr, const float* gt, float* loss, float* saved,
                     int W, int patch, void* stream);
 int sst_gv_loss_bwd(const float* sr, const float* saved, float* dsr, const float* scale_dev, float scale_host, int accumulate, int B,
                     int H, int W, int patch, void* stream);
+/* ---- artifact-map (LDL) loss (loss.py: ArtifactLoss; csrc/artifact_loss.hip).  sr, gt, ref, dsr: NCHW fp32
+ * [B,3,H,W]; ref (the averaged generator's output) may be null.  ksize = k odd, 3..11, p = k / 2; H, W >= p + 1; 1 <= B <= 65535.
+ *   r = |gt - sr| summed over R, G, B (r_e the same of ref); s_b = (unbiased variance of r over image b)^(1/5); v = the unbiased
+ *   variance of the k x k window of r, reflect-padded by p; w = s_b v, and 0 where r < r_e; loss[0] = mean over B*3*H*W of w |sr - gt|.
+ *   w is a constant of the gradient: d loss / d sr = w sign(sr - gt) / (3 B H W), sign(0) = 0.
+ * sst_artifact_loss_workspace: with T = B * ceil(H/32) * ceil(W/32) workgroups, map_floats = B*H*W (w, one float per pixel: written by
+ *   the forward, read by the backward, owned by the call), stat_floats = 2 * (2 T + B) (fp64: two sums per workgroup, then the B global
+ *   weights), partial_floats = 2 * T (one fp64 partial per workgroup); `stats` and `partials` must be 8-byte aligned.
+ * fwd: two launches (the per-image variance and s_b; the map and the loss).  wmap may be null (no gradient wanted: nothing is written
+ *   there).  stat_counter and counter are one 32-bit word each, 0 at the first call, and re-arm themselves; every sum is taken in a
+ *   fixed order by a last-arriving workgroup: no float atomics, the same bits in every run.
+ * bwd: one launch: dsr (+)= scale_host * (scale_dev ? *scale_dev : 1) * w sign(sr - gt) / (3 B H W) from sr, gt and `wmap` of the
+ *   forward of the same sr; every element of dsr is written.  scale_dev may be null.
+ * Everything is validated on the host before any launch (null pointer, B < 1, ksize even or outside 3..11, H or W < p + 1, alignment,
+ * grid limits: non-zero return, message in sst_last_error); no allocation, no sync, asynchronous on `stream`. */
+int sst_artifact_loss_workspace(int B, int H, int W, int ksize, int64_t* map_floats, int64_t* stat_floats, int64_t* partial_floats);
+int sst_artifact_loss_fwd(const float* sr, const float* gt, const float* ref, float* loss, float* wmap, float* stats,
+                          unsigned* stat_counter, float* partials, unsigned* counter, int B, int H, int W, int ksize, void* stream);
+int sst_artifact_loss_bwd(const float* sr, const float* gt, const float* wmap, float* dsr, const float* scale_dev, float scale_host,
+                          int accumulate, int B, int H, int W, int ksize, void* stream);
 
 /* ---- convolution (fp32 MFMA implicit GEMM, NHWC) --------------------------------------------------
  * Replaces the cuDNN/oneDNN kernels behind nn.Conv2d fwd/bwd of model.py:32-56,101,113,127,159,173,176.

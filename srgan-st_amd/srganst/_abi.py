@@ -48,6 +48,9 @@ SIGNATURES = {
     "sst_gv_loss_workspace": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "sst_gv_loss_fwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
     "sst_gv_loss_bwd": (c_int, [P, P, P, P, c_float, c_int, c_int, c_int, c_int, c_int, P]),
+    "sst_artifact_loss_workspace": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
+    "sst_artifact_loss_fwd": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "sst_artifact_loss_bwd": (c_int, [P, P, P, P, P, c_float, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_conv_packed_floats": (c_int64, [c_int, c_int, c_int]),
     "sst_conv_pack": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     "sst_conv_pack_multi": (c_int, [P, c_int, c_int, P]),

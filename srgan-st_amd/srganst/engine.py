@@ -98,10 +98,39 @@ def _one(like):
     return o
 
 
-def _criterion_total(sr, gt, criterions, weights, adversarial=None, adv_logits=None, adv_label=None):
+def _reference_buffers(criterions, generator, shadow):
+    """What the step needs for criteria that take the averaged generator's output (`wants_reference`, loss.ArtifactLoss): ->
+    (the shadow's buffers, the generator's buffers of the same names), or None when no criterion wants one.  Without an average
+    (SOLVER.G_EMA_DECAY = 0) such a criterion is a configuration error."""
+    wanting = [name for name, c in criterions.items() if getattr(c, "wants_reference", False)]
+    if not wanting:
+        return None
+    if shadow is None:
+        raise ValueError(f"criterion {wanting[0]!r} needs the averaged generator as its reference: set SOLVER.G_EMA_DECAY > 0 "
+                         "(or construct the criterion with refine=False)")
+    src = dict(generator.named_buffers())
+    names = [n for n, _ in shadow.named_buffers()]
+    return [b for _, b in shadow.named_buffers()], [src[n] for n in names]
+
+
+def _reference_forward(eng):
+    """ref = g_ema(lr) for the criteria that want it, called in front of G's forward of the same step: G's BatchNorm buffers are
+    copied into the shadow first (one multi-tensor copy per dtype, not one per buffer), so ref is the eval-mode forward with the
+    averaged weights and G's running statistics as the previous step left them.  None when no criterion wants a reference: then
+    nothing is launched."""
+    if eng._ref_bufs is None:
+        return None
+    with torch.no_grad():
+        torch._foreach_copy_(*eng._ref_bufs)
+        eng.sr_ref = eng.g_ema(eng.lr)
+    return eng.sr_ref
+
+
+def _criterion_total(sr, gt, criterions, weights, adversarial=None, adv_logits=None, adv_label=None, ref=None):
     """sum_name weight * criterion(sr, gt) as in the reference loops (train.py:129-140, warmup.py:79-86); the values come
     back per name (already weighted, detached).  HIP-path pixel / structure-tensor terms share one autograd node
-    (loss.criterion_sum); "Adversarial" (through D) and any other criterion go through autograd term by term."""
+    (loss.criterion_sum); "Adversarial" (through D) and any other criterion go through autograd term by term.  ref: the averaged
+    generator's output, handed as a third operand to the criteria that declare `wants_reference`."""
     from .loss import criterion_sum, fusable
     vals = OrderedDict((name, None) for name in criterions)
     fused = [n for n, c in criterions.items() if n != "Adversarial" and fusable(c)]
@@ -119,7 +148,11 @@ def _criterion_total(sr, gt, criterions, weights, adversarial=None, adv_logits=N
             # instead of mul + add; backward: the weight is folded into the BCE gradient's scale)
             total, vals[name] = adversarial_term(total, adv_logits(), crit, adv_label, weights[name])
             continue
-        l = (adversarial(crit) if (name == "Adversarial" and adversarial is not None) else crit(sr, gt)) * weights[name]
+        if name == "Adversarial" and adversarial is not None:
+            l = adversarial(crit)
+        else:
+            l = crit(sr, gt, ref) if getattr(crit, "wants_reference", False) else crit(sr, gt)
+        l = l * weights[name]
         vals[name] = l.detach()
         total = l if total is None else total + l
     return total, vals
@@ -243,6 +276,9 @@ class WarmupEngine:
         # SOLVER.G_EMA_DECAY > 0: g_ema is the averaged generator (eval mode), its weights written by the optimizer's kernel
         ema_decay, ema_warmup = _ema_knobs(config)
         self.g_ema, ema_buf = make_shadow(config, self.G) if ema_decay > 0 else (None, None)
+        # a criterion that wants a reference reads the shadow's forward of the step's LR batch (_reference_forward)
+        self._ref_bufs = _reference_buffers(self.criterions, self.G, self.g_ema)
+        self.sr_ref = None
         g_clip, guard = _clip_knobs(config, "G")
         self.opt = make_adam(self.G, config.SOLVER.G_BASE_LR, (config.SOLVER.G_BETA1, config.SOLVER.G_BETA2),
                              config.SOLVER.G_EPS, config.SOLVER.G_WEIGHT_DECAY,
@@ -296,8 +332,9 @@ class WarmupEngine:
     # -- pieces
     def _fwd_bwd(self):
         self.opt.zero_grad(set_to_none=True)
+        ref = _reference_forward(self)
         sr = self.G(self.lr)
-        total, vals = _criterion_total(sr, self.gt, self.criterions, self.weights)
+        total, vals = _criterion_total(sr, self.gt, self.criterions, self.weights, ref=ref)
         total.backward(_one(total))
         self.sr = sr.detach()
         self.loss_values = vals
@@ -324,8 +361,8 @@ class WarmupEngine:
         """Drop the captured graphs and static buffers (also breaks the engine <-> bound-method reference cycle, so the
         device objects are released right here and not by a later cyclic collection)."""
         self._fb = self._op = None
-        self.gt = self.lr = self.sr = None
-        self.g_ema = None
+        self.gt = self.lr = self.sr = self.sr_ref = None
+        self.g_ema = self._ref_bufs = None
 
     def step(self, gt, lr):
         """One optimisation step on the batch (gt [B,3,H,W], lr [B,3,H/4,W/4], device tensors)."""
@@ -354,6 +391,9 @@ class TrainEngine:
         # update rides in whichever graph holds g_opt.step.  D has no average.
         ema_decay, ema_warmup = _ema_knobs(config)
         self.g_ema, ema_buf = make_shadow(config, self.G) if ema_decay > 0 else (None, None)
+        # a criterion that wants a reference reads the shadow's forward of the step's LR batch (_reference_forward)
+        self._ref_bufs = _reference_buffers(config.MODEL.G_LOSS.CRITERIONS, self.G, self.g_ema)
+        self.sr_ref = None
         (g_clip, guard), (d_clip, _) = _clip_knobs(config, "G"), _clip_knobs(config, "D")
         self.g_opt = make_adam(self.G, s.G_BASE_LR, (s.G_BETA1, s.G_BETA2), s.G_EPS, s.G_WEIGHT_DECAY, cap,
                                ema_decay=ema_decay, ema_warmup=ema_warmup, ema_buffer=ema_buf, max_grad_norm=g_clip,
@@ -467,13 +507,14 @@ class TrainEngine:
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     disc_graph.packs(self.D, disc_graph.param_dict(self.D)[1], True, counter_add=counter_add)
+            ref = _reference_forward(self)
             sr = self.G(self.lr)
             if early_pack:
                 main.wait_stream(side)               # D(sr) below reads the packed weights
             stamp(1)
             total, vals = _criterion_total(sr, self.gt, crits, cfg.MODEL.G_LOSS.CRITERION_WEIGHTS,
                                            adversarial=lambda crit: crit(self.D(sr), self.real),
-                                           adv_logits=lambda: self.D(sr), adv_label=self.real)
+                                           adv_logits=lambda: self.D(sr), adv_label=self.real, ref=ref)
         self.sr = sr.detach()
         self.loss_values = vals
         stamp(2)
@@ -712,8 +753,8 @@ class TrainEngine:
         self._d_state = self._d_buckets = None
         # D is handed back: no owner, so it packs on every call again (a later optimizer step on it would not clear packs_fresh)
         self._ds.owner, self._ds.packs_fresh, self._ds.last_pass = None, False, None
-        self.gt = self.lr = self.sr = None
-        self.g_ema = None
+        self.gt = self.lr = self.sr = self.sr_ref = None
+        self.g_ema = self._ref_bufs = None
 
     def _step_overlapped(self):
         """Data-parallel iteration: collectives hidden behind compute AND the discriminator half beside the generator's backward

@@ -11,11 +11,14 @@ GradientLoss         the gradient-magnitude loss of structure-preserving SR (Ma 
                         central-difference or Sobel; kernels csrc/grad_loss.hip
 GradientVarianceLoss the gradient-variance loss (Abrahamyan et al., 2022): the MSE between the per-patch variances of the
                         gray Sobel responses; kernels csrc/grad_loss.hip
-ContentLossVGG       <- reference loss.py:11-70, in vgg_loss.py (re-exported here)
+ArtifactLoss         the artifact-map (locally discriminative) loss of Liang et al. (CVPR 2022): |sr - gt| under a per-pixel weight map
+                        from the local variance of the residual, switched off where sr beats the averaged generator's output (a
+                        third operand, handed in by the engines); kernels csrc/artifact_loss.hip
+ContentLossVGG      <- reference loss.py:11-70, in vgg_loss.py (re-exported here)
 BestBuddyLoss / GramLoss / PatchwiseStructureTensorLoss <- reference loss.py:78-228, 292-375, kernels csrc/bb_loss.hip
 ContentLossDiscriminator <- reference loss.py:231-289, in disc_loss.py (re-exported here)
 
-The eight pixel-space criteria speak one term protocol (_Term): stand-alone they run under one autograd node
+The nine pixel-space criteria speak one term protocol (_Term): stand-alone they run under one autograd node
 (_TermFn), summed under another (_CriterionSumFn, with the fused pixel + structure-tensor pair _StPixelPair as one more term), and
 each of their library entries is launched from one place.
 """
@@ -64,6 +67,7 @@ class _Term(nn.Module):
     _bwd(sr, gt, saved, dsr, g, scale_host, accumulate)   dsr (+)= scale_host * g[0] * d raw / d sr; dsr is the caller's buffer,
                                   g a device scalar"""
     _constant = "gt"          # what the second operand is called where a gradient is asked for it
+    wants_reference = False   # True: the engines hand the averaged generator's output in as a third operand (ArtifactLoss)
 
     def __init__(self):
         super().__init__()
@@ -491,6 +495,101 @@ class GradientVarianceLoss(_Term):
 
     def __repr__(self):
         return f"GradientVarianceLoss(patch_size={self.patch_size})"
+
+
+# ------------------------------------------------------------------------------------------------
+ARTIFACT_KSIZES = (3, 5, 7, 9, 11)        # the windows csrc/artifact_loss.hip is built for
+
+
+class _RefTermFn(torch.autograd.Function):
+    """One _Term that takes a reference image as a third operand (None: none), stand-alone."""
+
+    @staticmethod
+    def forward(ctx, x, gt, ref, term, want_grad):
+        route = term._route()
+        term._check(x, gt, ref)
+        x, gt, ref = x.contiguous(), gt.contiguous(), None if ref is None else ref.contiguous()
+        loss, ctx.kept = term._fwd(x, gt, want_grad, route, ref)
+        ctx.term = term
+        ctx.save_for_backward(x, gt)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, gt = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        ctx.term._bwd(x, gt, ctx.kept, dx, grad_out.contiguous().to(torch.float32), 1.0, False)
+        return dx, None, None, None, None
+
+
+class ArtifactLoss(_Term):
+    """The artifact-map (locally discriminative, "LDL") loss of Liang et al., "Details or Artifacts" (CVPR 2022).  With
+    r = sum over R, G, B of |gt - sr| and p = ksize // 2: s_b = (unbiased variance of r over image b) ** (1/5), v = the unbiased variance
+    of the ksize x ksize window of r around a pixel (r reflect-padded by p), w = s_b * v; loss = mean over B*3*H*W of w * |sr - gt|.
+    refine=True: the call takes a third operand ref - the averaged generator's output for the same LR batch (the engines hand it in:
+    SOLVER.G_EMA_DECAY > 0) - and w = 0 wherever r < r_e = sum |gt - ref| strictly, i.e. where sr is already closer to gt than ref is;
+    ref equal to sr masks nothing.  refine=False ignores a third operand.  The map is a weighting, as the paper describes it: a
+    constant of the gradient, d loss / d sr = w * sign(sr - gt) / (3 B H W) with sign(0) = 0; a variant that differentiates through
+    the map is out of scope.  fp32 [B,3,H,W] operands with H, W >= p + 1 on one ROCm device, ksize odd from 3 to 11; the gradient is
+    taken with respect to sr only.  Kernels: csrc/artifact_loss.hip."""
+    _constant = "gt, like ref,"
+
+    def __init__(self, ksize: int = 7, refine: bool = True):
+        super().__init__()
+        if isinstance(ksize, bool) or not isinstance(ksize, int) or ksize not in ARTIFACT_KSIZES:
+            raise ValueError(f"ArtifactLoss: ksize must be an odd int from {ARTIFACT_KSIZES[0]} to {ARTIFACT_KSIZES[-1]}, got {ksize!r}")
+        self.ksize, self.refine = ksize, bool(refine)
+
+    @property
+    def wants_reference(self):
+        return self.refine
+
+    def forward(self, x, gt, ref=None):
+        want_grad = torch.is_grad_enabled() and isinstance(x, torch.Tensor) and x.requires_grad
+        return _RefTermFn.apply(x, gt, ref if self.refine else None, self, want_grad)
+
+    def _check(self, x, gt, ref=None):
+        _check_pair("ArtifactLoss", x, gt, on_device=True)
+        if self.refine:
+            if ref is None:
+                raise _abi.HipPathError("ArtifactLoss: refine=True takes the averaged generator's output as a third operand (the engines "
+                                        "hand it in when SOLVER.G_EMA_DECAY > 0); without one, construct it with refine=False")
+            if not isinstance(ref, torch.Tensor) or not ref.is_cuda:
+                raise _abi.HipPathError("ArtifactLoss: ref must be a tensor on a ROCm device (no CPU fallback)")
+            if ref.dtype != torch.float32 or ref.shape != x.shape or ref.device != x.device:
+                raise _abi.HipPathError(f"ArtifactLoss: ref must be fp32, of sr's shape and on sr's device, got {ref.dtype} "
+                                        f"{tuple(ref.shape)} for sr {tuple(x.shape)}")
+        B, _, H, W = x.shape
+        if B < 1 or H < self.ksize // 2 + 1 or W < self.ksize // 2 + 1:
+            raise _abi.HipPathError(f"ArtifactLoss: images of {W}x{H} are below the {self.ksize // 2 + 1}-px minimum of the reflected "
+                                    f"{self.ksize}x{self.ksize} window")
+
+    def _fwd(self, x, gt, want_grad, route, ref=None):
+        """want_grad False (no_grad, or sr does not require grad): the w map is neither allocated nor written.  Two reduction
+        workspaces: "stat_" for the per-image variance (its partials end in the B global weights), the plain one for the loss."""
+        B, _, H, W = x.shape
+        n_map, n_stat, n_part = _workspace("artifact_loss", B, H, W, self.ksize, n=3)
+        key = (x.device, B, H, W, self.ksize)
+        partials, counter = ops.reduction_ws(self._ws, key, n_part)
+        stats, stat_counter = ops.reduction_ws(self._ws, key, n_stat, "stat_")
+        wmap = torch.empty(n_map, device=x.device, dtype=torch.float32) if want_grad else None
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(ref), _abi.ptr(loss), _abi.ptr(wmap), _abi.ptr(stats), _abi.ptr(stat_counter),
+                _abi.ptr(partials), _abi.ptr(counter), B, H, W, self.ksize)
+        # algorithmic bytes: the forward reads sr + gt (+ ref), the backward writes d(sr)
+        ops._launch_hbm(_abi.lib().sst_artifact_loss_fwd, args, "sst_artifact_loss_fwd", "artifact_loss_fwd_kernel",
+                        (2.0 if ref is None else 3.0) * x.numel() * 4, (x, gt, loss, wmap, self._ws, ref))
+        return loss, (wmap,) if want_grad else None
+
+    def _bwd(self, x, gt, saved, dsr, g, scale_host, accumulate):
+        wmap, = self._kept(saved)
+        B, _, H, W = x.shape
+        args = (_abi.ptr(x), _abi.ptr(gt), _abi.ptr(wmap), _abi.ptr(dsr), _abi.ptr(g), float(scale_host), int(accumulate), B, H, W, self.ksize)
+        ops._launch_hbm(_abi.lib().sst_artifact_loss_bwd, args, "sst_artifact_loss_bwd", "artifact_loss_bwd_kernel", 1.0 * x.numel() * 4,
+                        (x, gt, wmap, dsr, g))
+
+    def __repr__(self):
+        return f"ArtifactLoss(ksize={self.ksize}, refine={self.refine})"
 
 
 # ------------------------------------------------------------------------------------------------

@@ -13,11 +13,15 @@ rate of the HIP path.
            image, sqrt, autograd's backward); GB/s of the algorithmic bytes (read sr and gt, write d(sr))
     gv     GradientVarianceLoss (csrc/grad_loss.hip) at patch_size 8 against tests/grad_refs.py (gray, two conv2d, unfold, var);
            GB/s of the same algorithmic bytes
+    artifact  ArtifactLoss (csrc/artifact_loss.hip) at ksize 7, without and with the reference image, against tests/artifact_refs.py
+           (pad, unfold, var); GB/s of the algorithmic bytes (read sr and gt - and ref -, write d(sr))
     bp     BackProjectionLoss x4 (csrc/bp_loss.hip), both criteria, against the tap-gather form of bicubic.Bicubic.forward without
            its rounding and autograd's backward; GB/s of the algorithmic bytes (forward: read sr and gt; backward: write d(sr))
 
 With --engine also the step time of a reduced WarmupEngine (two residual blocks, B = 16, 96 px, hipGraph) with Pixel only and with
-Pixel + the criterion at its usual weight.
+Pixel + the criterion at its usual weight.  For `artifact` the steps are: Pixel alone (no average: the launches of a step before the
+criterion existed), Pixel with the averaged generator on, Pixel + the unrefined term (the criterion's own launches), and Pixel + the
+refined term (which adds the buffer copy and one eval-mode generator forward for the reference).
 
 Prints one JSON line.  Under its own time limit:
 
@@ -54,14 +58,15 @@ def eager_us(fn, reps):
     return e0.elapsed_time(e1) * 1e3 / reps
 
 
-def engine_step_us(extra, steps):
-    """extra: None or (name, criterion, weight) beside Pixel."""
+def engine_step_us(extra, steps, ema_decay=0.0):
+    """extra: None or (name, criterion, weight) beside Pixel; ema_decay: SOLVER.G_EMA_DECAY."""
     from srganst.config import Config
     from srganst.engine import WarmupEngine
     from srganst.loss import MSELoss
     from srganst.model import Generator
     cfg = Config()
     cfg.MODEL.G_N_RCB = 2
+    cfg.SOLVER.G_EMA_DECAY = ema_decay
     torch.manual_seed(0)
     G = Generator(cfg).cuda().train()
     crits, weights = {"Pixel": MSELoss()}, {"Pixel": 1.0}
@@ -114,6 +119,27 @@ def _gv_variants(x, gt, size):
     import grad_refs
     from srganst.loss import GradientVarianceLoss
     return [({"patch_size": 8}, GradientVarianceLoss(8), lambda x, gt: grad_refs.gv_loss(x, gt, 8))]
+
+
+def _artifact_variants(x, gt, size):
+    import artifact_refs
+    from srganst.loss import ArtifactLoss
+    ref = (gt + 0.08 * torch.randn(gt.shape, generator=torch.Generator().manual_seed(2)).cuda()).clamp(0, 1)
+    plain, refined = ArtifactLoss(refine=False), ArtifactLoss()
+    return [({"ref": False}, plain, lambda x, gt: artifact_refs.artifact_loss(x, gt)),
+            ({"ref": True}, lambda x, gt: refined(x, gt, ref), lambda x, gt: artifact_refs.artifact_loss(x, gt, ref))]
+
+
+def _artifact_rate(row, x):
+    images = 4.0 if row["ref"] else 3.0
+    row["hip"]["algorithmic_GBps"] = round(images * x.numel() * 4 / (row["hip"]["fwd_bwd_us"] * 1e-6) / 1e9, 1)
+
+
+def _artifact_engine_rows():
+    """(key, what runs beside Pixel, SOLVER.G_EMA_DECAY) of the steps timed beside the plain Pixel step."""
+    from srganst.loss import ArtifactLoss
+    return [("pixel_ema", None, 0.999), ("pixel_artifact_unrefined_ema", ("Artifact", ArtifactLoss(refine=False), 1.0), 0.999),
+            ("pixel_artifact_ema", ("Artifact", ArtifactLoss(), 1.0), 0.999)]
 
 
 def _freq_variants(x, gt, size):
@@ -174,6 +200,11 @@ CRITERIA = {
     "gv": dict(variants=_gv_variants, rate=_algorithmic_rate, torch=("torch", replay_us), clamp=True,
                engine=_engine("pixel_gv", "GV", "GradientVarianceLoss", 0.1),
                note=NOTE % "per-patch values" + "; algorithmic bytes = read sr + gt, write d(sr)"),
+    "artifact": dict(variants=_artifact_variants, rate=lambda hip, x, size: None, row_rate=_artifact_rate, torch=("torch", replay_us), clamp=True,
+                     engine_rows=_artifact_engine_rows,
+                     note=NOTE % "w map" + "; algorithmic bytes = read sr + gt (+ ref), write d(sr); in warmup_engine_step_us the difference "
+                     "pixel_artifact_unrefined_ema - pixel_ema is the criterion's own launches, pixel_artifact_ema - "
+                     "pixel_artifact_unrefined_ema the reference: the buffer copy and one eval-mode generator forward"),
     "bp": dict(variants=_bp_variants, rate=_bp_rate, torch=("torch", replay_us), clamp=True, on_grid=True, head={"scale": BP_SCALE},
                engine=_engine("pixel_bp", "BackProjection", "BackProjectionLoss", 0.1),
                note=NOTE % "saved map" + " and, for the HIP path, the saved map's store; algorithmic bytes: forward = read sr + gt, "
@@ -206,12 +237,19 @@ def main():
             row["hip"] = fwd_and_fwd_bwd(replay_us, lambda: crit(x, gt), x, a.reps)
             row[tkey] = fwd_and_fwd_bwd(timer, lambda: ref(x, gt), x, a.reps)
             c["rate"](row["hip"], x, size)
+            if "row_rate" in c:
+                c["row_rate"](row, x)
             with torch.no_grad():
                 row["loss_hip"], row["loss_torch"] = crit(x, gt).item(), ref(x, gt).item()
             print(json.dumps(row), file=sys.stderr, flush=True)
             out["rows"].append(row)
             work.append((row, lambda ref=ref, x=x, gt=gt: ref(x, gt), x))
-    if a.engine:
+    if a.engine and "engine_rows" in c:
+        out["warmup_engine_step_us"] = {"pixel": round(engine_step_us(None, a.engine_steps), 1)}
+        for key, extra, ema in c["engine_rows"]():
+            out["warmup_engine_step_us"][key] = round(engine_step_us(extra, a.engine_steps, ema), 1)
+        print(json.dumps(out["warmup_engine_step_us"]), file=sys.stderr, flush=True)
+    elif a.engine:
         key, make = c["engine"]
         out["warmup_engine_step_us"] = {"pixel": round(engine_step_us(None, a.engine_steps), 1), key: round(engine_step_us(make(), a.engine_steps), 1)}
         print(json.dumps(out["warmup_engine_step_us"]), file=sys.stderr, flush=True)
