@@ -494,6 +494,27 @@ int sst_gather_batch(const uint8_t* src, int64_t N, const int* idx, int B, int H
 int sst_gather_crops(const uint8_t* arena, int64_t arena_bytes, const int64_t* table, int64_t N, const int* desc, int B, int S,
                      const float* lut, float* gt, float* lr, const float* wy, const int* iy, const float* wx, const int* ix,
                      int oh, int ow, int Ty, int Tx, int span, void* stream);
+/* ---- the blind-SR degradation stage (device_data.py: Degradation / degrade; csrc/degrade.h):
+ *   lr = quantise( clamp( bicubic_down( x (*) k ) + n ) )   per sample, from its row of deg.
+ * deg: int32 [B,8] (device, 32-byte aligned): the fp32 bit patterns of qa, qb, qc, sigma_n, then the Philox key k0, k1, then two zero
+ * words.  Blur (skipped when qa < 0): w[dy][dx] = expf(-(qa dx^2 + qb dx dy + qc dy^2)) over the K x K window (K odd, 3..21, one
+ * per launch), normalised by its fp64 sum, applied with torch's `reflect` padding as one fp32 FMA chain in row-major order.
+ * Downscale: the bicubic of sst_gather_crops, term for term.  Noise (skipped when sigma_n == 0): sigma_n * z, z from Philox4x32-10
+ * with counter (e, 0, 0, 0), e the element's index in the sample's [3,oh,ow] LR, and Box-Muller on its first two words.  A sample
+ * with blur or noise is clamped to [0, 1]; one with neither takes sst_gather_crops' path and bits.  quantise = 0 writes the
+ * unclamped, unrounded value (tests and tools).  Weights that do not sum to a finite positive number yield a NaN LR.
+ * sst_gather_crops_degraded: sst_gather_crops (same arguments, lr not optional; span: with gt or without) with the stage between
+ * the conversion and the LR; gt is what sst_gather_crops writes.  K / 2 < S.  One launch, no allocation, no sync (capturable).
+ * sst_degrade: the same stage on x fp32 [B,3,H,W] -> lr [B,3,oh,ow], any H, W with K / 2 < min(H, W), through the same device code:
+ * sst_gather_crops_degraded's lr equals sst_degrade of its gt bit for bit.  Tiled in rows and in columns of
+ * sst_degrade_tile_cols() LR pixels.  One launch, no allocation, no sync. */
+int sst_gather_crops_degraded(const uint8_t* arena, int64_t arena_bytes, const int64_t* table, int64_t N, const int* desc, int B,
+                              int S, const float* lut, float* gt, float* lr, const float* wy, const int* iy, const float* wx,
+                              const int* ix, int oh, int ow, int Ty, int Tx, int span, const int* deg, int K, int quantise,
+                              void* stream);
+int sst_degrade(const float* x, const int* deg, int B, int H, int W, int K, int quantise, float* lr, const float* wy, const int* iy,
+                const float* wx, const int* ix, int oh, int ow, int Ty, int Tx, void* stream);
+int sst_degrade_tile_cols(void);
 /* Validation metrics of validate.image_metrics on the device (metrics.py), rounding for rounding: sr, hr fp32 NCHW [B,3,H,W] RGB;
  * out fp64 [B,2] = (MSE of the Y channel on the 0..255 scale over all H*W pixels, mean of the SSIM map over its (H-10) x (W-10)
  * valid region); sr_u8 / hr_u8: uint8 [B,H,W,3] BGR = tensor2img of each image (either may be null).  workspace:

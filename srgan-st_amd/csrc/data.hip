@@ -14,6 +14,8 @@
 // (192 px, x1/8: about 28 KiB).
 #include "common.h"
 #include "pixel_io.h"      // load_dword_unaligned
+#include "degrade.h"       // the degradation stage of gather_crops_degraded_kernel
+#include <algorithm>
 
 namespace {
 
@@ -126,6 +128,37 @@ __global__ __launch_bounds__(GATHER_NT) void gather_batch_kernel(
 // one column's own, so its place in V changes no bit) and the horizontal pass reads V through the hflip map.
 constexpr int CROPS_NT = 256;
 
+// The sample of descriptor d = (image, y0, x0, t): every field checked here again (the host has checked them); false when anything
+// is out of range.  off: the image's byte offset in the arena, Wi: its width.
+__device__ __forceinline__ bool crop_sample(const int4 d, const int64_t* __restrict__ table, int64_t N, int64_t arena_bytes, int S,
+                                            int64_t& off, int64_t& Wi) {
+  bool ok = d.x >= 0 && d.x < N && d.w >= 0 && d.w < 8;
+  if (ok) {
+    off = table[(int64_t)d.x * 3], Wi = table[(int64_t)d.x * 3 + 2];
+    const int64_t Hi = table[(int64_t)d.x * 3 + 1];
+    ok = off >= 0 && off <= arena_bytes && Hi > 0 && Wi > 0 && Wi <= arena_bytes && Hi <= (arena_bytes - off) / (3 * Wi) &&
+         d.y >= 0 && d.z >= 0 && (int64_t)d.y + S <= Hi && (int64_t)d.z + S <= Wi;
+  }
+  return ok;
+}
+
+// Stage the major lines [lo, lo + nline) of the sample's window as raw bytes (layout: above); consecutive lanes take consecutive
+// dwords of a source row's segment.
+__device__ __forceinline__ void stage_lines(const uint8_t* __restrict__ arena, uint8_t* __restrict__ s_src, int64_t off, int64_t Wi,
+                                            const int4 d, bool tr, int lo, int nline, int S, int W3p, int P) {
+  const int nrow = tr ? S : nline;                                       // source rows read
+  const int seg = tr ? nline * 3 : S * 3;                                // bytes of each
+  const int pitch = tr ? P : W3p;
+  const int ndw = (seg + 3) >> 2;
+  const int64_t base = off + (((int64_t)d.y + (tr ? 0 : lo)) * Wi + d.z + (tr ? lo : 0)) * 3;
+  const int64_t rowb = Wi * 3;
+  uint32_t* dst = reinterpret_cast<uint32_t*>(s_src);
+  for (int i = threadIdx.x; i < nrow * ndw; i += CROPS_NT) {
+    const int row = i / ndw, k = i - row * ndw;
+    dst[row * (pitch >> 2) + k] = load_dword_unaligned(arena, base + row * rowb + 4 * k, min(4, seg - 4 * k));
+  }
+}
+
 __global__ __launch_bounds__(CROPS_NT) void gather_crops_kernel(
     const uint8_t* __restrict__ arena, int64_t arena_bytes, const int64_t* __restrict__ table, int64_t N,
     const int* __restrict__ desc, int S, int nband, const float* __restrict__ lut, float* __restrict__ gt, float* __restrict__ lr,
@@ -144,13 +177,8 @@ __global__ __launch_bounds__(CROPS_NT) void gather_crops_kernel(
   const int4 d = reinterpret_cast<const int4*>(desc)[b];
   const int t = d.w;
   const bool tr = t & 4, vf = t & 2, hf = t & 1;
-  bool ok = d.x >= 0 && d.x < N && t >= 0 && t < 8;
-  int64_t off = 0, Hi = 0, Wi = 0;
-  if (ok) {
-    off = table[(int64_t)d.x * 3], Hi = table[(int64_t)d.x * 3 + 1], Wi = table[(int64_t)d.x * 3 + 2];
-    ok = off >= 0 && off <= arena_bytes && Hi > 0 && Wi > 0 && Wi <= arena_bytes && Hi <= (arena_bytes - off) / (3 * Wi) &&
-         d.y >= 0 && d.z >= 0 && (int64_t)d.y + S <= Hi && (int64_t)d.z + S <= Wi;
-  }
+  int64_t off = 0, Wi = 0;
+  bool ok = crop_sample(d, table, N, arena_bytes, S, off, Wi);
   // ---- the run [lo, hi] of major lines this band needs
   int lo = S, hi = -1;
   if (gt) {
@@ -180,19 +208,7 @@ __global__ __launch_bounds__(CROPS_NT) void gather_crops_kernel(
   s_lut[tid] = lut[tid];                                                 // CROPS_NT == 256
 
   // ---- stage: consecutive lanes take consecutive dwords of a source row's segment
-  {
-    const int nrow = tr ? S : nline;                                     // source rows read
-    const int seg = tr ? nline * 3 : S3;                                 // bytes of each
-    const int pitch = tr ? P : W3p;
-    const int ndw = (seg + 3) >> 2;
-    const int64_t base = off + (((int64_t)d.y + (tr ? 0 : lo)) * Wi + d.z + (tr ? lo : 0)) * 3;
-    const int64_t rowb = Wi * 3;
-    uint32_t* dst = reinterpret_cast<uint32_t*>(s_src);
-    for (int i = tid; i < nrow * ndw; i += CROPS_NT) {
-      const int row = i / ndw, k = i - row * ndw;
-      dst[row * (pitch >> 2) + k] = load_dword_unaligned(arena, base + row * rowb + 4 * k, min(4, seg - 4 * k));
-    }
-  }
+  stage_lines(arena, s_src, off, Wi, d, tr, lo, nline, S, W3p, P);
   __syncthreads();
   const int sL = tr ? 3 : W3p, sX = tr ? P : 3;                          // byte(line, x', c) = s_src[(line - lo) * sL + x' * sX + c]
 
@@ -234,6 +250,87 @@ __global__ __launch_bounds__(CROPS_NT) void gather_crops_kernel(
     }
     lr[(((int64_t)b * 3 + c) * oh + band) * ow + ox] = rintf(255.f * acc) / 255.f;
   }
+}
+
+
+// ---- The same gather with the degradation stage of degrade.h between the conversion and the LR (DATA.DEGRADE): per sample a blur
+// with its own Gaussian kernel, the bicubic, noise, quantise; gt as above.  One workgroup per (sample, band of R <= deg::ROWS_MAX LR
+// rows, channel): the blur is K*K FMAs per pixel, so the channels are spread over workgroups (each stages the band's bytes for
+// itself: 12 KiB against 0.85 M FMAs at S = 96, K = 21) and a band of R LR rows blurs (R - 1) * scale + Ty rows for the R * scale it
+// owns (R = 2, x4: 20 for 8) instead of Ty for scale (16 for 4).  The band's taps name the blur rows [lo_b, hi_b] of the OUTPUT
+// (transformed) crop; those, p = K / 2 rows of reflected halo on either side (reflected at the crop's border: rows
+// [max(0, lo_b - p), min(S - 1, hi_b + p)], a contiguous run, as p < S) and the band's own rows are staged as the major lines
+// [lo, hi] exactly as above.  The channel's fp32 plane is then built ONCE from the bytes, in output orientation and with the halo
+// laid out (deg::finish_tile's input), so both flips, the transposition and the reflection are index maps of that one pass.
+__global__ __launch_bounds__(deg::NT) void gather_crops_degraded_kernel(
+    const uint8_t* __restrict__ arena, int64_t arena_bytes, const int64_t* __restrict__ table, int64_t N,
+    const int* __restrict__ desc, int S, const float* __restrict__ lut, float* __restrict__ gt, float* __restrict__ lr,
+    const float* __restrict__ wy, const int* __restrict__ iy, const float* __restrict__ wx, const int* __restrict__ ix, int oh,
+    int ow, int Ty, int Tx, const int* __restrict__ dg, int K, int quantise, int R, int nr_max, int nline_max, int P) {
+  static_assert(CROPS_NT == deg::NT, "stage_lines and the degradation stage run with one workgroup size");
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int b = blockIdx.y, band = blockIdx.x / 3, c = blockIdx.x % 3, tid = threadIdx.x;
+  const int W3p = (S * 3 + 15) & ~15;
+  const int64_t raw = (int64_t)nline_max * W3p > (int64_t)S * P ? (int64_t)nline_max * W3p : (int64_t)S * P;
+  const deg::Layout L(K, R, nr_max, S, raw, 256 * 4);
+  const int p = L.p;
+  uint8_t* s_src = smem + L.o_a;                                         // the staged run of major lines; later the blurred tile
+  float* s_lut = reinterpret_cast<float*>(smem + L.o_tail);              // [256]
+  deg::Tile tl;
+  tl.oy0 = band * R, tl.noy = min(R, oh - tl.oy0), tl.ox0 = 0, tl.nox = ow, tl.c0 = 0, tl.nc = S;
+  const int yb0 = (int)((int64_t)tl.oy0 * S / oh), yb1 = (int)((int64_t)(tl.oy0 + tl.noy) * S / oh);
+  float* lr_plane = lr + ((int64_t)b * 3 + c) * oh * ow;
+
+  const int4 d = reinterpret_cast<const int4*>(desc)[b];
+  const int t = d.w;
+  const bool tr = t & 4, vf = t & 2, hf = t & 1;
+  int64_t off = 0, Wi = 0;
+  bool ok = crop_sample(d, table, N, arena_bytes, S, off, Wi);
+  // ---- the blur rows [lo_b, hi_b], then the run [lo, hi] of major lines: those with their halo, and with gt the band's own rows
+  int hi_b;
+  ok = deg::tap_rows(iy, Ty, tl.oy0, tl.noy, S, tl.r0, hi_b) && ok;
+  tl.nr = hi_b - tl.r0 + 1;
+  int y_lo = max(0, tl.r0 - p), y_hi = min(S - 1, hi_b + p);
+  if (gt) y_lo = min(y_lo, yb0), y_hi = max(y_hi, yb1 - 1);
+  const int lo = vf ? S - 1 - y_hi : y_lo, hi = vf ? S - 1 - y_lo : y_hi;
+  const int nline = hi - lo + 1;
+  ok = ok && tl.nr <= nr_max && nline >= 1 && nline <= nline_max;
+  if (!ok) {
+    const float q = __builtin_nanf("");
+    if (gt)
+      for (int i = tid; i < (yb1 - yb0) * S; i += deg::NT) gt[(((int64_t)b * 3 + c) * S + yb0 + i / S) * S + i % S] = q;
+    return deg::fill_nan(lr_plane, tl, ow);
+  }
+  const deg::Params q = deg::load_params(dg, b);
+  s_lut[tid] = lut[tid];                                                 // deg::NT == 256
+  if (q.blur()) deg::weights_raw(reinterpret_cast<float*>(smem + L.o_k), q, K);
+  stage_lines(arena, s_src, off, Wi, d, tr, lo, nline, S, W3p, P);
+  __syncthreads();
+  if (q.blur() && tid == deg::NT - 1)                                   // one thread, beside the others' gt and plane passes
+    deg::weights_sum(reinterpret_cast<const float*>(smem + L.o_k), reinterpret_cast<double*>(smem), K);
+  const int sL = tr ? 3 : W3p, sX = tr ? P : 3;                          // byte(line, x', c) = s_src[(line - lo) * sL + x' * sX + c]
+
+  // ---- gt: this channel's plane of the band's output rows, 4 pixels per float4 store  (S % 4 == 0)
+  if (gt) {
+    const int rows = yb1 - yb0, S4 = S >> 2;
+    for (int i = tid; i < rows * S4; i += deg::NT) {
+      const int x4 = i % S4, y = yb0 + i / S4, x = x4 * 4;
+      const uint8_t* s = s_src + ((vf ? S - 1 - y : y) - lo) * sL + (hf ? S - 1 - x : x) * sX + c;
+      const int dx = hf ? -sX : sX;
+      const float4 v = make_float4(s_lut[s[0]], s_lut[s[dx]], s_lut[s[2 * dx]], s_lut[s[3 * dx]]);
+      *reinterpret_cast<float4*>(gt + (((int64_t)b * 3 + c) * S + y) * S + x) = v;
+    }
+  }
+  // ---- the plane: plane[r][j] = out[refl(lo_b - p + r)][refl(j - p)], each byte converted once
+  float* plane = reinterpret_cast<float*>(smem + L.o_plane);
+  const int wp = S + 2 * p;
+  for (int i = tid; i < (tl.nr + 2 * p) * wp; i += deg::NT) {
+    const int r = i / wp, j = i - r * wp;
+    const int y = deg::refl(tl.r0 - p + r, S), x = deg::refl(j - p, S);
+    plane[r * L.pitch + j] = s_lut[s_src[((vf ? S - 1 - y : y) - lo) * sL + (hf ? S - 1 - x : x) * sX + c]];
+  }
+  __syncthreads();
+  deg::finish_tile(smem, L, tl, q, K, quantise, lr_plane, (uint32_t)c * (uint32_t)(oh * ow), wy, iy, wx, ix, ow, Ty, Tx);
 }
 
 }  // namespace
@@ -282,5 +379,44 @@ SST_API int sst_gather_crops(const uint8_t* arena, int64_t arena_bytes, const in
   gather_crops_kernel<<<dim3(nband, B), CROPS_NT, (size_t)lds, sst_stream(stream)>>>(arena, arena_bytes, table, N, desc, S, nband, lut,
                                                                                      gt, lr, wy, iy, wx, ix, oh, ow, Ty, Tx, span, P);
   SST_LAUNCH_CHECK("gather_crops_kernel");
+  return SST_OK;
+}
+
+SST_API int sst_gather_crops_degraded(const uint8_t* arena, int64_t arena_bytes, const int64_t* table, int64_t N, const int* desc,
+                                      int B, int S, const float* lut, float* gt, float* lr, const float* wy, const int* iy,
+                                      const float* wx, const int* ix, int oh, int ow, int Ty, int Tx, int span, const int* dg, int K,
+                                      int quantise, void* stream) {
+  SST_REQUIRE(arena && table && desc && lut && lr && dg && arena_bytes > 0 && N > 0 && B > 0 && S > 0,
+              "sst_gather_crops_degraded: bad argument (lr and deg are not optional)");
+  SST_REQUIRE((reinterpret_cast<uintptr_t>(arena) & 15) == 0 && arena_bytes % 16 == 0,
+              "sst_gather_crops_degraded: the arena and its size (%lld B) must be multiples of 16 bytes", (long long)arena_bytes);
+  SST_REQUIRE((reinterpret_cast<uintptr_t>(desc) & 15) == 0, "sst_gather_crops_degraded: desc must be 16-byte aligned");
+  SST_REQUIRE((reinterpret_cast<uintptr_t>(dg) & 31) == 0, "sst_gather_crops_degraded: deg must be 32-byte aligned (rows of 8 int32)");
+  SST_REQUIRE(B <= 65535, "sst_gather_crops_degraded: batch %d > 65535", B);
+  SST_REQUIRE(S % 4 == 0 && S <= 16384, "sst_gather_crops_degraded: crop side %d must be a multiple of 4 (and at most 16384)", S);
+  SST_REQUIRE(K >= deg::K_MIN && K <= deg::K_MAX && (K & 1), "sst_gather_crops_degraded: the blur window K = %d must be odd and in %d..%d",
+              K, deg::K_MIN, deg::K_MAX);
+  SST_REQUIRE(K / 2 < S, "sst_gather_crops_degraded: the half window %d (K = %d) must be smaller than the crop side %d", K / 2, K, S);
+  SST_REQUIRE(span > 0 && span <= S, "sst_gather_crops_degraded: span %d outside [1, %d]", span, S);
+  SST_REQUIRE(wy && iy && wx && ix && oh > 0 && ow > 0 && oh <= S && ow <= S && Ty > 0 && Tx > 0,
+              "sst_gather_crops_degraded: bad LR arguments");
+  // the band height: the most LR rows (at most deg::ROWS_MAX) whose workgroup fits the LDS budget.  Taps of consecutive LR rows move
+  // by the scale, which is at most S / oh.
+  const int W3p = (3 * S + 15) & ~15, p = K / 2;
+  int R = oh < deg::ROWS_MAX ? oh : deg::ROWS_MAX, nr_max = 0, nline_max = 0, P = 0;
+  int64_t lds = 0;
+  for (; R >= 1; --R) {
+    nr_max = (int)std::min<int64_t>(S, span + (int64_t)(R - 1) * (S / oh));
+    nline_max = std::min(S, nr_max + 2 * p);
+    P = (3 * nline_max + 3) & ~3;                                // pitch of a transposed sample's LDS rows: whole dwords, an odd number
+    if (((P >> 2) & 1) == 0) P += 4;
+    lds = deg::Layout(K, R, nr_max, S, std::max<int64_t>((int64_t)nline_max * W3p, (int64_t)S * P), 256 * 4).bytes;
+    if (lds <= deg::LDS_BUDGET) break;
+  }
+  SST_REQUIRE(R >= 1, "sst_gather_crops_degraded: %lld B of LDS needed (S %d, span %d, K %d) > 64 KiB", (long long)lds, S, span, K);
+  const int nband = (oh + R - 1) / R;
+  gather_crops_degraded_kernel<<<dim3(nband * 3, B), deg::NT, (size_t)lds, sst_stream(stream)>>>(
+      arena, arena_bytes, table, N, desc, S, lut, gt, lr, wy, iy, wx, ix, oh, ow, Ty, Tx, dg, K, quantise, R, nr_max, nline_max, P);
+  SST_LAUNCH_CHECK("gather_crops_degraded_kernel");
   return SST_OK;
 }

@@ -94,6 +94,22 @@ class Config:
         # one of the eight flips and transpositions per sample; drawn per epoch from a private generator seeded by (SEED, epoch)
         self.DATA.RANDOM_CROP = False
         self.DATA.AUGMENT = False
+        # with ON_DEVICE_WHOLE_IMAGES only: the classical blind-SR degradation lr = quantise(clamp(bicubic(gt * k) + n)) instead of
+        # lr = bicubic(gt), made per sample in the same gather launch (device_data.Degradation, sst_gather_crops_degraded): k an
+        # anisotropic Gaussian on a KSIZE x KSIZE window (odd, 3..21) with standard deviations uniform in BLUR_SIGMA (equal when
+        # ANISO is off) at a uniform angle, applied with probability BLUR_PROB; n Gaussian noise with a standard deviation uniform
+        # in NOISE_SIGMA (0..255 units), applied with probability NOISE_PROB.  Drawn per epoch and tile from a second private
+        # generator seeded by (SEED, epoch); gt is untouched
+        self.DATA.DEGRADE = False
+        self.DATA.DEGRADE_BLUR_SIGMA = (0.2, 4.0)
+        self.DATA.DEGRADE_BLUR_ANISO = True
+        self.DATA.DEGRADE_BLUR_PROB = 1.0
+        self.DATA.DEGRADE_BLUR_KSIZE = 21
+        self.DATA.DEGRADE_NOISE_SIGMA = (0.0, 25.0)
+        self.DATA.DEGRADE_NOISE_PROB = 1.0
+        # (sigma1, sigma2, theta_deg, noise): validation feeds the generator degrade(gt) with these fixed parameters (key = the image's
+        # index, window DEGRADE_BLUR_KSIZE) instead of the LR file; the printed line and _metrics.txt say so.  None: the LR files
+        self.DATA.VALIDATE_DEGRADE = None
 
         self.MODEL = dotdict()
         self.MODEL.G_CONTINUE_FROM_WARMUP = False

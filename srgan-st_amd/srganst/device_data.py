@@ -9,6 +9,8 @@ With config.DATA.ON_DEVICE_WHOLE_IMAGES the device holds the WHOLE training imag
 beforehand, images of any sizes) and the one launch per batch (sst_gather_crops) also cuts each sample's S x S window and applies one
 of the eight dihedral transforms to it: DeviceCropLoader walks the tile grid data-prep/prepare_dataset.py would have written, or,
 with DATA.RANDOM_CROP / DATA.AUGMENT, draws the window and the transform anew every epoch.
+With DATA.DEGRADE that launch (sst_gather_crops_degraded) also blurs each sample with its own Gaussian kernel before the bicubic and
+adds Gaussian noise after it (Degradation, the classical blind-SR model); degrade() is that stage alone on any fp32 batch.
 """
 from __future__ import annotations
 
@@ -292,6 +294,126 @@ def _pad16(n: int) -> int:
     return (n + 15) & ~15
 
 
+# ---- the blind-SR degradation stage (DATA.DEGRADE; csrc/degrade.h)
+DEGRADE_TILE_COLS = 16           # LR columns of one workgroup of sst_degrade (csrc/degrade.h: deg::TILE_COLS; sst_degrade_tile_cols())
+DEGRADE_KSIZES = tuple(range(3, 22, 2))
+_DEGRADE_STREAM = 0x6A09E667F3BCC908      # keeps the loader's degradation generator apart from its window / transform generator
+
+
+def degrade_rows(sigma1, sigma2, theta, noise255, keys) -> np.ndarray:
+    """The deg rows of the kernels, int32 [n, 8], from per-sample arrays: the Gaussian's standard deviations along its two axes
+    (pixels; <= 0 in either: no blur, the row gets the sentinel qa = -1), the angle of the first axis against x = columns (radians; y
+    = rows), the noise's standard deviation in 0..255 units and the Philox key [n, 2].  With [[A, B], [B, C]] the inverse of
+    R(theta) diag(sigma1^2, sigma2^2) R(theta)^T the row holds (A/2, B, C/2), computed in fp64 and rounded once to fp32, then
+    noise255 / 255, the key and two zero words."""
+    s1, s2, th, nz = (np.atleast_1d(np.asarray(a, np.float64)) for a in (sigma1, sigma2, theta, noise255))
+    n = len(s1)
+    keys = np.asarray(keys, np.int64).reshape(n, 2) & 0xFFFFFFFF
+    blur = (s1 > 0) & (s2 > 0)
+    i1, i2 = 1.0 / np.where(blur, s1, 1.0) ** 2, 1.0 / np.where(blur, s2, 1.0) ** 2
+    c, s = np.cos(th), np.sin(th)
+    q = np.stack([0.5 * (c * c * i1 + s * s * i2), c * s * (i1 - i2), 0.5 * (s * s * i1 + c * c * i2), nz / 255.0], 1)
+    q[~blur, :3] = (-1.0, 0.0, 0.0)
+    rows = np.zeros((n, 8), np.int32)
+    rows[:, :4] = q.astype(np.float32).view(np.int32)
+    rows[:, 4:6] = keys.astype(np.uint32).view(np.int32)
+    return rows
+
+
+class Degradation:
+    """The per-sample parameters of the classical blind-SR degradation lr = quantise(clamp(bicubic_down(gt (*) k) + n)): k an
+    anisotropic Gaussian on a ksize x ksize window, n Gaussian noise.  draw(n, generator) -> int32 [n, 8] on the host, one deg row
+    per sample: sigma1, sigma2 uniform in blur_sigma (equal when aniso is off), theta uniform in [0, pi), the no-blur sentinel with
+    probability 1 - blur_prob; the noise's standard deviation uniform in noise_sigma (0..255 units), 0 with probability
+    1 - noise_prob; two random key words.  Degradation.fixed(...) draws the same row every time (validation, tests)."""
+
+    def __init__(self, blur_sigma=(0.2, 4.0), aniso: bool = True, blur_prob: float = 1.0, noise_sigma=(0.0, 25.0),
+                 noise_prob: float = 1.0, ksize: int = 21):
+        self.blur_sigma, self.noise_sigma = (float(blur_sigma[0]), float(blur_sigma[1])), (float(noise_sigma[0]), float(noise_sigma[1]))
+        self.aniso, self.blur_prob, self.noise_prob, self.ksize = bool(aniso), float(blur_prob), float(noise_prob), int(ksize)
+        self._fixed = None
+        if not 0 < self.blur_sigma[0] <= self.blur_sigma[1]:
+            raise ValueError(f"Degradation: blur_sigma {blur_sigma} must be 0 < lo <= hi")
+        if not 0 <= self.noise_sigma[0] <= self.noise_sigma[1]:
+            raise ValueError(f"Degradation: noise_sigma {noise_sigma} must be 0 <= lo <= hi")
+        if not (0 <= self.blur_prob <= 1 and 0 <= self.noise_prob <= 1):
+            raise ValueError(f"Degradation: blur_prob {blur_prob} and noise_prob {noise_prob} must be in [0, 1]")
+        if self.ksize not in DEGRADE_KSIZES:
+            raise ValueError(f"Degradation: ksize {ksize} must be odd and in 3..21")
+
+    @classmethod
+    def fixed(cls, sigma1: float, sigma2: float, theta_deg: float, noise: float, key=0, ksize: int = 21) -> "Degradation":
+        """Every sample gets these parameters: the two standard deviations (0: no blur), the angle in degrees, the noise's standard
+        deviation in 0..255 units and the key (an int: the low and high 32 bits; or a pair of words)."""
+        if sigma1 < 0 or sigma2 < 0 or noise < 0 or (sigma1 > 0) != (sigma2 > 0):
+            raise ValueError(f"Degradation.fixed: sigma ({sigma1}, {sigma2}) must be both positive or both 0, noise {noise} >= 0")
+        d = cls(ksize=ksize)
+        k = (int(key) & 0xFFFFFFFF, (int(key) >> 32) & 0xFFFFFFFF) if isinstance(key, (int, np.integer)) else (int(key[0]), int(key[1]))
+        d._fixed = (float(sigma1), float(sigma2), float(theta_deg), float(noise), k)
+        return d
+
+    def __repr__(self) -> str:
+        if self._fixed:
+            s1, s2, th, nz, k = self._fixed
+            return f"Degradation.fixed(sigma1={s1:g}, sigma2={s2:g}, theta_deg={th:g}, noise={nz:g}, key={k}, ksize={self.ksize})"
+        return (f"Degradation(blur_sigma={self.blur_sigma}, aniso={self.aniso}, blur_prob={self.blur_prob:g}, "
+                f"noise_sigma={self.noise_sigma}, noise_prob={self.noise_prob:g}, ksize={self.ksize})")
+
+    def draw(self, n: int, generator: torch.Generator | None = None) -> Tensor:
+        if self._fixed:
+            s1, s2, th, nz, k = self._fixed
+            return torch.from_numpy(degrade_rows([s1] * n, [s2] * n, [np.deg2rad(th)] * n, [nz] * n, [k] * n))
+        u = torch.rand(n, 6, generator=generator, dtype=torch.float64).numpy()
+        keys = torch.randint(0, 1 << 32, (n, 2), generator=generator, dtype=torch.int64).numpy()
+        (b0, b1), (n0, n1) = self.blur_sigma, self.noise_sigma
+        s1 = b0 + (b1 - b0) * u[:, 0]
+        s2 = b0 + (b1 - b0) * u[:, 1] if self.aniso else s1
+        blur = u[:, 3] < self.blur_prob
+        nz = np.where(u[:, 5] < self.noise_prob, n0 + (n1 - n0) * u[:, 4], 0.0)
+        return torch.from_numpy(degrade_rows(np.where(blur, s1, 0.0), np.where(blur, s2, 0.0), np.pi * u[:, 2], nz, keys))
+
+    @classmethod
+    def from_config(cls, config) -> "Degradation | None":
+        """DATA.DEGRADE_* -> a Degradation, or None with DATA.DEGRADE off."""
+        data = config.DATA
+        if not data.get("DEGRADE", False):
+            return None
+        return cls(data.DEGRADE_BLUR_SIGMA, data.DEGRADE_BLUR_ANISO, data.DEGRADE_BLUR_PROB, data.DEGRADE_NOISE_SIGMA,
+                   data.DEGRADE_NOISE_PROB, data.DEGRADE_BLUR_KSIZE)
+
+
+def _check_deg(deg: Tensor, B: int, device, who: str) -> None:
+    if deg.dtype != torch.int32 or tuple(deg.shape) != (B, 8) or deg.device != device or not deg.is_contiguous():
+        raise ValueError(f"{who}: deg must be contiguous int32 [{B}, 8] on {device}, got {deg.dtype} {tuple(deg.shape)} on {deg.device}")
+
+
+_degrade_bicubic = {}
+
+
+def degrade(x: Tensor, deg: Tensor, scale: int, ksize: int = 21, quantise: bool = True) -> Tensor:
+    """ONE sst_degrade launch on the current stream: the degradation stage on an fp32 batch x [B,3,H,W] of any size (H, W >= scale,
+    ksize // 2 < min(H, W)) with per-sample rows deg int32 [B,8] (Degradation.draw / degrade_rows) -> lr [B,3,H//scale,W//scale].
+    The stand-alone form of DeviceImageArena.crops(desc, deg=...), whose lr it reproduces from its gt bit for bit.  quantise=False
+    (tests and tools) returns the unclamped, unrounded values."""
+    if scale not in (2, 4, 8):
+        raise ValueError(f"degrade: scale must be 2, 4 or 8, got {scale!r}")
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_cuda:
+        raise ValueError(f"degrade: x must be fp32 [B, 3, H, W] on a ROCm device, got {x.dtype} {tuple(x.shape)} on {x.device}")
+    B, _, H, W = x.shape
+    if H < scale or W < scale:
+        raise ValueError(f"degrade: image {W}x{H} is smaller than the scale {scale}")
+    _check_deg(deg, B, x.device, "degrade")
+    bic = _degrade_bicubic.setdefault(x.device, Bicubic(str(x.device)))
+    wy, iy, wx, ix = bic.tables_i32(H, W, 1.0 / scale, x.device)
+    oh, ow = int(H * (1.0 / scale)), int(W * (1.0 / scale))
+    x = x.contiguous()
+    lr = torch.empty(B, 3, oh, ow, device=x.device)
+    _abi.check(_abi.lib().sst_degrade(_abi.ptr(x), _abi.ptr(deg), B, H, W, int(ksize), int(bool(quantise)), _abi.ptr(lr), _abi.ptr(wy),
+                                      _abi.ptr(iy), _abi.ptr(wx), _abi.ptr(ix), oh, ow, wy.shape[1], wx.shape[1],
+                                      _abi.stream_ptr()), "sst_degrade")
+    return lr
+
+
 class DeviceImageArena:
     """WHOLE training images of any sizes on one device: one packed uint8 arena (HWC/RGB, every image at a 16-byte aligned
     offset) and a device table [N, 3] int64 of (byte offset, H, W).  len() is the number of tiles of the virtual tile list
@@ -430,10 +552,12 @@ class DeviceImageArena:
         return self._span[key]
 
     def crops(self, desc: Tensor, gt_out: Tensor | None = None, lr_out: Tensor | None = None, with_gt: bool = True,
-              with_lr: bool = True):
+              with_lr: bool = True, deg: Tensor | None = None, ksize: int | None = None, quantise: bool = True):
         """ONE sst_gather_crops launch on the current stream: gt [B,3,S,S] = the windows desc names, transformed, on the 1/255
         grid; lr [B,3,S/up,S/up] = their bicubic.  desc: int32 [B,4] on the arena's device (checked on the host by DeviceCropLoader /
-        check_desc).  Writes into gt_out / lr_out when given; with_gt / with_lr = False skips that output (returned as None)."""
+        check_desc).  Writes into gt_out / lr_out when given; with_gt / with_lr = False skips that output (returned as None).
+        deg: int32 [B,8] on the device (Degradation.draw) makes it ONE sst_gather_crops_degraded launch instead: the same gt, and lr
+        = degrade(gt, deg, upscale, ksize, quantise) bit for bit (blur, bicubic, noise, quantise); ksize defaults to 21."""
         if desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != 4 or desc.device != self.device:
             raise ValueError(f"DeviceImageArena.crops: desc must be int32 [B, 4] on {self.device}")
         B, S, o = desc.shape[0], self.crop, self.out
@@ -448,6 +572,16 @@ class DeviceImageArena:
             _expect(lr, (B, 3, o, o), "lr_out")
             wy, iy, wx, ix = self._bicubic.tables_i32(S, S, 1.0 / self.upscale, self.device)
             Ty, Tx = wy.shape[1], wx.shape[1]
+        if deg is not None:
+            if not with_lr:
+                raise ValueError("DeviceImageArena.crops: deg degrades the lr output; with_lr=False leaves nothing to degrade")
+            _check_deg(deg, B, self.device, "DeviceImageArena.crops")
+            _abi.check(_abi.lib().sst_gather_crops_degraded(
+                _abi.ptr(self.arena), self.arena.numel(), _abi.ptr(self.table), self.n_images, _abi.ptr(desc), B, S, _abi.ptr(self.lut),
+                _abi.ptr(gt), _abi.ptr(lr), _abi.ptr(wy), _abi.ptr(iy), _abi.ptr(wx), _abi.ptr(ix), o, o, Ty, Tx,
+                self.span(with_gt, True), _abi.ptr(deg), 21 if ksize is None else int(ksize), int(bool(quantise)),
+                _abi.stream_ptr()), "sst_gather_crops_degraded")
+            return gt, lr
         _abi.check(_abi.lib().sst_gather_crops(_abi.ptr(self.arena), self.arena.numel(), _abi.ptr(self.table), self.n_images,
                                                _abi.ptr(desc), B, S, _abi.ptr(self.lut), _abi.ptr(gt), _abi.ptr(lr), _abi.ptr(wy),
                                                _abi.ptr(iy), _abi.ptr(wx), _abi.ptr(ix), o, o, Ty, Tx,
@@ -464,16 +598,23 @@ class DeviceCropLoader:
     The draws come from a private torch.Generator seeded from (seed, epoch) and are made for ALL tiles of the set, then indexed by
     the sampler's order: a tile's window and transform in an epoch depend on neither world size nor rank nor batch size, and the
     default CPU generator (model init, shuffles) is never touched.  With both switches off nothing is drawn.  The epoch advances
-    with every __iter__; set_epoch() sets it."""
+    with every __iter__; set_epoch() sets it.
+    degradation: every batch is one sst_gather_crops_degraded launch; the epoch's deg rows are drawn for ALL tiles as well, from a
+    SECOND private generator (seed, epoch and a constant of its own), so a tile's degradation depends on neither world size nor rank
+    nor batch size either, the window and transform draws are the ones made without it, and resuming at an epoch reproduces it."""
 
     def __init__(self, arena: DeviceImageArena, batch_size: int, sampler=None, random_crop: bool = False, augment: bool = False,
-                 seed: int = 0):
+                 seed: int = 0, degradation: Degradation | None = None):
         if batch_size <= 0:
             raise ValueError("DeviceCropLoader: batch_size must be positive")
         self.dset = arena
         self.batch_size = int(batch_size)
         self.sampler = sampler if sampler is not None else torch.utils.data.RandomSampler(arena)
         self.random_crop, self.augment, self.seed = bool(random_crop), bool(augment), int(seed)
+        self.degradation = degradation
+        if degradation is not None and degradation.ksize // 2 >= arena.crop:
+            raise ValueError(f"DeviceCropLoader: the blur's half window {degradation.ksize // 2} must be smaller than the crop "
+                             f"side {arena.crop}")
         self.epoch = 0
         self._gt = self._lr = None
 
@@ -501,33 +642,71 @@ class DeviceCropLoader:
                 d[:, 3] = torch.randint(0, 8, (len(a),), generator=g, dtype=torch.int64).numpy()
         return d
 
-    def plan(self) -> Tensor:
-        """The current epoch's descriptors on the host, in the sampler's order: int32 [len(self) * batch_size, 4]; tile indices and
-        windows checked against the set."""
+    def deg_draws(self, epoch: int) -> np.ndarray | None:
+        """The epoch's deg row of EVERY tile of the set: int32 [len(arena), 8]; None without a degradation."""
+        if self.degradation is None:
+            return None
+        g = torch.Generator().manual_seed((self.seed * 1000003 + epoch + _DEGRADE_STREAM) % (1 << 63))
+        return self.degradation.draw(len(self.dset), g).numpy()
+
+    def plan_both(self):
+        """The current epoch on the host, in the sampler's order (ONE walk of the sampler): the descriptors int32
+        [len(self) * batch_size, 4], tile indices and windows checked against the set, and the deg rows int32 [.., 8] or None."""
         order = np.fromiter(iter(self.sampler), dtype=np.int64)[: len(self) * self.batch_size]
         n = len(self.dset)
         if order.size and (int(order.min()) < 0 or int(order.max()) >= n):
             raise IndexError(f"DeviceCropLoader: the sampler produced an index outside [0, {n})")
         desc = self.draws(self.epoch)[order]
         self.dset.check_desc(desc)
-        return torch.from_numpy(np.ascontiguousarray(desc))
+        deg = self.deg_draws(self.epoch)
+        return (torch.from_numpy(np.ascontiguousarray(desc)),
+                None if deg is None else torch.from_numpy(np.ascontiguousarray(deg[order])))
+
+    def plan(self) -> Tensor:
+        """plan_both()'s descriptors."""
+        return self.plan_both()[0]
 
     def __iter__(self):
         B = self.batch_size
-        host = self.plan()
+        host, host_deg = self.plan_both()
         self.epoch += 1
         dev = self.dset.device
-        desc = host.pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else host
+        up = (lambda t: t.pin_memory().to(dev, non_blocking=True)) if dev.type == "cuda" else (lambda t: t)
+        desc = up(host)
+        if host_deg is None:
+            for k in range(len(self)):
+                yield self.dset.crops(desc[k * B:(k + 1) * B], self._gt, self._lr)
+            return
+        deg = up(host_deg)                                               # once per epoch, next to desc
         for k in range(len(self)):
-            yield self.dset.crops(desc[k * B:(k + 1) * B], self._gt, self._lr)
+            yield self.dset.crops(desc[k * B:(k + 1) * B], self._gt, self._lr, deg=deg[k * B:(k + 1) * B],
+                                  ksize=self.degradation.ksize)
 
 
 def check_switches(config) -> None:
-    """DATA.RANDOM_CROP and DATA.AUGMENT are made by the whole-image gather only."""
+    """DATA.RANDOM_CROP, DATA.AUGMENT and DATA.DEGRADE are made by the whole-image gather only."""
     data = config.DATA
+    if data.get("DEGRADE", False) and not data.get("ON_DEVICE_WHOLE_IMAGES", False):
+        raise ValueError("DATA.DEGRADE needs DATA.ON_DEVICE_WHOLE_IMAGES = True: the per-sample blur and noise are made by the "
+                         "whole-image gather (device_data.DeviceCropLoader, sst_gather_crops_degraded), neither the pre-cut crops "
+                         "(DATA.ON_DEVICE) nor the host DataLoader have them")
     if (data.get("RANDOM_CROP", False) or data.get("AUGMENT", False)) and not data.get("ON_DEVICE_WHOLE_IMAGES", False):
         raise ValueError("DATA.RANDOM_CROP / DATA.AUGMENT need DATA.ON_DEVICE_WHOLE_IMAGES = True: the random window and the flips / "
                          "transposition are made by the whole-image gather (device_data.DeviceCropLoader), no other data path has them")
+
+
+def announce_degradation(config, degradation: Degradation) -> None:
+    """The drivers' one log line for DATA.DEGRADE, and a warning for every configured BackProjectionLoss(target="gt"): its target is
+    the bicubic of gt, which is then not the LR image the generator saw (target="lr" takes the loader's)."""
+    import warnings
+    from .loss import BackProjectionLoss
+    print(f"[Data] DATA.DEGRADE: lr = quantise(clamp(bicubic(gt * k) + n)) per sample in the gather launch, {degradation!r}")
+    loss = config.MODEL.G_LOSS
+    for where in ("CRITERIONS", "WARMUP_CRITERIONS"):
+        for name, crit in loss.get(where, {}).items():
+            if isinstance(crit, BackProjectionLoss) and crit.target == "gt":
+                warnings.warn(f"DATA.DEGRADE: MODEL.G_LOSS.{where}[{name!r}] is a BackProjectionLoss(target='gt'); its target is the "
+                              "bicubic of gt, not the degraded LR image the generator is given")
 
 
 def on_device(config) -> bool:
@@ -554,8 +733,11 @@ def train_loader(config, train_dataset, world: int, rank: int):
             raise ValueError("DATA.ON_DEVICE_WHOLE_IMAGES: the whole images come from DATA.TRAIN_ORIGINAL_IMAGES_DIR (or a "
                              "DeviceImageArena passed as train_dataset), not from a dataset of crops")
         sampler = DS(arena, world, rank, shuffle=True) if world > 1 else None
+        degradation = Degradation.from_config(config)
         loader = DeviceCropLoader(arena, config.DATA.BATCH_SIZE, sampler, config.DATA.RANDOM_CROP, config.DATA.AUGMENT,
-                                  config.DATA.SEED)
+                                  config.DATA.SEED, degradation)
+        if degradation is not None and rank == 0:
+            announce_degradation(config, degradation)
         loader.set_epoch(config.EXP.START_EPOCH)
         return loader, sampler
     if train_dataset is not None:

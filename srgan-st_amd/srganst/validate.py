@@ -8,7 +8,11 @@ With config.DATA.VALIDATE_TILE = T > 0 (or tile=T, or --tile T) the generator ru
 the exact halo): test images of any size, the whole-image forward's result.
 With config.DATA.VALIDATE_LR (or with_lr=True, or --lr-consistency) every image also gets its LR consistency (metrics.lr_consistency:
 the generator's output, clamped and downscaled again by the kernel that made the LR input, against that LR input) as an ``LR-PSNR``
-column: the quantity the ``BackProjection`` criterion optimises."""
+column: the quantity the ``BackProjection`` criterion optimises.
+With config.DATA.VALIDATE_DEGRADE = (sigma1, sigma2, theta_deg, noise) (or degrade=(...), or --degrade s1,s2,theta,noise) the
+generator's input is device_data.degrade(gt) with these fixed blur and noise parameters (key = the image's index) instead of the LR
+file: the test set under the degradation DATA.DEGRADE trains on.  Either validation path, with or without VALIDATE_TILE; the printed
+line and _metrics.txt name the parameters."""
 from __future__ import annotations
 
 import argparse
@@ -62,7 +66,28 @@ def _lr_scale(output, lr_img):
     return int(round(output.shape[2] / lr_img.shape[2]))
 
 
-def _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params=None, with_lr=False):
+def _degrade_params(config, degrade):
+    """None, or (sigma1, sigma2, theta_deg, noise) as four floats: the argument, else config.DATA.VALIDATE_DEGRADE."""
+    if degrade is None:
+        degrade = config.DATA.get("VALIDATE_DEGRADE", None)
+    if not degrade:
+        return None
+    degrade = tuple(float(v) for v in degrade)
+    if len(degrade) != 4:
+        raise ValueError(f"VALIDATE_DEGRADE: expected (sigma1, sigma2, theta_deg, noise), got {degrade}")
+    return degrade
+
+
+def _degraded_input(hr_img, idx, config, degrade):
+    """The generator's input under VALIDATE_DEGRADE: degrade(hr) with the fixed parameters and key = the image's index."""
+    from .device_data import Degradation
+    from .device_data import degrade as degrade_op
+    ksize = int(config.DATA.get("DEGRADE_BLUR_KSIZE", 21))
+    deg = Degradation.fixed(*degrade, key=idx, ksize=ksize).draw(1).to(hr_img.device)
+    return degrade_op(hr_img.to(torch.float32), deg, int(config.DATA.UPSCALE_FACTOR), ksize)
+
+
+def _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params=None, with_lr=False, degrade=None):
     """The per-image loop of _validate with everything on the device: generator forward -> sst_image_metrics into row idx of one
     [N,2] result buffer, ONE device-to-host copy after the loop.  Nothing syncs per image unless save_images is set (the uint8
     images tensor2img would make then cross per image and are written by _save_png).  st_params: also st_distance(output, hr) per
@@ -76,6 +101,8 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
         for idx, (hr_img, lr_img) in enumerate(val_loader):
             lr_img = lr_img.to(config.DEVICE, non_blocking=True)
             hr_img = hr_img.to(config.DEVICE, non_blocking=True)
+            if degrade:
+                lr_img = _degraded_input(hr_img, idx, config, degrade)
             output = generator(lr_img)
             row = results[idx:idx + 1]
             if save_images:
@@ -96,8 +123,10 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
 
 
 def _validate(generator, val_loader, config, save_images=False, concat_with_gt=False, save_metrics=False, on_device=None,
-              with_st=None, tile=None, with_lr=None):
-    """on_device: None = config.DATA.VALIDATE_ON_DEVICE; True = metrics by the HIP kernel, one host copy per pass
+              with_st=None, tile=None, with_lr=None, degrade=None):
+    """degrade: None = config.DATA.VALIDATE_DEGRADE; (sigma1, sigma2, theta_deg, noise) = the generator's input is degrade(hr)
+    (_degraded_input) instead of the loader's LR image, and the printed line and _metrics.txt start by saying so.
+    on_device: None = config.DATA.VALIDATE_ON_DEVICE; True = metrics by the HIP kernel, one host copy per pass
     (_metrics_on_device); False = the host loop below.  Same averages, same printed line, same _metrics.txt either way.
     with_st: None = config.DATA.VALIDATE_ST; True = every image also gets st.st_distance(output, hr) with the configured ``ST``
     criterion's (sigma, rho, normalize), _metrics.txt and the printed line gain an ``ST:`` column and the return value becomes
@@ -118,15 +147,21 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
     st_params = _st_params(config) if with_st else None
     if with_lr is None:
         with_lr = bool(config.DATA.get("VALIDATE_LR", False))
+    degrade = _degrade_params(config, degrade)
+    deg_head = ""
+    if degrade:
+        deg_head = "LR = degrade(GT): sigma {:g} / {:g}, theta {:g} deg, noise {:g} | ".format(*degrade)
     file = None
     if save_metrics:
         path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
         os.makedirs(path, exist_ok=True)
         file = open(os.path.join(path, "_metrics.txt"), mode="w")
+        if degrade:
+            file.write(deg_head + "\n")
     all_psnr, all_ssim, all_st, all_lr = [], [], [], []
     if on_device:
         all_psnr, all_ssim, all_st, all_lr = _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params,
-                                                                with_lr)
+                                                                with_lr, degrade)
         if file:
             for idx, (psnr, ssim) in enumerate(zip(all_psnr, all_ssim)):
                 st_col = f" | ST: {all_st[idx]:.4f}" if with_st else ""
@@ -137,6 +172,8 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
             for idx, (hr_img, lr_img) in enumerate(val_loader):
                 lr_img = lr_img.to(config.DEVICE)
                 hr_img = hr_img.to(config.DEVICE)
+                if degrade:
+                    lr_img = _degraded_input(hr_img, idx, config, degrade)
                 output = generator(lr_img)
                 if save_images:
                     path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
@@ -159,7 +196,7 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
                     file.write(f"{idx}.png | PSNR: {psnr:.2f} | SSIM: {ssim:.4f}{st_col}{lr_col}\n")
     avg_psnr = sum(all_psnr) / len(all_psnr)
     avg_ssim = sum(all_ssim) / len(all_ssim)
-    out = (f"[Test] | PSNR: {avg_psnr:.2f} ± {confidence_interval(all_psnr):.2f} | "
+    out = (f"[Test] | {deg_head}PSNR: {avg_psnr:.2f} ± {confidence_interval(all_psnr):.2f} | "
            f"SSIM: {avg_ssim:.4f} ± {confidence_interval(all_ssim):.4f} | ")
     if with_st:
         avg_st = sum(all_st) / len(all_st)
@@ -176,7 +213,7 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
 
 
 def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_gt: bool = False, dataset=None, on_device=None,
-         with_st=None, tile=None, with_lr=None):
+         with_st=None, tile=None, with_lr=None, degrade=None):
     if not g_path:                # the averaged generator's best when the run kept one (SOLVER.G_EMA_DECAY), else the last iterate's
         g_path = f"results/{config.EXP.NAME}/g_ema_best.pth"
         if not os.path.exists(g_path):
@@ -192,7 +229,7 @@ def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_
         generator = load_state_dict(generator, torch.load(g_path, map_location=config.DEVICE, weights_only=True))
         generator.eval()
     return _validate(generator, loader, config, save_images=save_images, concat_with_gt=concat_w_gt, save_metrics=True,
-                     on_device=on_device, with_st=with_st, tile=tile, with_lr=with_lr)
+                     on_device=on_device, with_st=with_st, tile=tile, with_lr=with_lr, degrade=degrade)
 
 
 if __name__ == "__main__":
@@ -205,6 +242,8 @@ if __name__ == "__main__":
     parser.add_argument("--st", action="store_true", help="also the structure-tensor distance per image (DATA.VALIDATE_ST)")
     parser.add_argument("--tile", type=int, default=None, help="run the generator tiled, windows of this many LR pixels (DATA.VALIDATE_TILE)")
     parser.add_argument("--lr-consistency", action="store_true", help="also the LR-PSNR of the re-downscaled output per image (DATA.VALIDATE_LR)")
+    parser.add_argument("--degrade", type=str, default=None, metavar="S1,S2,THETA,NOISE",
+                        help="feed the generator degrade(gt) with this fixed blur and noise instead of the LR files (DATA.VALIDATE_DEGRADE)")
     a = parser.parse_args()
     cfg = Config()
     if a.name:
@@ -214,4 +253,5 @@ if __name__ == "__main__":
         cfg.DATA.TEST_GT_IMAGES_DIR = f"/work3/{cfg.EXP.USER}/data/{a.test_set}/GTmod12"
         cfg.DATA.TEST_LR_IMAGES_DIR = f"/work3/{cfg.EXP.USER}/data/{a.test_set}/LRbicx4"
     test(cfg, save_images=not a.no_images, g_path=a.g_path, on_device=True if a.on_device else None,
-         with_st=True if a.st else None, tile=a.tile, with_lr=True if a.lr_consistency else None)
+         with_st=True if a.st else None, tile=a.tile, with_lr=True if a.lr_consistency else None,
+         degrade=tuple(float(v) for v in a.degrade.split(",")) if a.degrade else None)

@@ -23,6 +23,13 @@ difference between two legs).  Prints one JSON line.
         rocprofv3 --kernel-trace --stats -d OUT -o gather -- python tools/time_loader.py --gather-only
     python tools/time_loader.py --gather-only --crops grid|odd_x0|transposed [--iters N]
         # the same trace with N sst_gather_crops launches beside N sst_gather_batch launches on the same tiles, in one process
+    python tools/time_loader.py degrade [--launches L] [--replays R] [--repeat N] [--parent-lib PATH]
+        # the degradation stage (DATA.DEGRADE), B = 16, S = 96, x4, us per batch: each leg is a hipGraph of L launches on L different
+        # batches (random windows, all transforms), replayed R times between two device events; the legs run round robin N times and
+        # every repeat is reported.  Legs: the plain sst_gather_crops (and, with --parent-lib, the same launch through another build of
+        # the library, e.g. the parent commit's, in the same process); sst_gather_crops_degraded at K = 7 and 21 with and without
+        # noise; and the same degradation as fp32 torch ops on the gathered gt (reflect pad, per-sample grouped conv2d with
+        # precomputed weights, Bicubic("cuda"), randn, clamp, round) - the yardstick
 """
 import argparse
 import json
@@ -205,7 +212,108 @@ def gather_crops_only(iters, case):
     print(json.dumps({"gather_launches_each": iters, "crops_case": case, "batch": B, "hr": HR, "arena_bytes": arena.arena.numel()}))
 
 
+def degrade_mode(launches, replays, repeat, parent_lib):
+    import ctypes
+    from srganst import _abi
+    from srganst.bicubic import Bicubic
+    from srganst.device_data import Degradation, DeviceImageArena, degrade_rows
+    g = torch.Generator().manual_seed(0)
+    imgs = [torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8) for h, w in WHOLE_SIZES * 2]
+    arena = DeviceImageArena.from_arrays(imgs, HR, HR, UP, "cuda")
+    n = launches * B
+    tiles = torch.from_numpy(arena.tiles)[torch.randperm(len(arena), generator=g)[:n]]
+    room = torch.from_numpy(arena.table_host[tiles[:, 0].numpy(), 1:3] - HR + 1)
+    desc = torch.zeros(n, 4, dtype=torch.int32)
+    desc[:, 0] = tiles[:, 0]
+    desc[:, 1:3] = (torch.randint(0, 1 << 30, (n, 2), generator=g) % room).to(torch.int32)
+    desc[:, 3] = torch.randint(0, 8, (n,), generator=g).to(torch.int32)
+    arena.check_desc(desc.numpy())
+    desc = desc.cuda()
+    draw = lambda noise_prob: Degradation(noise_prob=noise_prob).draw(n, torch.Generator().manual_seed(1)).cuda()
+    deg_noise, deg_quiet = draw(1.0), draw(0.0)
+    gt, lr = torch.empty(B, 3, HR, HR, device="cuda"), torch.empty(B, 3, HR // UP, HR // UP, device="cuda")
+    bic = Bicubic("cuda")
+
+    def torch_weights(deg, K):          # per-sample normalised kernels [n * 3, 1, K, K], made beforehand: not part of the timed work
+        q = deg[:, :3].contiguous().view(torch.float32).double()
+        d = torch.arange(-(K // 2), K // 2 + 1, device="cuda", dtype=torch.float64)
+        dy, dx = d[None, :, None], d[None, None, :]
+        w = torch.exp(-(q[:, 0, None, None] * dx * dx + q[:, 1, None, None] * dx * dy + q[:, 2, None, None] * dy * dy))
+        w = (w / w.sum((1, 2), keepdim=True)).float()
+        return w.repeat_interleave(3, 0)[:, None].contiguous()
+
+    def torch_leg(K):
+        w, p = torch_weights(deg_noise, K), K // 2
+        sn = deg_noise[:, 3].contiguous().view(torch.float32)
+
+        def run(k):
+            arena.crops(desc[k * B:(k + 1) * B], gt, lr)
+            x = torch.nn.functional.pad(gt, (p, p, p, p), mode="reflect").reshape(1, B * 3, HR + 2 * p, HR + 2 * p)
+            x = torch.nn.functional.conv2d(x, w[k * B * 3:(k + 1) * B * 3], groups=B * 3).reshape(B, 3, HR, HR)
+            y = bic(x, scale=1.0 / UP) + sn[k * B:(k + 1) * B, None, None, None] * torch.randn(B, 3, HR // UP, HR // UP, device="cuda")
+            lr.copy_(torch.round(y.clamp(0, 1) * 255) / 255)
+        return run
+
+    def crops_leg(deg, K):
+        return lambda k: arena.crops(desc[k * B:(k + 1) * B], gt, lr, deg=deg[k * B:(k + 1) * B], ksize=K)
+
+    legs = {"gather_crops": lambda k: arena.crops(desc[k * B:(k + 1) * B], gt, lr)}
+    if parent_lib:
+        other = ctypes.CDLL(parent_lib)
+        other.sst_gather_crops.restype, other.sst_gather_crops.argtypes = _abi.SIGNATURES["sst_gather_crops"]
+        wy, iy, wx, ix = arena._bicubic.tables_i32(HR, HR, 1.0 / UP, arena.device)
+        o = HR // UP
+
+        def parent(k):
+            rc = other.sst_gather_crops(arena.arena.data_ptr(), arena.arena.numel(), arena.table.data_ptr(), arena.n_images,
+                                        desc[k * B:(k + 1) * B].data_ptr(), B, HR, arena.lut.data_ptr(), gt.data_ptr(), lr.data_ptr(),
+                                        wy.data_ptr(), iy.data_ptr(), wx.data_ptr(), ix.data_ptr(), o, o, wy.shape[1], wx.shape[1],
+                                        arena.span(True, True), _abi.stream_ptr())
+            assert rc == 0, rc
+        legs["gather_crops_parent_lib"] = parent
+    for K in (7, 21):
+        legs[f"degraded_k{K}"] = crops_leg(deg_quiet, K)
+        legs[f"degraded_k{K}_noise"] = crops_leg(deg_noise, K)
+    for K in (7, 21):
+        legs[f"torch_ops_k{K}_noise"] = torch_leg(K)
+
+    graphs = {}
+    for name, run in legs.items():
+        for k in range(min(3, launches)):               # warm up: tables, code objects, the allocator's pool
+            run(k)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for k in range(launches):
+                run(k)
+        gr.replay()
+        graphs[name] = gr
+    torch.cuda.synchronize()
+    out = {"mode": "degrade", "batch": B, "hr": HR, "scale": UP, "launches_per_graph": launches, "replays": replays, "repeat": repeat,
+           "us_per_batch": {name: [] for name in legs}}
+    for _ in range(repeat):
+        for name, gr in graphs.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(replays):
+                gr.replay()
+            t1.record()
+            torch.cuda.synchronize()
+            out["us_per_batch"][name].append(round(t0.elapsed_time(t1) * 1e3 / (replays * launches), 2))
+    out["median_us_per_batch"] = {name: sorted(v)[len(v) // 2] for name, v in out["us_per_batch"].items()}
+    print(json.dumps(out))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "degrade":
+        ap = argparse.ArgumentParser()
+        ap.add_argument("mode")
+        ap.add_argument("--launches", type=int, default=32)
+        ap.add_argument("--replays", type=int, default=50)
+        ap.add_argument("--repeat", type=int, default=5)
+        ap.add_argument("--parent-lib", default="", help="another build of libsrganst.so whose sst_gather_crops is timed beside this one's")
+        a = ap.parse_args()
+        return degrade_mode(a.launches, a.replays, a.repeat, a.parent_lib)
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=8192)
     ap.add_argument("--steps", type=int, default=300)
