@@ -515,6 +515,18 @@ int sst_gather_crops_degraded(const uint8_t* arena, int64_t arena_bytes, const i
 int sst_degrade(const float* x, const int* deg, int B, int H, int W, int K, int quantise, float* lr, const float* wy, const int* iy,
                 const float* wx, const int* ix, int oh, int ow, int Ty, int Tx, void* stream);
 int sst_degrade_tile_cols(void);
+/* ---- the JPEG stage of the degradation (device_data.py: jpeg / degrade(jpeg_chroma=...); csrc/jpeg.hip): a
+ * baseline JPEG round trip in int32 arithmetic at every step, in place on lr fp32 [B,3,h,w] (h, w in 1..8192), after the stage above
+ * has put it on the 1/255 grid.  Per sample Q = word 6 of its deg row (deg as above): 0 keeps the sample's bits, a Q outside 0..100
+ * makes the sample NaN, else p = (int)rintf(255 clamp01(v)), 16-bit fixed-point YCbCr, MCUs of 8 x 8 (chroma = 0: 444) or 16 x 16
+ * (chroma = 1: 420, chroma averaged 2 x 2 with rounding and replicated 2 x 2 on the way back) with edge replication, the Annex K
+ * tables under libjpeg's quality rule, an 8-point DCT with T = rint(8192 C) and fixed shifts, n = sign(F) ((|F| + q 32768) / (q 65536)),
+ * the inverse, 16-bit fixed-point RGB, out = (float)p / 255.f.  An MCU that holds a non-finite element comes out NaN in all three
+ * channels.  The result does not depend on the batch position or on how the image is cut into workgroups.  One launch, no
+ * allocation, no sync (capturable).
+ * sst_jpeg_tables: the luminance then the chrominance table of a quality in 1..100, row-major, into out128 (host memory). */
+int sst_jpeg(float* lr, const int* deg, int B, int h, int w, int chroma, void* stream);
+int sst_jpeg_tables(int quality, int* out128);
 /* Validation metrics of validate.image_metrics on the device (metrics.py), rounding for rounding: sr, hr fp32 NCHW [B,3,H,W] RGB;
  * out fp64 [B,2] = (MSE of the Y channel on the 0..255 scale over all H*W pixels, mean of the SSIM map over its (H-10) x (W-10)
  * valid region); sr_u8 / hr_u8: uint8 [B,H,W,3] BGR = tensor2img of each image (either may be null).  workspace:

@@ -107,9 +107,18 @@ class Config:
         self.DATA.DEGRADE_BLUR_KSIZE = 21
         self.DATA.DEGRADE_NOISE_SIGMA = (0.0, 25.0)
         self.DATA.DEGRADE_NOISE_PROB = 1.0
+        # with DEGRADE: with probability JPEG_PROB a sample's degraded LR also goes through a JPEG round trip at a quality that is a
+        # uniform integer in the closed range JPEG_QUALITY, chroma '420' or '444' (a second launch, sst_jpeg: an all-integer codec,
+        # DESIGN.md section 22).  Drawn after the blur and noise parameters, which stay the ones drawn without it.  0: no second launch
+        self.DATA.DEGRADE_JPEG_PROB = 0.0
+        self.DATA.DEGRADE_JPEG_QUALITY = (30, 95)
+        self.DATA.DEGRADE_JPEG_CHROMA = "420"
         # (sigma1, sigma2, theta_deg, noise): validation feeds the generator degrade(gt) with these fixed parameters (key = the image's
         # index, window DEGRADE_BLUR_KSIZE) instead of the LR file; the printed line and _metrics.txt say so.  None: the LR files
         self.DATA.VALIDATE_DEGRADE = None
+        # Q in 1..100: validation feeds the generator the JPEG round trip (chroma DEGRADE_JPEG_CHROMA) of its input at this quality -
+        # of degrade(gt) with VALIDATE_DEGRADE, else of the plain bicubic LR made from gt; the printed line says so.  None: off
+        self.DATA.VALIDATE_DEGRADE_JPEG = None
 
         self.MODEL = dotdict()
         self.MODEL.G_CONTINUE_FROM_WARMUP = False

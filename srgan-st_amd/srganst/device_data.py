@@ -11,6 +11,8 @@ of the eight dihedral transforms to it: DeviceCropLoader walks the tile grid dat
 with DATA.RANDOM_CROP / DATA.AUGMENT, draws the window and the transform anew every epoch.
 With DATA.DEGRADE that launch (sst_gather_crops_degraded) also blurs each sample with its own Gaussian kernel before the bicubic and
 adds Gaussian noise after it (Degradation, the classical blind-SR model); degrade() is that stage alone on any fp32 batch.
+With a JPEG quality in the sample's deg row (Degradation(jpeg_prob=...), DATA.DEGRADE_JPEG_PROB) a second launch (sst_jpeg) takes
+the LR batch through an all-integer JPEG round trip in place; jpeg() is that stage alone.
 """
 from __future__ import annotations
 
@@ -300,12 +302,21 @@ DEGRADE_KSIZES = tuple(range(3, 22, 2))
 _DEGRADE_STREAM = 0x6A09E667F3BCC908      # keeps the loader's degradation generator apart from its window / transform generator
 
 
-def degrade_rows(sigma1, sigma2, theta, noise255, keys) -> np.ndarray:
+JPEG_CHROMA = {"444": 0, "420": 1}         # sst_jpeg's chroma argument
+
+
+def _chroma(mode, who: str) -> int:
+    if mode not in JPEG_CHROMA:
+        raise ValueError(f"{who}: jpeg_chroma must be '444' or '420', got {mode!r}")
+    return JPEG_CHROMA[mode]
+
+
+def degrade_rows(sigma1, sigma2, theta, noise255, keys, jpeg=None) -> np.ndarray:
     """The deg rows of the kernels, int32 [n, 8], from per-sample arrays: the Gaussian's standard deviations along its two axes
     (pixels; <= 0 in either: no blur, the row gets the sentinel qa = -1), the angle of the first axis against x = columns (radians; y
     = rows), the noise's standard deviation in 0..255 units and the Philox key [n, 2].  With [[A, B], [B, C]] the inverse of
     R(theta) diag(sigma1^2, sigma2^2) R(theta)^T the row holds (A/2, B, C/2), computed in fp64 and rounded once to fp32, then
-    noise255 / 255, the key and two zero words."""
+    noise255 / 255, the key, the JPEG quality `jpeg` (per sample, 0..100; 0 or None: no JPEG stage) and a zero word."""
     s1, s2, th, nz = (np.atleast_1d(np.asarray(a, np.float64)) for a in (sigma1, sigma2, theta, noise255))
     n = len(s1)
     keys = np.asarray(keys, np.int64).reshape(n, 2) & 0xFFFFFFFF
@@ -317,6 +328,8 @@ def degrade_rows(sigma1, sigma2, theta, noise255, keys) -> np.ndarray:
     rows = np.zeros((n, 8), np.int32)
     rows[:, :4] = q.astype(np.float32).view(np.int32)
     rows[:, 4:6] = keys.astype(np.uint32).view(np.int32)
+    if jpeg is not None:
+        rows[:, 6] = np.broadcast_to(np.asarray(jpeg, np.int64), (n,))
     return rows
 
 
@@ -325,10 +338,13 @@ class Degradation:
     anisotropic Gaussian on a ksize x ksize window, n Gaussian noise.  draw(n, generator) -> int32 [n, 8] on the host, one deg row
     per sample: sigma1, sigma2 uniform in blur_sigma (equal when aniso is off), theta uniform in [0, pi), the no-blur sentinel with
     probability 1 - blur_prob; the noise's standard deviation uniform in noise_sigma (0..255 units), 0 with probability
-    1 - noise_prob; two random key words.  Degradation.fixed(...) draws the same row every time (validation, tests)."""
+    1 - noise_prob; two random key words.  With jpeg_prob > 0 a sample also gets, with that probability, a JPEG quality that is a
+    uniform integer in the closed range jpeg_quality (word 6 of its row; sst_jpeg, chroma mode jpeg_chroma): these draws are made
+    after all the others, so the other words are the ones drawn without them.  Degradation.fixed(...) draws the same row every time
+    (validation, tests)."""
 
     def __init__(self, blur_sigma=(0.2, 4.0), aniso: bool = True, blur_prob: float = 1.0, noise_sigma=(0.0, 25.0),
-                 noise_prob: float = 1.0, ksize: int = 21):
+                 noise_prob: float = 1.0, ksize: int = 21, jpeg_quality=(30, 95), jpeg_prob: float = 0.0, jpeg_chroma: str = "420"):
         self.blur_sigma, self.noise_sigma = (float(blur_sigma[0]), float(blur_sigma[1])), (float(noise_sigma[0]), float(noise_sigma[1]))
         self.aniso, self.blur_prob, self.noise_prob, self.ksize = bool(aniso), float(blur_prob), float(noise_prob), int(ksize)
         self._fixed = None
@@ -340,14 +356,30 @@ class Degradation:
             raise ValueError(f"Degradation: blur_prob {blur_prob} and noise_prob {noise_prob} must be in [0, 1]")
         if self.ksize not in DEGRADE_KSIZES:
             raise ValueError(f"Degradation: ksize {ksize} must be odd and in 3..21")
+        self.jpeg_quality, self.jpeg_prob, self.jpeg_chroma = (int(jpeg_quality[0]), int(jpeg_quality[1])), float(jpeg_prob), jpeg_chroma
+        self._fixed_jpeg = 0
+        if not (1 <= self.jpeg_quality[0] <= self.jpeg_quality[1] <= 100 and tuple(jpeg_quality) == self.jpeg_quality):
+            raise ValueError(f"Degradation: jpeg_quality {jpeg_quality} must be integers 1 <= lo <= hi <= 100")
+        if not 0 <= self.jpeg_prob <= 1:
+            raise ValueError(f"Degradation: jpeg_prob {jpeg_prob} must be in [0, 1]")
+        _chroma(jpeg_chroma, "Degradation")
+
+    @property
+    def has_jpeg(self) -> bool:
+        """True when a row this draws can hold a JPEG quality: the loader then issues the sst_jpeg launch after the gather."""
+        return self._fixed_jpeg > 0 if self._fixed else self.jpeg_prob > 0
 
     @classmethod
-    def fixed(cls, sigma1: float, sigma2: float, theta_deg: float, noise: float, key=0, ksize: int = 21) -> "Degradation":
+    def fixed(cls, sigma1: float, sigma2: float, theta_deg: float, noise: float, key=0, ksize: int = 21, jpeg: int = 0,
+              jpeg_chroma: str = "420") -> "Degradation":
         """Every sample gets these parameters: the two standard deviations (0: no blur), the angle in degrees, the noise's standard
-        deviation in 0..255 units and the key (an int: the low and high 32 bits; or a pair of words)."""
+        deviation in 0..255 units, the key (an int: the low and high 32 bits; or a pair of words) and the JPEG quality (0: none)."""
         if sigma1 < 0 or sigma2 < 0 or noise < 0 or (sigma1 > 0) != (sigma2 > 0):
             raise ValueError(f"Degradation.fixed: sigma ({sigma1}, {sigma2}) must be both positive or both 0, noise {noise} >= 0")
-        d = cls(ksize=ksize)
+        if int(jpeg) != jpeg or not 0 <= jpeg <= 100:
+            raise ValueError(f"Degradation.fixed: the JPEG quality {jpeg!r} must be an integer in 0..100 (0: none)")
+        d = cls(ksize=ksize, jpeg_chroma=jpeg_chroma)
+        d._fixed_jpeg = int(jpeg)
         k = (int(key) & 0xFFFFFFFF, (int(key) >> 32) & 0xFFFFFFFF) if isinstance(key, (int, np.integer)) else (int(key[0]), int(key[1]))
         d._fixed = (float(sigma1), float(sigma2), float(theta_deg), float(noise), k)
         return d
@@ -355,14 +387,16 @@ class Degradation:
     def __repr__(self) -> str:
         if self._fixed:
             s1, s2, th, nz, k = self._fixed
-            return f"Degradation.fixed(sigma1={s1:g}, sigma2={s2:g}, theta_deg={th:g}, noise={nz:g}, key={k}, ksize={self.ksize})"
+            jp = f", jpeg={self._fixed_jpeg}, jpeg_chroma={self.jpeg_chroma!r}" if self._fixed_jpeg else ""
+            return f"Degradation.fixed(sigma1={s1:g}, sigma2={s2:g}, theta_deg={th:g}, noise={nz:g}, key={k}, ksize={self.ksize}{jp})"
+        jp = f", jpeg_quality={self.jpeg_quality}, jpeg_prob={self.jpeg_prob:g}, jpeg_chroma={self.jpeg_chroma!r}" if self.jpeg_prob > 0 else ""
         return (f"Degradation(blur_sigma={self.blur_sigma}, aniso={self.aniso}, blur_prob={self.blur_prob:g}, "
-                f"noise_sigma={self.noise_sigma}, noise_prob={self.noise_prob:g}, ksize={self.ksize})")
+                f"noise_sigma={self.noise_sigma}, noise_prob={self.noise_prob:g}, ksize={self.ksize}{jp})")
 
     def draw(self, n: int, generator: torch.Generator | None = None) -> Tensor:
         if self._fixed:
             s1, s2, th, nz, k = self._fixed
-            return torch.from_numpy(degrade_rows([s1] * n, [s2] * n, [np.deg2rad(th)] * n, [nz] * n, [k] * n))
+            return torch.from_numpy(degrade_rows([s1] * n, [s2] * n, [np.deg2rad(th)] * n, [nz] * n, [k] * n, self._fixed_jpeg))
         u = torch.rand(n, 6, generator=generator, dtype=torch.float64).numpy()
         keys = torch.randint(0, 1 << 32, (n, 2), generator=generator, dtype=torch.int64).numpy()
         (b0, b1), (n0, n1) = self.blur_sigma, self.noise_sigma
@@ -370,7 +404,12 @@ class Degradation:
         s2 = b0 + (b1 - b0) * u[:, 1] if self.aniso else s1
         blur = u[:, 3] < self.blur_prob
         nz = np.where(u[:, 5] < self.noise_prob, n0 + (n1 - n0) * u[:, 4], 0.0)
-        return torch.from_numpy(degrade_rows(np.where(blur, s1, 0.0), np.where(blur, s2, 0.0), np.pi * u[:, 2], nz, keys))
+        jpeg = None
+        if self.jpeg_prob > 0:                              # drawn last: every word above is the one drawn without the JPEG stage
+            on = torch.rand(n, generator=generator, dtype=torch.float64).numpy() < self.jpeg_prob
+            q = torch.randint(self.jpeg_quality[0], self.jpeg_quality[1] + 1, (n,), generator=generator, dtype=torch.int64).numpy()
+            jpeg = np.where(on, q, 0)
+        return torch.from_numpy(degrade_rows(np.where(blur, s1, 0.0), np.where(blur, s2, 0.0), np.pi * u[:, 2], nz, keys, jpeg))
 
     @classmethod
     def from_config(cls, config) -> "Degradation | None":
@@ -379,7 +418,8 @@ class Degradation:
         if not data.get("DEGRADE", False):
             return None
         return cls(data.DEGRADE_BLUR_SIGMA, data.DEGRADE_BLUR_ANISO, data.DEGRADE_BLUR_PROB, data.DEGRADE_NOISE_SIGMA,
-                   data.DEGRADE_NOISE_PROB, data.DEGRADE_BLUR_KSIZE)
+                   data.DEGRADE_NOISE_PROB, data.DEGRADE_BLUR_KSIZE, tuple(data.get("DEGRADE_JPEG_QUALITY", (30, 95))),
+                   data.get("DEGRADE_JPEG_PROB", 0.0), data.get("DEGRADE_JPEG_CHROMA", "420"))
 
 
 def _check_deg(deg: Tensor, B: int, device, who: str) -> None:
@@ -390,11 +430,36 @@ def _check_deg(deg: Tensor, B: int, device, who: str) -> None:
 _degrade_bicubic = {}
 
 
-def degrade(x: Tensor, deg: Tensor, scale: int, ksize: int = 21, quantise: bool = True) -> Tensor:
+def jpeg(lr: Tensor, deg: Tensor, chroma: str = "420", out: Tensor | None = None) -> Tensor:
+    """ONE sst_jpeg launch on the current stream: the JPEG stage alone on an fp32 batch lr [B,3,h,w] (h, w <= 8192) with the qualities
+    in word 6 of the rows deg int32 [B,8] (0: the sample keeps its bits) -> a new tensor, or `out` (contiguous fp32 of lr's shape; out
+    = lr runs in place).  An all-integer codec: the result is the same bits in every run and batch position."""
+    c = _chroma(chroma, "jpeg")
+    if lr.dtype != torch.float32 or lr.dim() != 4 or lr.shape[1] != 3 or not lr.is_cuda:
+        raise ValueError(f"jpeg: lr must be fp32 [B, 3, h, w] on a ROCm device, got {lr.dtype} {tuple(lr.shape)} on {lr.device}")
+    B, _, h, w = lr.shape
+    _check_deg(deg, B, lr.device, "jpeg")
+    if out is None:
+        out = lr.clone(memory_format=torch.contiguous_format)
+    else:
+        if out.dtype != torch.float32 or tuple(out.shape) != tuple(lr.shape) or not out.is_contiguous() or out.device != lr.device:
+            raise ValueError(f"jpeg: out must be contiguous fp32 {tuple(lr.shape)} on {lr.device}, got {out.dtype} {tuple(out.shape)}")
+        if out.data_ptr() != lr.data_ptr():
+            out.copy_(lr)
+    _abi.check(_abi.lib().sst_jpeg(_abi.ptr(out), _abi.ptr(deg), B, h, w, c, _abi.stream_ptr()), "sst_jpeg")
+    return out
+
+
+def degrade(x: Tensor, deg: Tensor, scale: int, ksize: int = 21, quantise: bool = True, jpeg_chroma: str | None = None) -> Tensor:
     """ONE sst_degrade launch on the current stream: the degradation stage on an fp32 batch x [B,3,H,W] of any size (H, W >= scale,
     ksize // 2 < min(H, W)) with per-sample rows deg int32 [B,8] (Degradation.draw / degrade_rows) -> lr [B,3,H//scale,W//scale].
     The stand-alone form of DeviceImageArena.crops(desc, deg=...), whose lr it reproduces from its gt bit for bit.  quantise=False
-    (tests and tools) returns the unclamped, unrounded values."""
+    (tests and tools) returns the unclamped, unrounded values.  jpeg_chroma ('444' / '420'): a second launch (sst_jpeg) takes lr
+    through the JPEG stage in place, at the qualities in word 6 of the rows; it needs the quantised values."""
+    if jpeg_chroma is not None:
+        _chroma(jpeg_chroma, "degrade")
+        if not quantise:
+            raise ValueError("degrade: the JPEG stage works on the 1/255 grid; jpeg_chroma needs quantise=True")
     if scale not in (2, 4, 8):
         raise ValueError(f"degrade: scale must be 2, 4 or 8, got {scale!r}")
     if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_cuda:
@@ -411,6 +476,8 @@ def degrade(x: Tensor, deg: Tensor, scale: int, ksize: int = 21, quantise: bool 
     _abi.check(_abi.lib().sst_degrade(_abi.ptr(x), _abi.ptr(deg), B, H, W, int(ksize), int(bool(quantise)), _abi.ptr(lr), _abi.ptr(wy),
                                       _abi.ptr(iy), _abi.ptr(wx), _abi.ptr(ix), oh, ow, wy.shape[1], wx.shape[1],
                                       _abi.stream_ptr()), "sst_degrade")
+    if jpeg_chroma is not None:
+        jpeg(lr, deg, jpeg_chroma, out=lr)
     return lr
 
 
@@ -552,12 +619,18 @@ class DeviceImageArena:
         return self._span[key]
 
     def crops(self, desc: Tensor, gt_out: Tensor | None = None, lr_out: Tensor | None = None, with_gt: bool = True,
-              with_lr: bool = True, deg: Tensor | None = None, ksize: int | None = None, quantise: bool = True):
+              with_lr: bool = True, deg: Tensor | None = None, ksize: int | None = None, quantise: bool = True,
+              jpeg_chroma: str | None = None):
         """ONE sst_gather_crops launch on the current stream: gt [B,3,S,S] = the windows desc names, transformed, on the 1/255
         grid; lr [B,3,S/up,S/up] = their bicubic.  desc: int32 [B,4] on the arena's device (checked on the host by DeviceCropLoader /
         check_desc).  Writes into gt_out / lr_out when given; with_gt / with_lr = False skips that output (returned as None).
         deg: int32 [B,8] on the device (Degradation.draw) makes it ONE sst_gather_crops_degraded launch instead: the same gt, and lr
-        = degrade(gt, deg, upscale, ksize, quantise) bit for bit (blur, bicubic, noise, quantise); ksize defaults to 21."""
+        = degrade(gt, deg, upscale, ksize, quantise) bit for bit (blur, bicubic, noise, quantise); ksize defaults to 21.
+        jpeg_chroma ('444' / '420', with deg): a second launch, sst_jpeg on lr in place, as degrade(..., jpeg_chroma=) does."""
+        if jpeg_chroma is not None:
+            _chroma(jpeg_chroma, "DeviceImageArena.crops")
+            if deg is None or not quantise:
+                raise ValueError("DeviceImageArena.crops: jpeg_chroma needs deg (the qualities are word 6 of its rows) and quantise=True")
         if desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != 4 or desc.device != self.device:
             raise ValueError(f"DeviceImageArena.crops: desc must be int32 [B, 4] on {self.device}")
         B, S, o = desc.shape[0], self.crop, self.out
@@ -581,6 +654,8 @@ class DeviceImageArena:
                 _abi.ptr(gt), _abi.ptr(lr), _abi.ptr(wy), _abi.ptr(iy), _abi.ptr(wx), _abi.ptr(ix), o, o, Ty, Tx,
                 self.span(with_gt, True), _abi.ptr(deg), 21 if ksize is None else int(ksize), int(bool(quantise)),
                 _abi.stream_ptr()), "sst_gather_crops_degraded")
+            if jpeg_chroma is not None:
+                jpeg(lr, deg, jpeg_chroma, out=lr)
             return gt, lr
         _abi.check(_abi.lib().sst_gather_crops(_abi.ptr(self.arena), self.arena.numel(), _abi.ptr(self.table), self.n_images,
                                                _abi.ptr(desc), B, S, _abi.ptr(self.lut), _abi.ptr(gt), _abi.ptr(lr), _abi.ptr(wy),
@@ -601,7 +676,9 @@ class DeviceCropLoader:
     with every __iter__; set_epoch() sets it.
     degradation: every batch is one sst_gather_crops_degraded launch; the epoch's deg rows are drawn for ALL tiles as well, from a
     SECOND private generator (seed, epoch and a constant of its own), so a tile's degradation depends on neither world size nor rank
-    nor batch size either, the window and transform draws are the ones made without it, and resuming at an epoch reproduces it."""
+    nor batch size either, the window and transform draws are the ones made without it, and resuming at an epoch reproduces it.
+    A degradation that can draw a JPEG quality (Degradation.has_jpeg) adds one sst_jpeg launch per batch; any other leaves the
+    launches as they are."""
 
     def __init__(self, arena: DeviceImageArena, batch_size: int, sampler=None, random_crop: bool = False, augment: bool = False,
                  seed: int = 0, degradation: Degradation | None = None):
@@ -678,9 +755,10 @@ class DeviceCropLoader:
                 yield self.dset.crops(desc[k * B:(k + 1) * B], self._gt, self._lr)
             return
         deg = up(host_deg)                                               # once per epoch, next to desc
+        jpeg_chroma = self.degradation.jpeg_chroma if self.degradation.has_jpeg else None
         for k in range(len(self)):
             yield self.dset.crops(desc[k * B:(k + 1) * B], self._gt, self._lr, deg=deg[k * B:(k + 1) * B],
-                                  ksize=self.degradation.ksize)
+                                  ksize=self.degradation.ksize, jpeg_chroma=jpeg_chroma)
 
 
 def check_switches(config) -> None:
@@ -690,6 +768,9 @@ def check_switches(config) -> None:
         raise ValueError("DATA.DEGRADE needs DATA.ON_DEVICE_WHOLE_IMAGES = True: the per-sample blur and noise are made by the "
                          "whole-image gather (device_data.DeviceCropLoader, sst_gather_crops_degraded), neither the pre-cut crops "
                          "(DATA.ON_DEVICE) nor the host DataLoader have them")
+    if data.get("DEGRADE_JPEG_PROB", 0.0) > 0 and not data.get("DEGRADE", False):
+        raise ValueError("DATA.DEGRADE_JPEG_PROB needs DATA.DEGRADE = True: the JPEG stage follows the degraded gather and reads its "
+                         "quality from the same per-sample rows (set DEGRADE_BLUR_PROB = DEGRADE_NOISE_PROB = 0 for JPEG alone)")
     if (data.get("RANDOM_CROP", False) or data.get("AUGMENT", False)) and not data.get("ON_DEVICE_WHOLE_IMAGES", False):
         raise ValueError("DATA.RANDOM_CROP / DATA.AUGMENT need DATA.ON_DEVICE_WHOLE_IMAGES = True: the random window and the flips / "
                          "transposition are made by the whole-image gather (device_data.DeviceCropLoader), no other data path has them")
@@ -701,6 +782,9 @@ def announce_degradation(config, degradation: Degradation) -> None:
     import warnings
     from .loss import BackProjectionLoss
     print(f"[Data] DATA.DEGRADE: lr = quantise(clamp(bicubic(gt * k) + n)) per sample in the gather launch, {degradation!r}")
+    if degradation.has_jpeg:
+        print(f"[Data] DATA.DEGRADE: then lr = jpeg(lr) in a second launch (sst_jpeg, integer codec, chroma {degradation.jpeg_chroma})"
+              + ("" if degradation._fixed else f": quality uniform in {degradation.jpeg_quality} with probability {degradation.jpeg_prob:g}"))
     loss = config.MODEL.G_LOSS
     for where in ("CRITERIONS", "WARMUP_CRITERIONS"):
         for name, crit in loss.get(where, {}).items():

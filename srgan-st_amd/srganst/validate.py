@@ -12,7 +12,10 @@ column: the quantity the ``BackProjection`` criterion optimises.
 With config.DATA.VALIDATE_DEGRADE = (sigma1, sigma2, theta_deg, noise) (or degrade=(...), or --degrade s1,s2,theta,noise) the
 generator's input is device_data.degrade(gt) with these fixed blur and noise parameters (key = the image's index) instead of the LR
 file: the test set under the degradation DATA.DEGRADE trains on.  Either validation path, with or without VALIDATE_TILE; the printed
-line and _metrics.txt name the parameters."""
+line and _metrics.txt name the parameters.
+With config.DATA.VALIDATE_DEGRADE_JPEG = Q (or degrade_jpeg=Q, or --degrade-jpeg Q; 1..100) that input also goes through the JPEG
+stage (device_data.jpeg, chroma DATA.DEGRADE_JPEG_CHROMA) at quality Q; without VALIDATE_DEGRADE the input is then the JPEG round trip
+of the plain bicubic LR made from gt.  The printed line and _metrics.txt name the quality."""
 from __future__ import annotations
 
 import argparse
@@ -78,16 +81,31 @@ def _degrade_params(config, degrade):
     return degrade
 
 
-def _degraded_input(hr_img, idx, config, degrade):
-    """The generator's input under VALIDATE_DEGRADE: degrade(hr) with the fixed parameters and key = the image's index."""
+def _jpeg_param(config, degrade_jpeg):
+    """None, or the JPEG quality as an int in 1..100: the argument, else config.DATA.VALIDATE_DEGRADE_JPEG."""
+    if degrade_jpeg is None:
+        degrade_jpeg = config.DATA.get("VALIDATE_DEGRADE_JPEG", None)
+    if degrade_jpeg is None:
+        return None
+    if int(degrade_jpeg) != degrade_jpeg or not 1 <= degrade_jpeg <= 100:
+        raise ValueError(f"VALIDATE_DEGRADE_JPEG: expected a quality in 1..100, got {degrade_jpeg!r}")
+    return int(degrade_jpeg)
+
+
+def _degraded_input(hr_img, idx, config, degrade, jpeg=None):
+    """The generator's input under VALIDATE_DEGRADE / VALIDATE_DEGRADE_JPEG: degrade(hr) with the fixed parameters and key = the
+    image's index (without VALIDATE_DEGRADE: neither blur nor noise, the plain bicubic's bits), then the JPEG stage at quality jpeg."""
     from .device_data import Degradation
     from .device_data import degrade as degrade_op
     ksize = int(config.DATA.get("DEGRADE_BLUR_KSIZE", 21))
-    deg = Degradation.fixed(*degrade, key=idx, ksize=ksize).draw(1).to(hr_img.device)
-    return degrade_op(hr_img.to(torch.float32), deg, int(config.DATA.UPSCALE_FACTOR), ksize)
+    chroma = config.DATA.get("DEGRADE_JPEG_CHROMA", "420")
+    deg = Degradation.fixed(*(degrade or (0.0, 0.0, 0.0, 0.0)), key=idx, ksize=ksize, jpeg=jpeg or 0, jpeg_chroma=chroma)
+    return degrade_op(hr_img.to(torch.float32), deg.draw(1).to(hr_img.device), int(config.DATA.UPSCALE_FACTOR), ksize,
+                      jpeg_chroma=chroma if jpeg else None)
 
 
-def _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params=None, with_lr=False, degrade=None):
+def _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params=None, with_lr=False, degrade=None,
+                       jpeg=None):
     """The per-image loop of _validate with everything on the device: generator forward -> sst_image_metrics into row idx of one
     [N,2] result buffer, ONE device-to-host copy after the loop.  Nothing syncs per image unless save_images is set (the uint8
     images tensor2img would make then cross per image and are written by _save_png).  st_params: also st_distance(output, hr) per
@@ -101,8 +119,8 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
         for idx, (hr_img, lr_img) in enumerate(val_loader):
             lr_img = lr_img.to(config.DEVICE, non_blocking=True)
             hr_img = hr_img.to(config.DEVICE, non_blocking=True)
-            if degrade:
-                lr_img = _degraded_input(hr_img, idx, config, degrade)
+            if degrade or jpeg:
+                lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg)
             output = generator(lr_img)
             row = results[idx:idx + 1]
             if save_images:
@@ -123,9 +141,11 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
 
 
 def _validate(generator, val_loader, config, save_images=False, concat_with_gt=False, save_metrics=False, on_device=None,
-              with_st=None, tile=None, with_lr=None, degrade=None):
+              with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None):
     """degrade: None = config.DATA.VALIDATE_DEGRADE; (sigma1, sigma2, theta_deg, noise) = the generator's input is degrade(hr)
     (_degraded_input) instead of the loader's LR image, and the printed line and _metrics.txt start by saying so.
+    degrade_jpeg: None = config.DATA.VALIDATE_DEGRADE_JPEG; Q in 1..100 = that input, or without `degrade` the plain bicubic LR made
+    from hr, goes through the JPEG stage at quality Q, and the head line names it.
     on_device: None = config.DATA.VALIDATE_ON_DEVICE; True = metrics by the HIP kernel, one host copy per pass
     (_metrics_on_device); False = the host loop below.  Same averages, same printed line, same _metrics.txt either way.
     with_st: None = config.DATA.VALIDATE_ST; True = every image also gets st.st_distance(output, hr) with the configured ``ST``
@@ -148,20 +168,25 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
     if with_lr is None:
         with_lr = bool(config.DATA.get("VALIDATE_LR", False))
     degrade = _degrade_params(config, degrade)
+    jpeg = _jpeg_param(config, degrade_jpeg)
     deg_head = ""
     if degrade:
         deg_head = "LR = degrade(GT): sigma {:g} / {:g}, theta {:g} deg, noise {:g} | ".format(*degrade)
+    if jpeg:
+        chroma = config.DATA.get("DEGRADE_JPEG_CHROMA", "420")
+        deg_head = (deg_head[:-3] + f", JPEG quality {jpeg} ({chroma}) | " if degrade
+                    else f"LR = jpeg(bicubic(GT)): JPEG quality {jpeg} ({chroma}) | ")
     file = None
     if save_metrics:
         path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
         os.makedirs(path, exist_ok=True)
         file = open(os.path.join(path, "_metrics.txt"), mode="w")
-        if degrade:
+        if deg_head:
             file.write(deg_head + "\n")
     all_psnr, all_ssim, all_st, all_lr = [], [], [], []
     if on_device:
         all_psnr, all_ssim, all_st, all_lr = _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params,
-                                                                with_lr, degrade)
+                                                                with_lr, degrade, jpeg)
         if file:
             for idx, (psnr, ssim) in enumerate(zip(all_psnr, all_ssim)):
                 st_col = f" | ST: {all_st[idx]:.4f}" if with_st else ""
@@ -172,8 +197,8 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
             for idx, (hr_img, lr_img) in enumerate(val_loader):
                 lr_img = lr_img.to(config.DEVICE)
                 hr_img = hr_img.to(config.DEVICE)
-                if degrade:
-                    lr_img = _degraded_input(hr_img, idx, config, degrade)
+                if degrade or jpeg:
+                    lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg)
                 output = generator(lr_img)
                 if save_images:
                     path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
@@ -213,7 +238,7 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
 
 
 def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_gt: bool = False, dataset=None, on_device=None,
-         with_st=None, tile=None, with_lr=None, degrade=None):
+         with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None):
     if not g_path:                # the averaged generator's best when the run kept one (SOLVER.G_EMA_DECAY), else the last iterate's
         g_path = f"results/{config.EXP.NAME}/g_ema_best.pth"
         if not os.path.exists(g_path):
@@ -229,7 +254,7 @@ def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_
         generator = load_state_dict(generator, torch.load(g_path, map_location=config.DEVICE, weights_only=True))
         generator.eval()
     return _validate(generator, loader, config, save_images=save_images, concat_with_gt=concat_w_gt, save_metrics=True,
-                     on_device=on_device, with_st=with_st, tile=tile, with_lr=with_lr, degrade=degrade)
+                     on_device=on_device, with_st=with_st, tile=tile, with_lr=with_lr, degrade=degrade, degrade_jpeg=degrade_jpeg)
 
 
 if __name__ == "__main__":
@@ -244,6 +269,9 @@ if __name__ == "__main__":
     parser.add_argument("--lr-consistency", action="store_true", help="also the LR-PSNR of the re-downscaled output per image (DATA.VALIDATE_LR)")
     parser.add_argument("--degrade", type=str, default=None, metavar="S1,S2,THETA,NOISE",
                         help="feed the generator degrade(gt) with this fixed blur and noise instead of the LR files (DATA.VALIDATE_DEGRADE)")
+    parser.add_argument("--degrade-jpeg", type=int, default=None, metavar="Q",
+                        help="also take that input (or, without --degrade, the bicubic LR made from gt) through the JPEG stage at "
+                             "quality Q (DATA.VALIDATE_DEGRADE_JPEG)")
     a = parser.parse_args()
     cfg = Config()
     if a.name:
@@ -254,4 +282,4 @@ if __name__ == "__main__":
         cfg.DATA.TEST_LR_IMAGES_DIR = f"/work3/{cfg.EXP.USER}/data/{a.test_set}/LRbicx4"
     test(cfg, save_images=not a.no_images, g_path=a.g_path, on_device=True if a.on_device else None,
          with_st=True if a.st else None, tile=a.tile, with_lr=True if a.lr_consistency else None,
-         degrade=tuple(float(v) for v in a.degrade.split(",")) if a.degrade else None)
+         degrade=tuple(float(v) for v in a.degrade.split(",")) if a.degrade else None, degrade_jpeg=a.degrade_jpeg)

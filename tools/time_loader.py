@@ -30,6 +30,11 @@ difference between two legs).  Prints one JSON line.
         # the library, e.g. the parent commit's, in the same process); sst_gather_crops_degraded at K = 7 and 21 with and without
         # noise; and the same degradation as fp32 torch ops on the gathered gt (reflect pad, per-sample grouped conv2d with
         # precomputed weights, Bicubic("cuda"), randn, clamp, round) - the yardstick
+    python tools/time_loader.py jpeg [--launches L] [--replays R] [--repeat N] [--parent-lib PATH [--parent-first]]
+        # the JPEG stage (DATA.DEGRADE_JPEG_PROB), same sizes and method, every sample with blur (K = 21), noise and a quality in
+        # 30..95.  Legs: sst_gather_crops_degraded alone (and, with --parent-lib, through another build of the library in the same
+        # process); the same followed by sst_jpeg in 444 and in 420; sst_jpeg alone on the LR buffer; and the degraded gather followed
+        # by the same codec as torch int32 ops on the device (torch_jpeg, checked against the kernel bit for bit first) - the yardstick
 """
 import argparse
 import json
@@ -304,7 +309,156 @@ def degrade_mode(launches, replays, repeat, parent_lib):
     print(json.dumps(out))
 
 
+def torch_jpeg(lr, q_luma, q_chroma, on, chroma, T):
+    """The codec of csrc/jpeg.hip as torch int32 ops on the device: lr fp32 [B,3,h,w], q_luma / q_chroma int32
+    [B,1,1,8,8] (the samples' tables), on bool [B] (False: the sample keeps its bits), chroma 0 / 1, T int32 [8,8].  The yardstick of
+    the jpeg legs, and checked against the kernel bit for bit before anything is timed."""
+    n, _, h, w = lr.shape
+    M = 16 if chroma else 8
+    iy = torch.arange(-(-h // M) * M, device=lr.device).clamp(max=h - 1)
+    ix = torch.arange(-(-w // M) * M, device=lr.device).clamp(max=w - 1)
+    p = torch.round(255 * lr.clamp(0, 1)).to(torch.int32)[:, :, iy][:, :, :, ix]
+    R, G, Bl = p[:, 0], p[:, 1], p[:, 2]
+    planes = [(19595 * R + 38470 * G + 7471 * Bl + 32768) >> 16,
+              (-11059 * R - 21709 * G + 32768 * Bl + (128 << 16) + 32767) >> 16,
+              (32768 * R - 27439 * G - 5329 * Bl + (128 << 16) + 32767) >> 16]
+    if chroma:
+        planes[1:] = [(c[:, 0::2, 0::2] + c[:, 0::2, 1::2] + c[:, 1::2, 0::2] + c[:, 1::2, 1::2] + 2) >> 2 for c in planes[1:]]
+    Tt = T.t().contiguous()
+
+    def round_trip(pl, q):
+        m, k = pl.shape[1] // 8, pl.shape[2] // 8
+        s = pl.reshape(n, m, 8, k, 8).permute(0, 1, 3, 2, 4) - 128                      # [n, m, k, y, x]
+        a = ((s[..., :, None, :] * T).sum(-1, dtype=torch.int32) + 512) >> 10            # a[y][u] = sum_x T[u][x] s[y][x]
+        F = (T[:, :, None] * a[..., None, :, :]).sum(-2, dtype=torch.int32)              # F[v][u] = sum_y T[v][y] a[y][u]
+        D = torch.sign(F) * torch.div(F.abs() + q * 32768, q * 65536, rounding_mode="floor") * q
+        b = ((Tt[:, :, None] * D[..., None, :, :]).sum(-2, dtype=torch.int32) + 512) >> 10      # b[y][u] = sum_v T[v][y] D[v][u]
+        r = ((b[..., :, None, :] * Tt).sum(-1, dtype=torch.int32) + 32768) >> 16         # r[y][x] = sum_u T[u][x] b[y][u]
+        return (r + 128).clamp(0, 255).permute(0, 1, 3, 2, 4).reshape(n, m * 8, k * 8)
+    Y, cb, cr = round_trip(planes[0], q_luma), round_trip(planes[1], q_chroma), round_trip(planes[2], q_chroma)
+    if chroma:
+        cb, cr = (c.repeat_interleave(2, 1).repeat_interleave(2, 2) for c in (cb, cr))
+    cb, cr = cb - 128, cr - 128
+    rgb = torch.stack([Y + ((91881 * cr + 32768) >> 16), Y + ((-22554 * cb - 46802 * cr + 32768) >> 16),
+                       Y + ((116130 * cb + 32768) >> 16)], 1).clamp(0, 255)[:, :, :h, :w]
+    # (divided by a tensor: by a Python scalar, torch's device kernel multiplies by the rounded reciprocal, which is not p / 255.f)
+    return torch.where(on[:, None, None, None], rgb.float() / torch.full((), 255.0, device=lr.device), lr)
+
+
+def jpeg_mode(launches, replays, repeat, parent_lib, parent_first=False):
+    import ctypes
+    from srganst import _abi
+    from srganst.device_data import JPEG_CHROMA, Degradation, DeviceImageArena, jpeg
+    g = torch.Generator().manual_seed(0)
+    imgs = [torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8) for h, w in WHOLE_SIZES * 2]
+    arena = DeviceImageArena.from_arrays(imgs, HR, HR, UP, "cuda")
+    n, K, o = launches * B, 21, HR // UP
+    tiles = torch.from_numpy(arena.tiles)[torch.randperm(len(arena), generator=g)[:n]]
+    room = torch.from_numpy(arena.table_host[tiles[:, 0].numpy(), 1:3] - HR + 1)
+    desc = torch.zeros(n, 4, dtype=torch.int32)
+    desc[:, 0] = tiles[:, 0]
+    desc[:, 1:3] = (torch.randint(0, 1 << 30, (n, 2), generator=g) % room).to(torch.int32)
+    desc[:, 3] = torch.randint(0, 8, (n,), generator=g).to(torch.int32)
+    arena.check_desc(desc.numpy())
+    desc = desc.cuda()
+    deg_host = Degradation(jpeg_prob=1.0).draw(n, torch.Generator().manual_seed(1))       # blur, noise and a quality in 30..95 each
+    deg = deg_host.cuda()
+    gt, lr = torch.empty(B, 3, HR, HR, device="cuda"), torch.empty(B, 3, o, o, device="cuda")
+    # the comparator's constants, made beforehand: not part of the timed work
+    tabs = (ctypes.c_int * 128)()
+    q_all = []
+    for Q in deg_host[:, 6].tolist():
+        _abi.check(_abi.lib().sst_jpeg_tables(Q, tabs), "sst_jpeg_tables")
+        q_all.append(list(tabs))
+    q_all = torch.tensor(q_all, dtype=torch.int32).reshape(n, 2, 1, 1, 8, 8).cuda()
+    on = torch.ones(n, dtype=torch.bool, device="cuda")
+    u, x = np.arange(8.0)[:, None], np.arange(8.0)[None, :]
+    C = 0.5 * np.cos((2 * x + 1) * u * np.pi / 16)
+    C[0] = np.sqrt(0.125)
+    T = torch.from_numpy(np.rint(8192 * C).astype(np.int32)).cuda()
+
+    def degraded(k):
+        arena.crops(desc[k * B:(k + 1) * B], gt, lr, deg=deg[k * B:(k + 1) * B], ksize=K)
+
+    def with_jpeg(mode):
+        return lambda k: arena.crops(desc[k * B:(k + 1) * B], gt, lr, deg=deg[k * B:(k + 1) * B], ksize=K, jpeg_chroma=mode)
+
+    def jpeg_only(mode):
+        return lambda k: jpeg(lr, deg[k * B:(k + 1) * B], mode, out=lr)
+
+    def torch_leg(mode):
+        def run(k):
+            degraded(k)
+            lr.copy_(torch_jpeg(lr, q_all[k * B:(k + 1) * B, 0], q_all[k * B:(k + 1) * B, 1], on[k * B:(k + 1) * B], JPEG_CHROMA[mode], T))
+        return run
+
+    for mode in ("444", "420"):                          # the comparator is the kernel's codec: the same bits
+        with_jpeg(mode)(0)
+        want = lr.clone()
+        torch_leg(mode)(0)
+        assert torch.equal(lr, want), (f"torch_jpeg and sst_jpeg differ ({mode}): {int((lr != want).sum())} of {lr.numel()} elements, "
+                                       f"by {float((lr - want).abs().max()) * 255:.3g} levels at most")
+    legs = {"degraded_k21_noise": degraded}
+    if parent_lib:
+        other = ctypes.CDLL(parent_lib)
+        other.sst_gather_crops_degraded.restype, other.sst_gather_crops_degraded.argtypes = _abi.SIGNATURES["sst_gather_crops_degraded"]
+        wy, iy, wx, ix = arena._bicubic.tables_i32(HR, HR, 1.0 / UP, arena.device)
+
+        def parent(k):
+            rc = other.sst_gather_crops_degraded(arena.arena.data_ptr(), arena.arena.numel(), arena.table.data_ptr(), arena.n_images,
+                                                 desc[k * B:(k + 1) * B].data_ptr(), B, HR, arena.lut.data_ptr(), gt.data_ptr(),
+                                                 lr.data_ptr(), wy.data_ptr(), iy.data_ptr(), wx.data_ptr(), ix.data_ptr(), o, o,
+                                                 wy.shape[1], wx.shape[1], arena.span(True, True), deg[k * B:(k + 1) * B].data_ptr(), K, 1,
+                                                 _abi.stream_ptr())
+            assert rc == 0, rc
+        legs["degraded_k21_noise_parent_lib"] = parent
+        if parent_first:                                 # the same two legs in the other order: what the order alone is worth
+            legs = {"degraded_k21_noise_parent_lib": parent, "degraded_k21_noise": degraded}
+    for mode in ("444", "420"):
+        legs[f"degraded_jpeg_{mode}"] = with_jpeg(mode)
+    for mode in ("444", "420"):
+        legs[f"jpeg_only_{mode}"] = jpeg_only(mode)
+    for mode in ("444", "420"):
+        legs[f"degraded_torch_ops_jpeg_{mode}"] = torch_leg(mode)
+
+    graphs = {}
+    for name, run in legs.items():
+        for k in range(min(3, launches)):               # warm up: tables, code objects, the allocator's pool
+            run(k)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for k in range(launches):
+                run(k)
+        gr.replay()
+        graphs[name] = gr
+    torch.cuda.synchronize()
+    out = {"mode": "jpeg", "batch": B, "hr": HR, "scale": UP, "launches_per_graph": launches, "replays": replays, "repeat": repeat,
+           "us_per_batch": {name: [] for name in legs}}
+    for _ in range(repeat):
+        for name, gr in graphs.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(replays):
+                gr.replay()
+            t1.record()
+            torch.cuda.synchronize()
+            out["us_per_batch"][name].append(round(t0.elapsed_time(t1) * 1e3 / (replays * launches), 2))
+    out["median_us_per_batch"] = {name: sorted(v)[len(v) // 2] for name, v in out["us_per_batch"].items()}
+    print(json.dumps(out))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "jpeg":
+        ap = argparse.ArgumentParser()
+        ap.add_argument("mode")
+        ap.add_argument("--launches", type=int, default=32)
+        ap.add_argument("--replays", type=int, default=50)
+        ap.add_argument("--repeat", type=int, default=5)
+        ap.add_argument("--parent-lib", default="", help="another build of libsrganst.so whose degraded gather is timed beside this one's")
+        ap.add_argument("--parent-first", action="store_true", help="time the parent library's leg before this library's")
+        a = ap.parse_args()
+        return jpeg_mode(a.launches, a.replays, a.repeat, a.parent_lib, a.parent_first)
     if len(sys.argv) > 1 and sys.argv[1] == "degrade":
         ap = argparse.ArgumentParser()
         ap.add_argument("mode")
