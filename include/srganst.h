@@ -527,6 +527,25 @@ int sst_degrade_tile_cols(void);
  * sst_jpeg_tables: the luminance then the chrominance table of a quality in 1..100, row-major, into out128 (host memory). */
 int sst_jpeg(float* lr, const int* deg, int B, int h, int w, int chroma, void* stream);
 int sst_jpeg_tables(int quality, int* out128);
+/* ---- the second-order degradation stage (device_data.py: filter2d / SecondOrder; csrc/filter.hip): a K x K
+ * correlation with a per-sample kernel taken from a table, then noise, clamp and the 1/255 grid, out of place: x, y fp32 [B,3,h,w]
+ * (h, w in 1..8192; y == x is refused).  bank fp32 [M,K,K], row-major [dy][dx], 16-byte aligned, normalised by the host (the kernel
+ * does not renormalise); K odd, 3..21, p = K / 2 < min(h, w) when M > 0; M == 0 with a null bank is legal (noise only).  flt int32
+ * [B,8] (device, 32-byte aligned), per sample: the kernel index (-1: no blur), the fp32 bits of sigma_n, the fp32 bits of the shot
+ * coefficient s_p, the gray flag (0 / 1), the Philox key k0, k1, two zero words.  Per sample:
+ *   pass-through  idx == -1 && sigma_n == 0 && s_p == 0: y = the bits of x (NaNs and values outside [0, 1] included)
+ *   blur   (idx >= 0)  v[y][x] = sum_{dy,dx} bank[idx][dy][dx] * X[refl(y+dy-p)][refl(x+dx-p)] - a correlation (F.conv2d's
+ *          orientation), torch's `reflect` padding, one fp32 fmaf chain per pixel in row-major order from 0.f
+ *   noise  (sigma_n != 0 || s_p != 0)  z from Philox4x32-10, counter (e, 0, 0, 0), Box-Muller as in the stage above; e the element's
+ *          index in the sample's [3,h,w], or y*w + x with the gray flag (the three channels then get the same z);
+ *          sd = s_p == 0 ? sigma_n : sqrtf(fmaf(s_p, fmaxf(v, 0), sigma_n^2));  v = fmaf(sd, z, v).  s_p is a heteroscedastic
+ *          Gaussian (variance proportional to intensity: the Poisson-Gaussian model), not a Poisson sampler
+ *   output clamp to [0, 1] by comparisons (a NaN is kept), then rintf(255 v) / 255.f; quantise = 0 writes the unclamped, unrounded v
+ * An idx outside [-1, M), a gray flag outside {0, 1}, !(sigma_n >= 0) or !(s_p >= 0) makes that sample NaN and touches no other.  No
+ * atomics: a result is a function of its sample's inputs alone, whatever the batch position, batch size and tile geometry.  One
+ * launch, no allocation, no sync (capturable). */
+int sst_filter2d(const float* x, float* y, const int* flt, const float* bank, int M, int B, int h, int w, int K, int quantise,
+                 void* stream);
 /* Validation metrics of validate.image_metrics on the device (metrics.py), rounding for rounding: sr, hr fp32 NCHW [B,3,H,W] RGB;
  * out fp64 [B,2] = (MSE of the Y channel on the 0..255 scale over all H*W pixels, mean of the SSIM map over its (H-10) x (W-10)
  * valid region); sr_u8 / hr_u8: uint8 [B,H,W,3] BGR = tensor2img of each image (either may be null).  workspace:

@@ -119,6 +119,41 @@ class Config:
         # Q in 1..100: validation feeds the generator the JPEG round trip (chroma DEGRADE_JPEG_CHROMA) of its input at this quality -
         # of degrade(gt) with VALIDATE_DEGRADE, else of the plain bicubic LR made from gt; the printed line says so.  None: off
         self.DATA.VALIDATE_DEGRADE_JPEG = None
+        # with DEGRADE: the second-order stage of BSRGAN / Real-ESRGAN on the first stage's LR batch (device_data.SecondOrder,
+        # sst_filter2d): a second blur at LR resolution with a kernel of a table drawn per epoch - BANK_SIZE
+        # kernels, each a sinc (SINC_PROB, cutoff uniform in OMEGA) or of one of the six families of FAMILY_PROB (iso / aniso Gaussian,
+        # iso / aniso generalised Gaussian with exponent uniform in BETA_GAUSSIAN, iso / aniso plateau with BETA_PLATEAU), standard
+        # deviations uniform in BLUR_SIGMA, on a window that is odd and uniform in 7..KSIZE - applied with BLUR_PROB; noise (NOISE_PROB):
+        # Gaussian with a standard deviation uniform in NOISE_SIGMA (0..255 units) or, with SHOT_PROB, signal-dependent with a shot
+        # coefficient in SHOT (a heteroscedastic Gaussian, variance s_p * v: Real-ESRGAN's Poisson scale 0.05..2.5, squared, over 256
+        # levels; not a Poisson sampler), gray with GRAY_PROB; a JPEG pass (JPEG_PROB, quality a uniform integer in JPEG_QUALITY, chroma
+        # DEGRADE_JPEG_CHROMA); and a final sinc filter (FINAL_SINC_PROB, one of SINC_BANK_SIZE kernels with cutoffs uniform in OMEGA)
+        # before the JPEG pass with SINC_FIRST_PROB, else after it.  The table is a function of (SEED, epoch); the per-tile draws come
+        # from a third private generator, so the first stage's draws are the ones made without it
+        self.DATA.DEGRADE_SECOND = False
+        self.DATA.DEGRADE2_BLUR_PROB = 0.8
+        self.DATA.DEGRADE2_BLUR_SIGMA = (0.2, 1.5)
+        self.DATA.DEGRADE2_FAMILY_PROB = (0.45, 0.25, 0.12, 0.03, 0.12, 0.03)
+        self.DATA.DEGRADE2_BETA_GAUSSIAN = (0.5, 4.0)
+        self.DATA.DEGRADE2_BETA_PLATEAU = (1.0, 2.0)
+        self.DATA.DEGRADE2_SINC_PROB = 0.1
+        self.DATA.DEGRADE2_NOISE_PROB = 1.0
+        self.DATA.DEGRADE2_NOISE_SIGMA = (1.0, 25.0)
+        self.DATA.DEGRADE2_SHOT = (1e-5, 0.025)
+        self.DATA.DEGRADE2_SHOT_PROB = 0.5
+        self.DATA.DEGRADE2_GRAY_PROB = 0.4
+        self.DATA.DEGRADE2_FINAL_SINC_PROB = 0.8
+        self.DATA.DEGRADE2_OMEGA = (3.141592653589793 / 3, 3.141592653589793)
+        self.DATA.DEGRADE2_SINC_FIRST_PROB = 0.5
+        self.DATA.DEGRADE2_JPEG_QUALITY = (30, 95)
+        self.DATA.DEGRADE2_JPEG_PROB = 1.0
+        self.DATA.DEGRADE2_KSIZE = 21
+        self.DATA.DEGRADE2_BANK_SIZE = 1024
+        self.DATA.DEGRADE2_SINC_BANK_SIZE = 256
+        # omega in (0, pi]: validation's input also goes through the sinc filter (kernels.sinc, window DEGRADE2_KSIZE) at this cutoff -
+        # after degrade(gt) (or the plain bicubic LR made from gt) and before the VALIDATE_DEGRADE_JPEG stage; the printed line says
+        # so.  None: off
+        self.DATA.VALIDATE_DEGRADE_SINC = None
 
         self.MODEL = dotdict()
         self.MODEL.G_CONTINUE_FROM_WARMUP = False

@@ -13,6 +13,9 @@ With DATA.DEGRADE that launch (sst_gather_crops_degraded) also blurs each sample
 adds Gaussian noise after it (Degradation, the classical blind-SR model); degrade() is that stage alone on any fp32 batch.
 With a JPEG quality in the sample's deg row (Degradation(jpeg_prob=...), DATA.DEGRADE_JPEG_PROB) a second launch (sst_jpeg) takes
 the LR batch through an all-integer JPEG round trip in place; jpeg() is that stage alone.
+With DATA.DEGRADE_SECOND (SecondOrder) the second-order stage of BSRGAN / Real-ESRGAN follows on the LR batch: a second blur with a
+kernel from a table drawn per epoch (kernels.py: Gaussian, generalised Gaussian, plateau, sinc), gray / signal-dependent noise, a JPEG
+pass and a final sinc filter before or after it - three sst_filter2d launches around one sst_jpeg; filter2d() is that stage alone.
 """
 from __future__ import annotations
 
@@ -481,6 +484,254 @@ def degrade(x: Tensor, deg: Tensor, scale: int, ksize: int = 21, quantise: bool 
     return lr
 
 
+# ---- the second-order degradation stage (DATA.DEGRADE_SECOND; csrc/filter.hip)
+_SECOND_STREAM = 0x3C6EF372FE94F82B       # keeps the loader's second-stage generator apart from its two others
+_SECOND_BANK_STREAM = 0x510E527FADE682D1  # and the epoch's kernel bank apart from the per-tile rows
+SECOND_FAMILIES = ("iso", "aniso", "generalized_iso", "generalized_aniso", "plateau_iso", "plateau_aniso")
+
+
+def filter_rows(index, noise255, shot, gray, keys) -> np.ndarray:
+    """The rows of sst_filter2d, int32 [n, 8], from per-sample arrays: the kernel's index in the bank (-1: no blur), the Gaussian
+    noise's standard deviation in 0..255 units (stored / 255), the shot coefficient s_p itself (the noise's variance is
+    sigma_n^2 + s_p * max(v, 0): a heteroscedastic Gaussian, not a Poisson sampler), the gray flag (one draw for the three channels)
+    and the Philox key [n, 2].  Words 6 and 7 are zero."""
+    idx = np.atleast_1d(np.asarray(index, np.int64))
+    n = len(idx)
+    nz, sp = (np.broadcast_to(np.asarray(a, np.float64), (n,)) for a in (noise255, shot))
+    gr = np.broadcast_to(np.asarray(gray), (n,))
+    if not (np.isfinite(nz).all() and (nz >= 0).all() and np.isfinite(sp).all() and (sp >= 0).all()):
+        raise ValueError("filter_rows: noise255 and shot must be finite and >= 0")
+    if (idx < -1).any() or (idx > 0x7FFFFFFF).any():
+        raise ValueError("filter_rows: a kernel index must be -1 (no blur) or an index into the bank")
+    if not np.isin(gr, (0, 1)).all():
+        raise ValueError("filter_rows: gray must be 0 or 1")
+    keys = np.asarray(keys, np.int64).reshape(n, 2) & 0xFFFFFFFF
+    rows = np.zeros((n, 8), np.int32)
+    rows[:, 0] = idx
+    rows[:, 1] = (nz / 255.0).astype(np.float32).view(np.int32)
+    rows[:, 2] = sp.astype(np.float32).view(np.int32)
+    rows[:, 3] = gr.astype(np.int32)
+    rows[:, 4:6] = keys.astype(np.uint32).view(np.int32)
+    return rows
+
+
+def filter2d(x: Tensor, flt: Tensor, bank: Tensor | None, quantise: bool = True, out: Tensor | None = None) -> Tensor:
+    """ONE sst_filter2d launch on the current stream: the second-order stage alone on an fp32 batch x [B,3,h,w] (h, w <= 8192) with
+    the rows flt int32 [B,8] (filter_rows) and the kernel table bank fp32 [M,K,K] on x's device (kernels.bank; None: no kernels, noise
+    only) -> a new tensor, or `out` (contiguous fp32 of x's shape; never x itself: a tile reads its neighbours' pixels).  Per sample:
+    the correlation with its kernel under torch's `reflect` padding, noise, clamp to [0, 1] and the 1/255 grid; a row with neither a
+    kernel nor noise keeps the sample's bits.  quantise=False (tests and tools) returns the unclamped, unrounded values."""
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_cuda:
+        raise ValueError(f"filter2d: x must be fp32 [B, 3, h, w] on a ROCm device, got {x.dtype} {tuple(x.shape)} on {x.device}")
+    B, _, h, w = x.shape
+    _check_deg(flt, B, x.device, "filter2d")
+    M, K = 0, 3
+    if bank is not None:
+        if (bank.dtype != torch.float32 or bank.dim() != 3 or bank.shape[1] != bank.shape[2] or bank.device != x.device
+                or not bank.is_contiguous()):
+            raise ValueError(f"filter2d: bank must be contiguous fp32 [M, K, K] on {x.device}, got {bank.dtype} {tuple(bank.shape)} "
+                             f"on {bank.device}")
+        M, K = (bank.shape[0], bank.shape[1]) if bank.shape[0] else (0, 3)
+    if out is None:
+        out = torch.empty(B, 3, h, w, device=x.device)
+    else:
+        if out is x or out.data_ptr() == x.data_ptr():
+            raise ValueError("filter2d: out must not be x (a tile reads its neighbours' pixels: out of place only)")
+        if out.dtype != torch.float32 or tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or out.device != x.device:
+            raise ValueError(f"filter2d: out must be contiguous fp32 {tuple(x.shape)} on {x.device}, got {out.dtype} {tuple(out.shape)}")
+    x = x.contiguous()
+    _abi.check(_abi.lib().sst_filter2d(_abi.ptr(x), _abi.ptr(out), _abi.ptr(flt), _abi.ptr(bank) if M else None, M, B, h, w, K,
+                                       int(bool(quantise)), _abi.stream_ptr()), "sst_filter2d")
+    return out
+
+
+def _range(v, name: str, lo_min: float = 0.0, strict: bool = False):
+    a, b = float(v[0]), float(v[1])
+    if not ((lo_min < a if strict else lo_min <= a) and a <= b and np.isfinite(b)):
+        raise ValueError(f"SecondOrder: {name} {tuple(v)} must be {lo_min:g} {'<' if strict else '<='} lo <= hi")
+    return a, b
+
+
+class SecondOrder:
+    """The parameters of the second degradation stage (BSRGAN / Real-ESRGAN's second order), applied to the first stage's LR batch:
+      A  blur 2 with a kernel of the epoch's bank (probability blur_prob) and noise 2 (noise_prob): Gaussian with a standard deviation
+         uniform in noise_sigma (0..255 units), or with probability shot_prob signal-dependent, s_p with sqrt(s_p) uniform between the
+         roots of `shot`; gray (one draw for the three channels) with probability gray_prob
+      B  the final sinc filter (final_sinc_prob, cutoff uniform in omega) for the samples that take it BEFORE the JPEG pass
+         (sinc_first_prob), the others passed through
+      J  JPEG at a quality that is a uniform integer in jpeg_quality (jpeg_prob)
+      C  the final sinc filter for the other samples.
+    draw_bank(generator) -> fp32 [bank_size + sinc_bank_size, ksize, ksize] on the host: bank_size blur kernels, each a sinc
+    (sinc_prob) or of one of the six families of family_prob (iso / aniso Gaussian, generalised Gaussian, plateau) with standard
+    deviations uniform in blur_sigma at a uniform angle, on a window `support` that is odd and uniform in 7..ksize; then
+    sinc_bank_size final-sinc kernels.  draw(n, generator) -> int32 [4, n, 8] on the host: the rows of A, B, J (word 6: the quality,
+    as sst_jpeg reads it) and C.  SecondOrder.fixed(...) draws the same bank and rows every time (validation, tests)."""
+
+    def __init__(self, blur_prob: float = 0.8, blur_sigma=(0.2, 1.5), family_prob=(0.45, 0.25, 0.12, 0.03, 0.12, 0.03),
+                 beta_gaussian=(0.5, 4.0), beta_plateau=(1.0, 2.0), sinc_prob: float = 0.1, noise_prob: float = 1.0,
+                 noise_sigma=(1.0, 25.0), shot=(1e-5, 0.025), shot_prob: float = 0.5, gray_prob: float = 0.4,
+                 final_sinc_prob: float = 0.8, omega=(np.pi / 3, np.pi), sinc_first_prob: float = 0.5, jpeg_quality=(30, 95),
+                 jpeg_prob: float = 1.0, ksize: int = 21, bank_size: int = 1024, sinc_bank_size: int = 256, jpeg_chroma: str = "420"):
+        self.blur_sigma = _range(blur_sigma, "blur_sigma", strict=True)
+        self.beta_gaussian = _range(beta_gaussian, "beta_gaussian", strict=True)
+        self.beta_plateau = _range(beta_plateau, "beta_plateau", strict=True)
+        self.noise_sigma, self.shot = _range(noise_sigma, "noise_sigma"), _range(shot, "shot")
+        self.omega = _range(omega, "omega", strict=True)
+        if self.omega[1] > np.pi:
+            raise ValueError(f"SecondOrder: omega {tuple(omega)} must be within (0, pi]")
+        probs = dict(blur_prob=blur_prob, sinc_prob=sinc_prob, noise_prob=noise_prob, shot_prob=shot_prob, gray_prob=gray_prob,
+                     final_sinc_prob=final_sinc_prob, sinc_first_prob=sinc_first_prob, jpeg_prob=jpeg_prob)
+        for name, v in probs.items():
+            if not 0 <= v <= 1:
+                raise ValueError(f"SecondOrder: {name} {v!r} must be in [0, 1]")
+            setattr(self, name, float(v))
+        self.family_prob = tuple(float(v) for v in family_prob)
+        if len(self.family_prob) != 6 or min(self.family_prob) < 0 or abs(sum(self.family_prob) - 1) > 1e-9:
+            raise ValueError(f"SecondOrder: family_prob {tuple(family_prob)} must be six probabilities that sum to 1 {SECOND_FAMILIES}")
+        self.jpeg_quality, self.jpeg_chroma = (int(jpeg_quality[0]), int(jpeg_quality[1])), jpeg_chroma
+        if not (1 <= self.jpeg_quality[0] <= self.jpeg_quality[1] <= 100 and tuple(jpeg_quality) == self.jpeg_quality):
+            raise ValueError(f"SecondOrder: jpeg_quality {jpeg_quality} must be integers 1 <= lo <= hi <= 100")
+        _chroma(jpeg_chroma, "SecondOrder")
+        self.ksize, self.bank_size, self.sinc_bank_size = int(ksize), int(bank_size), int(sinc_bank_size)
+        if self.ksize not in DEGRADE_KSIZES:
+            raise ValueError(f"SecondOrder: ksize {ksize} must be odd and in 3..21")
+        if self.bank_size < 1 or self.sinc_bank_size < 1:
+            raise ValueError(f"SecondOrder: bank_size {bank_size} and sinc_bank_size {sinc_bank_size} must be positive")
+        self._fixed = None
+
+    @property
+    def has_jpeg(self) -> bool:
+        """True when a row this draws can hold a JPEG quality: the loader then issues the stage's sst_jpeg launch."""
+        return self._fixed["jpeg"] > 0 if self._fixed else self.jpeg_prob > 0
+
+    @classmethod
+    def fixed(cls, kernel=None, noise: float = 0.0, shot: float = 0.0, gray: bool = False, key=0, sinc_omega: float | None = None,
+              sinc_first: bool = True, jpeg: int = 0, ksize: int = 21, jpeg_chroma: str = "420") -> "SecondOrder":
+        """Every sample gets these: the blur kernel (a [ksize, ksize] table; None: no blur), the noise's standard deviation in 0..255
+        units and shot coefficient, the gray flag, the key (an int: the low and high 32 bits; or a pair of words), the final sinc
+        filter's cutoff (None: none) before (sinc_first) or after the JPEG pass, and the JPEG quality (0: none)."""
+        from . import kernels
+        if int(jpeg) != jpeg or not 0 <= jpeg <= 100:
+            raise ValueError(f"SecondOrder.fixed: the JPEG quality {jpeg!r} must be an integer in 0..100 (0: none)")
+        d = cls(ksize=ksize, jpeg_chroma=jpeg_chroma)
+        tables = []
+        if kernel is not None:
+            kernel = np.asarray(kernel, np.float64)
+            if kernel.shape != (d.ksize, d.ksize):
+                raise ValueError(f"SecondOrder.fixed: the kernel must be a [{d.ksize}, {d.ksize}] table, got {kernel.shape}")
+            tables.append(kernel)
+        if sinc_omega is not None:
+            tables.append(kernels.sinc(d.ksize, float(sinc_omega)))
+        k = (int(key) & 0xFFFFFFFF, (int(key) >> 32) & 0xFFFFFFFF) if isinstance(key, (int, np.integer)) else (int(key[0]), int(key[1]))
+        filter_rows([-1], noise, shot, int(bool(gray)), [k])                         # the refusals
+        d._fixed = dict(bank=kernels.bank(tables) if tables else np.zeros((0, d.ksize, d.ksize), np.float32),
+                        blur=0 if kernel is not None else -1, sinc=-1 if sinc_omega is None else len(tables) - 1,
+                        noise=float(noise), shot=float(shot), gray=int(bool(gray)), key=k, sinc_first=bool(sinc_first), jpeg=int(jpeg),
+                        omega=sinc_omega)
+        return d
+
+    def __repr__(self) -> str:
+        if self._fixed:
+            f = self._fixed
+            return (f"SecondOrder.fixed(kernel={'a table' if f['blur'] >= 0 else None}, noise={f['noise']:g}, shot={f['shot']:g}, "
+                    f"gray={bool(f['gray'])}, key={f['key']}, sinc_omega={f['omega']}, sinc_first={f['sinc_first']}, jpeg={f['jpeg']}, "
+                    f"ksize={self.ksize})")
+        return (f"SecondOrder(blur_prob={self.blur_prob:g}, blur_sigma={self.blur_sigma}, family_prob={self.family_prob}, "
+                f"beta_gaussian={self.beta_gaussian}, beta_plateau={self.beta_plateau}, sinc_prob={self.sinc_prob:g}, "
+                f"noise_prob={self.noise_prob:g}, noise_sigma={self.noise_sigma}, shot={self.shot}, shot_prob={self.shot_prob:g}, "
+                f"gray_prob={self.gray_prob:g}, final_sinc_prob={self.final_sinc_prob:g}, omega=({self.omega[0]:.4g}, {self.omega[1]:.4g}), "
+                f"sinc_first_prob={self.sinc_first_prob:g}, jpeg_quality={self.jpeg_quality}, jpeg_prob={self.jpeg_prob:g}, "
+                f"jpeg_chroma={self.jpeg_chroma!r}, ksize={self.ksize}, bank_size={self.bank_size}+{self.sinc_bank_size})")
+
+    def _support(self, u: float) -> int:
+        lo = min(7, self.ksize)
+        return lo + 2 * min(int(u * ((self.ksize - lo) // 2 + 1)), (self.ksize - lo) // 2)
+
+    def draw_bank(self, generator: torch.Generator | None = None) -> np.ndarray:
+        from . import kernels
+        if self._fixed:
+            return self._fixed["bank"]
+        K, n = self.ksize, self.bank_size
+        u = torch.rand(n + self.sinc_bank_size, 8, generator=generator, dtype=torch.float64).numpy()
+        edges = np.cumsum(self.family_prob)
+        (b0, b1), (w0, w1) = self.blur_sigma, self.omega
+        tables = []
+        for m in range(n):
+            support = self._support(u[m, 1])
+            if u[m, 0] < self.sinc_prob:
+                tables.append(kernels.sinc(K, w0 + (w1 - w0) * u[m, 2], support))
+                continue
+            fam = min(int(np.searchsorted(edges, u[m, 3], side="right")), 5)
+            s1 = b0 + (b1 - b0) * u[m, 4]
+            s2 = b0 + (b1 - b0) * u[m, 5] if fam % 2 else s1
+            theta = np.pi * u[m, 6] if fam % 2 else 0.0
+            if fam < 2:
+                tables.append(kernels.gaussian(K, s1, s2, theta, support))
+            elif fam < 4:
+                g0, g1 = self.beta_gaussian
+                tables.append(kernels.generalized_gaussian(K, s1, s2, theta, g0 + (g1 - g0) * u[m, 7], support))
+            else:
+                p0, p1 = self.beta_plateau
+                tables.append(kernels.plateau(K, s1, s2, theta, p0 + (p1 - p0) * u[m, 7], support))
+        for m in range(n, n + self.sinc_bank_size):
+            tables.append(kernels.sinc(K, w0 + (w1 - w0) * u[m, 2], self._support(u[m, 1])))
+        return kernels.bank(tables)
+
+    def draw(self, n: int, generator: torch.Generator | None = None) -> Tensor:
+        rows = np.zeros((4, n, 8), np.int32)
+        if self._fixed:
+            f = self._fixed
+            rows[0] = filter_rows([f["blur"]] * n, f["noise"], f["shot"], f["gray"], [f["key"]] * n)
+            first = f["sinc"] >= 0 and f["sinc_first"]
+            rows[1, :, 0] = f["sinc"] if first else -1
+            rows[2, :, 6] = f["jpeg"]
+            rows[3, :, 0] = -1 if first else f["sinc"]
+            return torch.from_numpy(rows)
+        u = torch.rand(n, 8, generator=generator, dtype=torch.float64).numpy()
+        keys = torch.randint(0, 1 << 32, (n, 2), generator=generator, dtype=torch.int64).numpy()
+        pick = torch.randint(0, 1 << 62, (n, 3), generator=generator, dtype=torch.int64).numpy()
+        blur = np.where(u[:, 0] < self.blur_prob, pick[:, 0] % self.bank_size, -1)
+        noisy, shot = u[:, 1] < self.noise_prob, u[:, 2] < self.shot_prob
+        (n0, n1), (s0, s1) = self.noise_sigma, (np.sqrt(self.shot[0]), np.sqrt(self.shot[1]))
+        nz = np.where(noisy & ~shot, n0 + (n1 - n0) * u[:, 3], 0.0)
+        sp = np.where(noisy & shot, np.clip((s0 + (s1 - s0) * u[:, 3]) ** 2, *self.shot), 0.0)
+        rows[0] = filter_rows(blur, nz, sp, (u[:, 4] < self.gray_prob).astype(np.int32), keys)
+        sinc = np.where(u[:, 5] < self.final_sinc_prob, self.bank_size + pick[:, 1] % self.sinc_bank_size, -1)
+        first = u[:, 6] < self.sinc_first_prob
+        rows[1, :, 0] = np.where(first, sinc, -1)
+        q0, q1 = self.jpeg_quality
+        rows[2, :, 6] = np.where(u[:, 7] < self.jpeg_prob, q0 + pick[:, 2] % (q1 - q0 + 1), 0)
+        rows[3, :, 0] = np.where(first, -1, sinc)
+        return torch.from_numpy(rows)
+
+    @classmethod
+    def from_config(cls, config) -> "SecondOrder | None":
+        """DATA.DEGRADE2_* -> a SecondOrder, or None with DATA.DEGRADE_SECOND off."""
+        d = config.DATA
+        if not d.get("DEGRADE_SECOND", False):
+            return None
+        return cls(d.DEGRADE2_BLUR_PROB, d.DEGRADE2_BLUR_SIGMA, d.DEGRADE2_FAMILY_PROB, d.DEGRADE2_BETA_GAUSSIAN, d.DEGRADE2_BETA_PLATEAU,
+                   d.DEGRADE2_SINC_PROB, d.DEGRADE2_NOISE_PROB, d.DEGRADE2_NOISE_SIGMA, d.DEGRADE2_SHOT, d.DEGRADE2_SHOT_PROB,
+                   d.DEGRADE2_GRAY_PROB, d.DEGRADE2_FINAL_SINC_PROB, d.DEGRADE2_OMEGA, d.DEGRADE2_SINC_FIRST_PROB,
+                   tuple(d.DEGRADE2_JPEG_QUALITY), d.DEGRADE2_JPEG_PROB, d.DEGRADE2_KSIZE, d.DEGRADE2_BANK_SIZE,
+                   d.DEGRADE2_SINC_BANK_SIZE, d.get("DEGRADE_JPEG_CHROMA", "420"))
+
+
+def second_order(lr: Tensor, rows: Tensor, bank: Tensor | None, jpeg_chroma: str | None = "420", out: Tensor | None = None,
+                 scratch=None) -> Tensor:
+    """The second stage on an LR batch on the 1/255 grid, as the loader issues it: filter2d with rows[0] (blur 2, noise 2), filter2d
+    with rows[1] (the final sinc before JPEG), jpeg with rows[2] (jpeg_chroma None: no such launch), filter2d with rows[3] (the final
+    sinc after it).  rows: int32 [4, B, 8] on lr's device (SecondOrder.draw).  The last launch writes `out`; scratch: two buffers of
+    lr's shape for the passes between (allocated when None: lr is then left as it is; the second may be lr itself, as the loader has
+    it, and lr is then overwritten)."""
+    a, b = scratch if scratch is not None else (torch.empty_like(lr, memory_format=torch.contiguous_format) for _ in range(2))
+    filter2d(lr, rows[0], bank, out=a)
+    filter2d(a, rows[1], bank, out=b)
+    if jpeg_chroma is not None:
+        jpeg(b, rows[2], jpeg_chroma, out=b)
+    return filter2d(b, rows[3], bank, out=out)
+
+
 class DeviceImageArena:
     """WHOLE training images of any sizes on one device: one packed uint8 arena (HWC/RGB, every image at a 16-byte aligned
     offset) and a device table [N, 3] int64 of (byte offset, H, W).  len() is the number of tiles of the virtual tile list
@@ -678,10 +929,15 @@ class DeviceCropLoader:
     SECOND private generator (seed, epoch and a constant of its own), so a tile's degradation depends on neither world size nor rank
     nor batch size either, the window and transform draws are the ones made without it, and resuming at an epoch reproduces it.
     A degradation that can draw a JPEG quality (Degradation.has_jpeg) adds one sst_jpeg launch per batch; any other leaves the
-    launches as they are."""
+    launches as they are.
+    second (needs degradation): the second-order stage follows, per batch three sst_filter2d launches and one sst_jpeg between the
+    last two (second_order()); the gather then writes a scratch buffer of the loader and the last launch the bound lr buffer.  The
+    epoch's kernel bank is a function of (seed, epoch); the epoch's rows are drawn for ALL tiles from a THIRD private generator (seed,
+    epoch and a constant of its own), so a tile's second stage depends on neither world size nor rank nor batch size, the window,
+    transform and first-stage draws are the ones made without it, and resuming at an epoch reproduces it."""
 
     def __init__(self, arena: DeviceImageArena, batch_size: int, sampler=None, random_crop: bool = False, augment: bool = False,
-                 seed: int = 0, degradation: Degradation | None = None):
+                 seed: int = 0, degradation: Degradation | None = None, second: SecondOrder | None = None):
         if batch_size <= 0:
             raise ValueError("DeviceCropLoader: batch_size must be positive")
         self.dset = arena
@@ -692,8 +948,17 @@ class DeviceCropLoader:
         if degradation is not None and degradation.ksize // 2 >= arena.crop:
             raise ValueError(f"DeviceCropLoader: the blur's half window {degradation.ksize // 2} must be smaller than the crop "
                              f"side {arena.crop}")
+        self.second = second
+        if second is not None:
+            if degradation is None:
+                raise ValueError("DeviceCropLoader: second (the second-order stage) needs degradation: it works on the first stage's "
+                                 "quantised LR batch")
+            if second.ksize // 2 >= arena.out:
+                raise ValueError(f"DeviceCropLoader: the second stage's half window {second.ksize // 2} must be smaller than the LR "
+                                 f"side {arena.out}")
         self.epoch = 0
         self._gt = self._lr = None
+        self._scratch = None
 
     def __len__(self) -> int:
         return len(self.sampler) // self.batch_size
@@ -726,10 +991,30 @@ class DeviceCropLoader:
         g = torch.Generator().manual_seed((self.seed * 1000003 + epoch + _DEGRADE_STREAM) % (1 << 63))
         return self.degradation.draw(len(self.dset), g).numpy()
 
+    def second_draws(self, epoch: int):
+        """The epoch's second-stage rows of EVERY tile of the set, int32 [4, len(arena), 8] (SecondOrder.draw), and its kernel bank,
+        fp32 [M, K, K]; None without a second stage."""
+        if self.second is None:
+            return None
+        base = self.seed * 1000003 + epoch
+        rows = self.second.draw(len(self.dset), torch.Generator().manual_seed((base + _SECOND_STREAM) % (1 << 63))).numpy()
+        return rows, self.second.draw_bank(torch.Generator().manual_seed((base + _SECOND_BANK_STREAM) % (1 << 63)))
+
+    def plan_all(self):
+        """plan_both() and, in the same order, the second stage's rows int32 [4, len(self) * batch_size, 8] and bank (or None, None)."""
+        order = np.fromiter(iter(self.sampler), dtype=np.int64)[: len(self) * self.batch_size]
+        desc, deg = self._plan(order)
+        if self.second is None:
+            return desc, deg, None, None
+        rows, bank = self.second_draws(self.epoch)
+        return desc, deg, torch.from_numpy(np.ascontiguousarray(rows[:, order])), torch.from_numpy(bank)
+
     def plan_both(self):
         """The current epoch on the host, in the sampler's order (ONE walk of the sampler): the descriptors int32
         [len(self) * batch_size, 4], tile indices and windows checked against the set, and the deg rows int32 [.., 8] or None."""
-        order = np.fromiter(iter(self.sampler), dtype=np.int64)[: len(self) * self.batch_size]
+        return self._plan(np.fromiter(iter(self.sampler), dtype=np.int64)[: len(self) * self.batch_size])
+
+    def _plan(self, order):
         n = len(self.dset)
         if order.size and (int(order.min()) < 0 or int(order.max()) >= n):
             raise IndexError(f"DeviceCropLoader: the sampler produced an index outside [0, {n})")
@@ -745,7 +1030,7 @@ class DeviceCropLoader:
 
     def __iter__(self):
         B = self.batch_size
-        host, host_deg = self.plan_both()
+        host, host_deg, host_rows, host_bank = self.plan_all() if self.second is not None else (*self.plan_both(), None, None)
         self.epoch += 1
         dev = self.dset.device
         up = (lambda t: t.pin_memory().to(dev, non_blocking=True)) if dev.type == "cuda" else (lambda t: t)
@@ -756,13 +1041,32 @@ class DeviceCropLoader:
             return
         deg = up(host_deg)                                               # once per epoch, next to desc
         jpeg_chroma = self.degradation.jpeg_chroma if self.degradation.has_jpeg else None
+        if self.second is not None:
+            yield from self._iter_second(desc, deg, jpeg_chroma, up(host_rows), up(host_bank) if host_bank.numel() else None)
+            return
         for k in range(len(self)):
             yield self.dset.crops(desc[k * B:(k + 1) * B], self._gt, self._lr, deg=deg[k * B:(k + 1) * B],
                                   ksize=self.degradation.ksize, jpeg_chroma=jpeg_chroma)
 
+    def _iter_second(self, desc, deg, jpeg_chroma, rows, bank):
+        """The batches with the second stage: the gather (and its sst_jpeg) into a scratch buffer, then second_order() from it, the last
+        launch into the bound lr buffer - no copy."""
+        B, o, dev = self.batch_size, self.dset.out, self.dset.device
+        if self._scratch is None or self._scratch[0].shape[0] != B:
+            self._scratch = (torch.empty(B, 3, o, o, device=dev), torch.empty(B, 3, o, o, device=dev))
+        s0, s1 = self._scratch
+        chroma2 = self.second.jpeg_chroma if self.second.has_jpeg else None
+        for k in range(len(self)):
+            sl = slice(k * B, (k + 1) * B)
+            gt, _ = self.dset.crops(desc[sl], self._gt, s0, deg=deg[sl], ksize=self.degradation.ksize, jpeg_chroma=jpeg_chroma)
+            lr = self._lr if self._lr is not None else torch.empty(B, 3, o, o, device=dev)
+            _expect(lr, (B, 3, o, o), "lr_out")
+            yield gt, second_order(s0, rows[:, sl], bank, chroma2, out=lr, scratch=(s1, s0))
+
 
 def check_switches(config) -> None:
-    """DATA.RANDOM_CROP, DATA.AUGMENT and DATA.DEGRADE are made by the whole-image gather only."""
+    """DATA.RANDOM_CROP, DATA.AUGMENT and DATA.DEGRADE are made by the whole-image gather only; DATA.DEGRADE_JPEG_PROB and
+    DATA.DEGRADE_SECOND follow DATA.DEGRADE."""
     data = config.DATA
     if data.get("DEGRADE", False) and not data.get("ON_DEVICE_WHOLE_IMAGES", False):
         raise ValueError("DATA.DEGRADE needs DATA.ON_DEVICE_WHOLE_IMAGES = True: the per-sample blur and noise are made by the "
@@ -771,20 +1075,28 @@ def check_switches(config) -> None:
     if data.get("DEGRADE_JPEG_PROB", 0.0) > 0 and not data.get("DEGRADE", False):
         raise ValueError("DATA.DEGRADE_JPEG_PROB needs DATA.DEGRADE = True: the JPEG stage follows the degraded gather and reads its "
                          "quality from the same per-sample rows (set DEGRADE_BLUR_PROB = DEGRADE_NOISE_PROB = 0 for JPEG alone)")
+    if data.get("DEGRADE_SECOND", False) and not data.get("DEGRADE", False):
+        raise ValueError("DATA.DEGRADE_SECOND needs DATA.DEGRADE = True: the second-order stage (sst_filter2d, DESIGN.md section 23) works "
+                         "on the first stage's quantised LR batch (set DEGRADE_BLUR_PROB = DEGRADE_NOISE_PROB = 0 for the second "
+                         "stage alone)")
     if (data.get("RANDOM_CROP", False) or data.get("AUGMENT", False)) and not data.get("ON_DEVICE_WHOLE_IMAGES", False):
         raise ValueError("DATA.RANDOM_CROP / DATA.AUGMENT need DATA.ON_DEVICE_WHOLE_IMAGES = True: the random window and the flips / "
                          "transposition are made by the whole-image gather (device_data.DeviceCropLoader), no other data path has them")
 
 
-def announce_degradation(config, degradation: Degradation) -> None:
-    """The drivers' one log line for DATA.DEGRADE, and a warning for every configured BackProjectionLoss(target="gt"): its target is
-    the bicubic of gt, which is then not the LR image the generator saw (target="lr" takes the loader's)."""
+def announce_degradation(config, degradation: Degradation, second: SecondOrder | None = None) -> None:
+    """The drivers' one log line for DATA.DEGRADE (one more with a JPEG stage, one more with the second-order stage), and a warning
+    for every configured BackProjectionLoss(target="gt"): its target is the bicubic of gt, which is then not the LR image the generator
+    saw (target="lr" takes the loader's)."""
     import warnings
     from .loss import BackProjectionLoss
     print(f"[Data] DATA.DEGRADE: lr = quantise(clamp(bicubic(gt * k) + n)) per sample in the gather launch, {degradation!r}")
     if degradation.has_jpeg:
         print(f"[Data] DATA.DEGRADE: then lr = jpeg(lr) in a second launch (sst_jpeg, integer codec, chroma {degradation.jpeg_chroma})"
               + ("" if degradation._fixed else f": quality uniform in {degradation.jpeg_quality} with probability {degradation.jpeg_prob:g}"))
+    if second is not None:
+        print("[Data] DATA.DEGRADE_SECOND: then lr = sinc(jpeg(sinc(quantise(clamp(lr * k2 + n2))))) per sample (sst_filter2d x 3 around "
+              f"sst_jpeg, kernels from a table drawn per epoch), {second!r}")
     loss = config.MODEL.G_LOSS
     for where in ("CRITERIONS", "WARMUP_CRITERIONS"):
         for name, crit in loss.get(where, {}).items():
@@ -819,9 +1131,9 @@ def train_loader(config, train_dataset, world: int, rank: int):
         sampler = DS(arena, world, rank, shuffle=True) if world > 1 else None
         degradation = Degradation.from_config(config)
         loader = DeviceCropLoader(arena, config.DATA.BATCH_SIZE, sampler, config.DATA.RANDOM_CROP, config.DATA.AUGMENT,
-                                  config.DATA.SEED, degradation)
+                                  config.DATA.SEED, degradation, SecondOrder.from_config(config))
         if degradation is not None and rank == 0:
-            announce_degradation(config, degradation)
+            announce_degradation(config, degradation, loader.second)
         loader.set_epoch(config.EXP.START_EPOCH)
         return loader, sampler
     if train_dataset is not None:

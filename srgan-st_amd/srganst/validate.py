@@ -15,7 +15,10 @@ file: the test set under the degradation DATA.DEGRADE trains on.  Either validat
 line and _metrics.txt name the parameters.
 With config.DATA.VALIDATE_DEGRADE_JPEG = Q (or degrade_jpeg=Q, or --degrade-jpeg Q; 1..100) that input also goes through the JPEG
 stage (device_data.jpeg, chroma DATA.DEGRADE_JPEG_CHROMA) at quality Q; without VALIDATE_DEGRADE the input is then the JPEG round trip
-of the plain bicubic LR made from gt.  The printed line and _metrics.txt name the quality."""
+of the plain bicubic LR made from gt.  The printed line and _metrics.txt name the quality.
+With config.DATA.VALIDATE_DEGRADE_SINC = omega (or degrade_sinc=omega, or --degrade-sinc OMEGA; 0 < omega <= pi) that input also goes
+through the sinc low-pass filter of the second-order degradation (device_data.filter2d with kernels.sinc at this cutoff, window
+DATA.DEGRADE2_KSIZE): after degrade(gt), or the plain bicubic LR made from gt, and before the JPEG stage.  The head line names it."""
 from __future__ import annotations
 
 import argparse
@@ -92,20 +95,50 @@ def _jpeg_param(config, degrade_jpeg):
     return int(degrade_jpeg)
 
 
-def _degraded_input(hr_img, idx, config, degrade, jpeg=None):
-    """The generator's input under VALIDATE_DEGRADE / VALIDATE_DEGRADE_JPEG: degrade(hr) with the fixed parameters and key = the
-    image's index (without VALIDATE_DEGRADE: neither blur nor noise, the plain bicubic's bits), then the JPEG stage at quality jpeg."""
+def _sinc_param(config, degrade_sinc):
+    """None, or the sinc filter's cutoff as a float in (0, pi]: the argument, else config.DATA.VALIDATE_DEGRADE_SINC."""
+    if degrade_sinc is None:
+        degrade_sinc = config.DATA.get("VALIDATE_DEGRADE_SINC", None)
+    if degrade_sinc is None:
+        return None
+    if not 0 < float(degrade_sinc) <= np.pi:
+        raise ValueError(f"VALIDATE_DEGRADE_SINC: expected a cutoff in (0, pi], got {degrade_sinc!r}")
+    return float(degrade_sinc)
+
+
+_sinc_banks = {}
+
+
+def _degraded_input(hr_img, idx, config, degrade, jpeg=None, sinc=None):
+    """The generator's input under VALIDATE_DEGRADE / VALIDATE_DEGRADE_SINC / VALIDATE_DEGRADE_JPEG: degrade(hr) with the fixed
+    parameters and key = the image's index (without VALIDATE_DEGRADE: neither blur nor noise, the plain bicubic's bits), then the sinc
+    filter at cutoff sinc, then the JPEG stage at quality jpeg."""
     from .device_data import Degradation
     from .device_data import degrade as degrade_op
     ksize = int(config.DATA.get("DEGRADE_BLUR_KSIZE", 21))
     chroma = config.DATA.get("DEGRADE_JPEG_CHROMA", "420")
+    if sinc:
+        from . import kernels
+        from .device_data import filter2d, filter_rows
+        from .device_data import jpeg as jpeg_op
+        k2 = int(config.DATA.get("DEGRADE2_KSIZE", 21))
+        deg = Degradation.fixed(*(degrade or (0.0, 0.0, 0.0, 0.0)), key=idx, ksize=ksize, jpeg=jpeg or 0, jpeg_chroma=chroma)
+        rows = deg.draw(1).to(hr_img.device)
+        lr = degrade_op(hr_img.to(torch.float32), rows, int(config.DATA.UPSCALE_FACTOR), ksize)
+        key = (str(hr_img.device), k2, sinc)
+        if key not in _sinc_banks:                           # the table and its one row: made once per (device, window, cutoff)
+            _sinc_banks[key] = (torch.from_numpy(kernels.bank([kernels.sinc(k2, sinc)])).to(hr_img.device),
+                                torch.from_numpy(filter_rows([0], 0.0, 0.0, 0, [(0, 0)])).to(hr_img.device))
+        bank, flt = _sinc_banks[key]
+        lr = filter2d(lr, flt, bank)
+        return jpeg_op(lr, rows, chroma, out=lr) if jpeg else lr
     deg = Degradation.fixed(*(degrade or (0.0, 0.0, 0.0, 0.0)), key=idx, ksize=ksize, jpeg=jpeg or 0, jpeg_chroma=chroma)
     return degrade_op(hr_img.to(torch.float32), deg.draw(1).to(hr_img.device), int(config.DATA.UPSCALE_FACTOR), ksize,
                       jpeg_chroma=chroma if jpeg else None)
 
 
 def _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params=None, with_lr=False, degrade=None,
-                       jpeg=None):
+                       jpeg=None, sinc=None):
     """The per-image loop of _validate with everything on the device: generator forward -> sst_image_metrics into row idx of one
     [N,2] result buffer, ONE device-to-host copy after the loop.  Nothing syncs per image unless save_images is set (the uint8
     images tensor2img would make then cross per image and are written by _save_png).  st_params: also st_distance(output, hr) per
@@ -119,8 +152,8 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
         for idx, (hr_img, lr_img) in enumerate(val_loader):
             lr_img = lr_img.to(config.DEVICE, non_blocking=True)
             hr_img = hr_img.to(config.DEVICE, non_blocking=True)
-            if degrade or jpeg:
-                lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg)
+            if degrade or jpeg or sinc:
+                lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg, sinc)
             output = generator(lr_img)
             row = results[idx:idx + 1]
             if save_images:
@@ -141,11 +174,13 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
 
 
 def _validate(generator, val_loader, config, save_images=False, concat_with_gt=False, save_metrics=False, on_device=None,
-              with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None):
+              with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None, degrade_sinc=None):
     """degrade: None = config.DATA.VALIDATE_DEGRADE; (sigma1, sigma2, theta_deg, noise) = the generator's input is degrade(hr)
     (_degraded_input) instead of the loader's LR image, and the printed line and _metrics.txt start by saying so.
     degrade_jpeg: None = config.DATA.VALIDATE_DEGRADE_JPEG; Q in 1..100 = that input, or without `degrade` the plain bicubic LR made
     from hr, goes through the JPEG stage at quality Q, and the head line names it.
+    degrade_sinc: None = config.DATA.VALIDATE_DEGRADE_SINC; omega in (0, pi] = that input goes through the sinc filter at this cutoff
+    before the JPEG stage, and the head line names it.
     on_device: None = config.DATA.VALIDATE_ON_DEVICE; True = metrics by the HIP kernel, one host copy per pass
     (_metrics_on_device); False = the host loop below.  Same averages, same printed line, same _metrics.txt either way.
     with_st: None = config.DATA.VALIDATE_ST; True = every image also gets st.st_distance(output, hr) with the configured ``ST``
@@ -169,12 +204,16 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
         with_lr = bool(config.DATA.get("VALIDATE_LR", False))
     degrade = _degrade_params(config, degrade)
     jpeg = _jpeg_param(config, degrade_jpeg)
+    sinc = _sinc_param(config, degrade_sinc)
     deg_head = ""
     if degrade:
         deg_head = "LR = degrade(GT): sigma {:g} / {:g}, theta {:g} deg, noise {:g} | ".format(*degrade)
+    if sinc:
+        deg_head = (deg_head[:-3] + f", sinc cutoff {sinc:g} | " if degrade
+                    else f"LR = {'jpeg(sinc(bicubic(GT)))' if jpeg else 'sinc(bicubic(GT))'}: sinc cutoff {sinc:g} | ")
     if jpeg:
         chroma = config.DATA.get("DEGRADE_JPEG_CHROMA", "420")
-        deg_head = (deg_head[:-3] + f", JPEG quality {jpeg} ({chroma}) | " if degrade
+        deg_head = (deg_head[:-3] + f", JPEG quality {jpeg} ({chroma}) | " if degrade or sinc
                     else f"LR = jpeg(bicubic(GT)): JPEG quality {jpeg} ({chroma}) | ")
     file = None
     if save_metrics:
@@ -186,7 +225,7 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
     all_psnr, all_ssim, all_st, all_lr = [], [], [], []
     if on_device:
         all_psnr, all_ssim, all_st, all_lr = _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params,
-                                                                with_lr, degrade, jpeg)
+                                                                with_lr, degrade, jpeg, sinc)
         if file:
             for idx, (psnr, ssim) in enumerate(zip(all_psnr, all_ssim)):
                 st_col = f" | ST: {all_st[idx]:.4f}" if with_st else ""
@@ -197,8 +236,8 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
             for idx, (hr_img, lr_img) in enumerate(val_loader):
                 lr_img = lr_img.to(config.DEVICE)
                 hr_img = hr_img.to(config.DEVICE)
-                if degrade or jpeg:
-                    lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg)
+                if degrade or jpeg or sinc:
+                    lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg, sinc)
                 output = generator(lr_img)
                 if save_images:
                     path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
@@ -238,7 +277,7 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
 
 
 def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_gt: bool = False, dataset=None, on_device=None,
-         with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None):
+         with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None, degrade_sinc=None):
     if not g_path:                # the averaged generator's best when the run kept one (SOLVER.G_EMA_DECAY), else the last iterate's
         g_path = f"results/{config.EXP.NAME}/g_ema_best.pth"
         if not os.path.exists(g_path):
@@ -254,7 +293,8 @@ def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_
         generator = load_state_dict(generator, torch.load(g_path, map_location=config.DEVICE, weights_only=True))
         generator.eval()
     return _validate(generator, loader, config, save_images=save_images, concat_with_gt=concat_w_gt, save_metrics=True,
-                     on_device=on_device, with_st=with_st, tile=tile, with_lr=with_lr, degrade=degrade, degrade_jpeg=degrade_jpeg)
+                     on_device=on_device, with_st=with_st, tile=tile, with_lr=with_lr, degrade=degrade, degrade_jpeg=degrade_jpeg,
+                     degrade_sinc=degrade_sinc)
 
 
 if __name__ == "__main__":
@@ -272,6 +312,9 @@ if __name__ == "__main__":
     parser.add_argument("--degrade-jpeg", type=int, default=None, metavar="Q",
                         help="also take that input (or, without --degrade, the bicubic LR made from gt) through the JPEG stage at "
                              "quality Q (DATA.VALIDATE_DEGRADE_JPEG)")
+    parser.add_argument("--degrade-sinc", type=float, default=None, metavar="OMEGA",
+                        help="also take that input through the sinc low-pass filter at cutoff OMEGA in (0, pi], before the JPEG stage "
+                             "(DATA.VALIDATE_DEGRADE_SINC)")
     a = parser.parse_args()
     cfg = Config()
     if a.name:
@@ -282,4 +325,5 @@ if __name__ == "__main__":
         cfg.DATA.TEST_LR_IMAGES_DIR = f"/work3/{cfg.EXP.USER}/data/{a.test_set}/LRbicx4"
     test(cfg, save_images=not a.no_images, g_path=a.g_path, on_device=True if a.on_device else None,
          with_st=True if a.st else None, tile=a.tile, with_lr=True if a.lr_consistency else None,
-         degrade=tuple(float(v) for v in a.degrade.split(",")) if a.degrade else None, degrade_jpeg=a.degrade_jpeg)
+         degrade=tuple(float(v) for v in a.degrade.split(",")) if a.degrade else None, degrade_jpeg=a.degrade_jpeg,
+         degrade_sinc=a.degrade_sinc)

@@ -35,6 +35,13 @@ difference between two legs).  Prints one JSON line.
         # 30..95.  Legs: sst_gather_crops_degraded alone (and, with --parent-lib, through another build of the library in the same
         # process); the same followed by sst_jpeg in 444 and in 420; sst_jpeg alone on the LR buffer; and the degraded gather followed
         # by the same codec as torch int32 ops on the device (torch_jpeg, checked against the kernel bit for bit first) - the yardstick
+    python tools/time_loader.py second [--launches L] [--replays R] [--repeat N] [--parent-lib PATH [--parent-first]]
+        # the second-order stage (DATA.DEGRADE_SECOND), same sizes and method, every sample with all stages on (first stage: blur
+        # K = 21, noise, JPEG 420; second stage: blur 2, noise 2, the final sinc, JPEG).  Legs: the off path = the degraded gather and
+        # its sst_jpeg (and, with --parent-lib, the same two launches through another build of the library in the same process); each
+        # added launch alone on the LR buffers (pass A, pass B, the second sst_jpeg, pass C); the whole second-order batch as the
+        # loader issues it; and the same pipeline behind the same first stage as torch ops (F.pad(reflect), grouped conv2d with the
+        # per-sample weights, randn, clamp, round, torch_jpeg) - the yardstick
 """
 import argparse
 import json
@@ -448,7 +455,152 @@ def jpeg_mode(launches, replays, repeat, parent_lib, parent_first=False):
     print(json.dumps(out))
 
 
+def second_mode(launches, replays, repeat, parent_lib, parent_first=False):
+    import ctypes
+    from srganst import _abi
+    from srganst.device_data import Degradation, DeviceImageArena, SecondOrder, filter2d, jpeg, second_order
+    g = torch.Generator().manual_seed(0)
+    imgs = [torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8) for h, w in WHOLE_SIZES * 2]
+    arena = DeviceImageArena.from_arrays(imgs, HR, HR, UP, "cuda")
+    n, K, o = launches * B, 21, HR // UP
+    tiles = torch.from_numpy(arena.tiles)[torch.randperm(len(arena), generator=g)[:n]]
+    room = torch.from_numpy(arena.table_host[tiles[:, 0].numpy(), 1:3] - HR + 1)
+    desc = torch.zeros(n, 4, dtype=torch.int32)
+    desc[:, 0] = tiles[:, 0]
+    desc[:, 1:3] = (torch.randint(0, 1 << 30, (n, 2), generator=g) % room).to(torch.int32)
+    desc[:, 3] = torch.randint(0, 8, (n,), generator=g).to(torch.int32)
+    arena.check_desc(desc.numpy())
+    desc = desc.cuda()
+    deg = Degradation(jpeg_prob=1.0).draw(n, torch.Generator().manual_seed(1)).cuda()
+    so = SecondOrder(blur_prob=1.0, noise_prob=1.0, final_sinc_prob=1.0, jpeg_prob=1.0, ksize=K)
+    rows_host = so.draw(n, torch.Generator().manual_seed(2))
+    bank_host = so.draw_bank(torch.Generator().manual_seed(3))
+    rows, bank = rows_host.cuda(), torch.from_numpy(bank_host).cuda()
+    gt, lr = torch.empty(B, 3, HR, HR, device="cuda"), torch.empty(B, 3, o, o, device="cuda")
+    s0, s1 = torch.empty_like(lr), torch.empty_like(lr)
+    sl = lambda k: slice(k * B, (k + 1) * B)
+
+    def off(k):
+        arena.crops(desc[sl(k)], gt, lr, deg=deg[sl(k)], ksize=K, jpeg_chroma="420")
+
+    def whole(k):
+        arena.crops(desc[sl(k)], gt, s0, deg=deg[sl(k)], ksize=K, jpeg_chroma="420")
+        second_order(s0, rows[:, sl(k)], bank, "420", out=lr, scratch=(s1, s0))
+
+    # ---- the comparator's constants, made beforehand: not part of the timed work.  A pass a sample does not take (B or C) is the
+    # identity kernel there, so that the torch pipeline is the same ops for every sample
+    p = K // 2
+    ident = torch.zeros(K, K)
+    ident[p, p] = 1.0
+    table = torch.cat([torch.from_numpy(bank_host), ident[None]]).cuda()
+    wts = [table[rows_host[j, :, 0].long()].repeat_interleave(3, 0)[:, None].contiguous() for j in (0, 1, 3)]     # idx -1: the last
+    sn, sp = (rows[0, :, j].contiguous().view(torch.float32)[:, None, None, None] for j in (1, 2))
+    gray = rows[0, :, 3].bool()[:, None, None, None]
+    tabs = (ctypes.c_int * 128)()
+    q_all = []
+    for Q in rows_host[2, :, 6].tolist():
+        _abi.check(_abi.lib().sst_jpeg_tables(Q, tabs), "sst_jpeg_tables")
+        q_all.append(list(tabs))
+    q_all = torch.tensor(q_all, dtype=torch.int32).reshape(n, 2, 1, 1, 8, 8).cuda()
+    on = torch.ones(n, dtype=torch.bool, device="cuda")
+    u, x = np.arange(8.0)[:, None], np.arange(8.0)[None, :]
+    C = 0.5 * np.cos((2 * x + 1) * u * np.pi / 16)
+    C[0] = np.sqrt(0.125)
+    T = torch.from_numpy(np.rint(8192 * C).astype(np.int32)).cuda()
+    pad, conv2d = torch.nn.functional.pad, torch.nn.functional.conv2d
+
+    def conv(v, w, k):
+        v = pad(v, (p, p, p, p), mode="reflect").reshape(1, B * 3, o + 2 * p, o + 2 * p)
+        return conv2d(v, w[k * B * 3:(k + 1) * B * 3], groups=B * 3).reshape(B, 3, o, o)
+
+    def grid(v):
+        return torch.round(v.clamp(0, 1) * 255) / 255
+
+    def torch_leg(k):
+        arena.crops(desc[sl(k)], gt, s0, deg=deg[sl(k)], ksize=K, jpeg_chroma="420")
+        v = conv(s0, wts[0], k)
+        z = torch.randn(B, 3, o, o, device="cuda")
+        z = torch.where(gray[sl(k)], z[:, :1], z)
+        v = grid(v + torch.sqrt(sp[sl(k)] * v.clamp(min=0) + sn[sl(k)] ** 2) * z)
+        v = grid(conv(v, wts[1], k))
+        v = torch_jpeg(v, q_all[sl(k), 0], q_all[sl(k), 1], on[sl(k)], 1, T)
+        lr.copy_(grid(conv(v, wts[2], k)))
+
+    # the comparator is the kernel's model: without noise (the two draw different normals) passes A and B of the two pipelines agree
+    # but for pixels whose rounding the summation order decides
+    quiet = rows.clone()
+    quiet[0, :, 1:3] = 0
+    arena.crops(desc[sl(0)], gt, s0, deg=deg[sl(0)], ksize=K, jpeg_chroma="420")
+    want = filter2d(filter2d(s0, quiet[0, sl(0)], bank), quiet[1, sl(0)], bank)
+    differ = float((((grid(conv(grid(conv(s0, wts[0], 0)), wts[1], 0)) - want).abs() * 255) > 0.5).float().mean())
+    assert differ < 0.05, f"the torch pipeline and sst_filter2d differ on {differ:.3f} of the pixels"
+
+    legs = {"off_degraded_jpeg": off}
+    if parent_lib:
+        other = ctypes.CDLL(parent_lib)
+        for name in ("sst_gather_crops_degraded", "sst_jpeg"):
+            getattr(other, name).restype, getattr(other, name).argtypes = _abi.SIGNATURES[name]
+        wy, iy, wx, ix = arena._bicubic.tables_i32(HR, HR, 1.0 / UP, arena.device)
+
+        def parent(k):
+            d = deg[sl(k)]
+            rc = other.sst_gather_crops_degraded(arena.arena.data_ptr(), arena.arena.numel(), arena.table.data_ptr(), arena.n_images,
+                                                 desc[sl(k)].data_ptr(), B, HR, arena.lut.data_ptr(), gt.data_ptr(), lr.data_ptr(),
+                                                 wy.data_ptr(), iy.data_ptr(), wx.data_ptr(), ix.data_ptr(), o, o, wy.shape[1], wx.shape[1],
+                                                 arena.span(True, True), d.data_ptr(), K, 1, _abi.stream_ptr())
+            assert rc == 0, rc
+            rc = other.sst_jpeg(lr.data_ptr(), d.data_ptr(), B, o, o, 1, _abi.stream_ptr())
+            assert rc == 0, rc
+        legs["off_degraded_jpeg_parent_lib"] = parent
+        if parent_first:                                 # the same two legs in the other order: what the order alone is worth
+            legs = {"off_degraded_jpeg_parent_lib": parent, "off_degraded_jpeg": off}
+    off(0)
+    s0.copy_(lr)
+    for j, name in ((0, "pass_a_blur_noise"), (1, "pass_b_sinc_or_through"), (3, "pass_c_sinc_or_through")):
+        legs[name] = lambda k, j=j: filter2d(s0, rows[j, sl(k)], bank, out=s1)
+    legs["jpeg_2"] = lambda k: jpeg(s1, rows[2, sl(k)], "420", out=s1)
+    legs["second_order_batch"] = whole
+    legs["torch_ops_batch"] = torch_leg
+
+    graphs = {}
+    for name, run in legs.items():
+        for k in range(min(3, launches)):               # warm up: tables, code objects, the allocator's pool
+            run(k)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for k in range(launches):
+                run(k)
+        gr.replay()
+        graphs[name] = gr
+    torch.cuda.synchronize()
+    out = {"mode": "second", "batch": B, "hr": HR, "scale": UP, "launches_per_graph": launches, "replays": replays, "repeat": repeat,
+           "torch_ops_pixels_off_by_a_level": round(differ, 5),
+           "us_per_batch": {name: [] for name in legs}}
+    for _ in range(repeat):
+        for name, gr in graphs.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(replays):
+                gr.replay()
+            t1.record()
+            torch.cuda.synchronize()
+            out["us_per_batch"][name].append(round(t0.elapsed_time(t1) * 1e3 / (replays * launches), 2))
+    out["median_us_per_batch"] = {name: sorted(v)[len(v) // 2] for name, v in out["us_per_batch"].items()}
+    print(json.dumps(out))
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "second":
+        ap = argparse.ArgumentParser()
+        ap.add_argument("mode")
+        ap.add_argument("--launches", type=int, default=32)
+        ap.add_argument("--replays", type=int, default=50)
+        ap.add_argument("--repeat", type=int, default=5)
+        ap.add_argument("--parent-lib", default="", help="another build of libsrganst.so whose off path is timed beside this one's")
+        ap.add_argument("--parent-first", action="store_true", help="time the parent library's leg before this library's")
+        a = ap.parse_args()
+        return second_mode(a.launches, a.replays, a.repeat, a.parent_lib, a.parent_first)
     if len(sys.argv) > 1 and sys.argv[1] == "jpeg":
         ap = argparse.ArgumentParser()
         ap.add_argument("mode")
