@@ -546,6 +546,26 @@ int sst_jpeg_tables(int quality, int* out128);
  * launch, no allocation, no sync (capturable). */
 int sst_filter2d(const float* x, float* y, const int* flt, const float* bank, int M, int B, int h, int w, int K, int quantise,
                  void* stream);
+/* ---- the random resize round trip of the second-order stage (device_data.py: rescale / SecondOrder(resize_prob=...);
+ * csrc/resize.hip): per sample, resample to an intermediate size (hi, wi), add noise there, resample back to
+ * (h, w), clamp and the 1/255 grid, out of place: x, y fp32 [B,3,h,w] (h, w in 1..8192; y == x is refused).  rows int32 [B,8]
+ * (device, 32-byte aligned), per sample: hi, wi (0, 0: no resize), the fp32 bits of sigma_n, the fp32 bits of the shot coefficient
+ * s_p, the Philox key k0, k1, m1 | m2 << 2 | gray << 4 (m1: the mode of the resize to (hi, wi), m2: of the resize back; 0 area,
+ * 1 bilinear, 2 bicubic), a zero word.  Per sample:
+ *   pass-through  hi == wi == 0 && sigma_n == 0 && s_p == 0: y = the bits of x
+ *   one axis n_in -> n_out, output index i, in integer arithmetic:  area: taps a = i n_in / n_out up to b = ((i + 1) n_in + n_out - 1)
+ *          / n_out (exclusive), each 1 / (b - a).  num = (2i + 1) n_in - n_out, den = 2 n_out, f = floor(num / den), t = float(num -
+ *          f den) / float(den);  bilinear (align_corners = False, no antialias): num < 0 gives f = t = 0, taps min(f, n_in - 1),
+ *          min(f + 1, n_in - 1) with 1 - t, t;  bicubic (A = -0.75): taps clamp(f - 1 .. f + 2, 0, n_in - 1) with torch's cubic
+ *          convolution coefficients of t.  At n_out == n_in every mode is the identity
+ *   u      u[Y][X] = sum_j wy[j] (sum_i wx[i] x[iy_j][ix_i]), each sum one fp32 fmaf chain from 0.f in tap order (0, 0: u = x)
+ *   noise  (sigma_n != 0 || s_p != 0)  sst_filter2d's rule on u, e = c hi wi + Y wi + X, or Y wi + X with the gray flag (0, 0: h, w
+ *          stand in for hi, wi); the intermediate is neither clamped nor rounded
+ *   back   (hi, wi) -> (h, w) with m2 by the same rule on u; then clamp and quantise as sst_filter2d does (quantise = 0: the raw value)
+ * Exactly one of hi, wi zero, a negative one, 4 hi < h, hi > 2 h (the same for wi against w), a mode 3, a bit above bit 4 of word 6,
+ * !(sigma_n >= 0) or !(s_p >= 0) makes that sample NaN and touches no other.  No atomics: a result is a function of its sample's
+ * inputs alone, whatever the batch position, batch size and tile geometry.  One launch, no allocation, no sync (capturable). */
+int sst_rescale(const float* x, float* y, const int* rows, int B, int h, int w, int quantise, void* stream);
 /* Validation metrics of validate.image_metrics on the device (metrics.py), rounding for rounding: sr, hr fp32 NCHW [B,3,H,W] RGB;
  * out fp64 [B,2] = (MSE of the Y channel on the 0..255 scale over all H*W pixels, mean of the SSIM map over its (H-10) x (W-10)
  * valid region); sr_u8 / hr_u8: uint8 [B,H,W,3] BGR = tensor2img of each image (either may be null).  workspace:

@@ -154,6 +154,18 @@ class Config:
         # after degrade(gt) (or the plain bicubic LR made from gt) and before the VALIDATE_DEGRADE_JPEG stage; the printed line says
         # so.  None: off
         self.DATA.VALIDATE_DEGRADE_SINC = None
+        # with DEGRADE_SECOND: the random resize of Real-ESRGAN's second stage (sst_rescale).  Between blur 2 and
+        # the final sinc / JPEG a sample is, with the probabilities RESIZE_PROB = (up, down, keep), resized to a scale uniform in
+        # [1, RESIZE_RANGE[1]] or [RESIZE_RANGE[0], 1] with a mode uniform in RESIZE_MODES, gets noise 2 at THAT size, and is resized back
+        # to the LR size with a mode drawn independently.  The draws come from a fourth private generator: all others stay as they are
+        self.DATA.DEGRADE2_RESIZE = False
+        self.DATA.DEGRADE2_RESIZE_PROB = (0.3, 0.4, 0.3)
+        self.DATA.DEGRADE2_RESIZE_RANGE = (0.3, 1.2)
+        self.DATA.DEGRADE2_RESIZE_MODES = ("area", "bilinear", "bicubic")
+        # s in [0.25, 2]: validation's input also goes through the resize round trip at this scale, bicubic both ways, no noise - after
+        # degrade(gt) (or the plain bicubic LR made from gt) and before the VALIDATE_DEGRADE_SINC stage; the printed line says so.
+        # None: off
+        self.DATA.VALIDATE_DEGRADE_RESIZE = None
 
         self.MODEL = dotdict()
         self.MODEL.G_CONTINUE_FROM_WARMUP = False

@@ -545,6 +545,99 @@ def filter2d(x: Tensor, flt: Tensor, bank: Tensor | None, quantise: bool = True,
     return out
 
 
+# ---- the random resize round trip inside the second stage (DATA.DEGRADE2_RESIZE; csrc/resize.hip)
+_RESIZE_STREAM = 0x1F83D9ABFB41BD6B       # keeps the loader's resize generator apart from its three others
+RESIZE_MODES = {"area": 0, "bilinear": 1, "bicubic": 2}
+RESIZE_MAX_RATIO, RESIZE_MIN_DIV = 2, 4   # sst_rescale's limits on an intermediate size: h <= 4 hi and hi <= 2 h
+
+
+def resize_size(n: int, s: float) -> int:
+    """The intermediate length of an axis of n pixels at scale s: int(n s), at least ceil(n / 4)."""
+    return max(int(n * s), -(-n // RESIZE_MIN_DIV))
+
+
+def rescale_size_ok(hi: int, wi: int, h: int, w: int) -> bool:
+    """True when sst_rescale takes the intermediate size (hi, wi) on an [h, w] image: 0, 0 (no resize), or both within
+    [ceil(n / 4), 2 n] of their axis."""
+    if hi == 0 and wi == 0:
+        return True
+    return (hi > 0 and wi > 0 and RESIZE_MIN_DIV * hi >= h and hi <= RESIZE_MAX_RATIO * h and RESIZE_MIN_DIV * wi >= w
+            and wi <= RESIZE_MAX_RATIO * w)
+
+
+def rescale_rows(size, modes, noise255, shot, gray, keys) -> np.ndarray:
+    """The rows of sst_rescale, int32 [n, 8], n = the number of keys [n, 2]: per sample the intermediate size (`size`: None or 0 for
+    no resize in any sample, else per sample None, 0 or (hi, wi)), the pair of mode names (`modes`: one pair for all, or a pair per
+    sample; "area" | "bilinear" | "bicubic"; the first for the resize to (hi, wi), the second for the resize back), then filter_rows'
+    noise arguments: the Gaussian noise's standard deviation in 0..255 units (stored / 255), the shot coefficient, the gray flag and
+    the Philox key.  Word 6 is m1 | m2 << 2 | gray << 4, word 7 zero."""
+    keys = np.asarray(keys, np.int64).reshape(-1, 2) & 0xFFFFFFFF
+    n = len(keys)
+    nz, sp = (np.broadcast_to(np.asarray(a, np.float64), (n,)) for a in (noise255, shot))
+    gr = np.broadcast_to(np.asarray(gray), (n,))
+    if not (np.isfinite(nz).all() and (nz >= 0).all() and np.isfinite(sp).all() and (sp >= 0).all()):
+        raise ValueError("rescale_rows: noise255 and shot must be finite and >= 0")
+    if not np.isin(gr, (0, 1)).all():
+        raise ValueError("rescale_rows: gray must be 0 or 1")
+    sizes = np.zeros((n, 2), np.int64)
+    none = lambda s: s is None or (isinstance(s, (int, np.integer)) and s == 0)
+    if not none(size):
+        if len(size) != n:
+            raise ValueError(f"rescale_rows: {len(size)} sizes for {n} keys")
+        for i, s in enumerate(size):
+            if none(s):
+                continue
+            if np.ndim(s) != 1 or len(s) != 2 or any(int(v) != v for v in s):
+                raise ValueError(f"rescale_rows: a size must be None, 0 or a pair of integers (hi, wi), got {s!r}")
+            sizes[i] = (int(s[0]), int(s[1]))
+    if (sizes < 0).any() or (sizes > 0x7FFFFFFF).any() or ((sizes[:, 0] == 0) != (sizes[:, 1] == 0)).any():
+        raise ValueError("rescale_rows: an intermediate size must be two positive integers, or 0, 0 (no resize)")
+    modes = [modes] * n if len(modes) == 2 and all(isinstance(m, str) for m in modes) else list(modes)
+    if len(modes) != n:
+        raise ValueError(f"rescale_rows: {len(modes)} mode pairs for {n} keys")
+    for pair in modes:
+        if len(pair) != 2 or pair[0] not in RESIZE_MODES or pair[1] not in RESIZE_MODES:
+            raise ValueError(f"rescale_rows: modes must be pairs of {tuple(RESIZE_MODES)}, got {pair!r}")
+    rows = np.zeros((n, 8), np.int32)
+    rows[:, 0:2] = sizes
+    rows[:, 2] = (nz / 255.0).astype(np.float32).view(np.int32)
+    rows[:, 3] = sp.astype(np.float32).view(np.int32)
+    rows[:, 4:6] = keys.astype(np.uint32).view(np.int32)
+    rows[:, 6] = [RESIZE_MODES[a] | RESIZE_MODES[b] << 2 for a, b in modes]
+    rows[:, 6] |= gr.astype(np.int32) << 4
+    return rows
+
+
+def rescale(x: Tensor, rows: Tensor, quantise: bool = True, out: Tensor | None = None) -> Tensor:
+    """ONE sst_rescale launch on the current stream: the resize round trip alone on an fp32 batch x [B,3,h,w] (h, w <= 8192) with the
+    rows int32 [B,8] (rescale_rows) -> a new tensor, or `out` (contiguous fp32 of x's shape; never x itself).  Per sample: resample
+    to its intermediate size with its first mode, noise there, resample back to (h, w) with its second mode, clamp to [0, 1] and the
+    1/255 grid; a row with neither a size nor noise keeps the sample's bits.  quantise=False (tests and tools) returns the unclamped,
+    unrounded values.  rows on x's device are taken as they are (a size outside the kernel's limits makes that sample NaN); rows on
+    the host are checked first - a size outside [ceil(n / 4), 2 n] of its axis raises - and then uploaded."""
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_cuda:
+        raise ValueError(f"rescale: x must be fp32 [B, 3, h, w] on a ROCm device, got {x.dtype} {tuple(x.shape)} on {x.device}")
+    B, _, h, w = x.shape
+    if rows.device.type == "cpu" and rows.dtype == torch.int32 and tuple(rows.shape) == (B, 8):
+        for b, (hi, wi) in enumerate(rows[:, :2].tolist()):
+            if not rescale_size_ok(hi, wi, h, w):
+                raise ValueError(f"rescale: row {b}: the intermediate size {hi}x{wi} (rows x columns) must be 0, 0 or within "
+                                 f"[ceil(n / {RESIZE_MIN_DIV}), {RESIZE_MAX_RATIO} n] of each axis of the {h}x{w} image")
+        rows = rows.contiguous().to(x.device)
+    _check_deg(rows, B, x.device, "rescale")
+    if out is None:
+        out = torch.empty(B, 3, h, w, device=x.device)
+    else:
+        if out is x or out.data_ptr() == x.data_ptr():
+            raise ValueError("rescale: out must not be x (a tile reads its neighbours' pixels: out of place only)")
+        if out.dtype != torch.float32 or tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or out.device != x.device:
+            raise ValueError(f"rescale: out must be contiguous fp32 {tuple(x.shape)} on {x.device}, got {out.dtype} {tuple(out.shape)}")
+    x = x.contiguous()
+    _abi.check(_abi.lib().sst_rescale(_abi.ptr(x), _abi.ptr(out), _abi.ptr(rows), B, h, w, int(bool(quantise)), _abi.stream_ptr()),
+               "sst_rescale")
+    return out
+
+
 def _range(v, name: str, lo_min: float = 0.0, strict: bool = False):
     a, b = float(v[0]), float(v[1])
     if not ((lo_min < a if strict else lo_min <= a) and a <= b and np.isfinite(b)):
@@ -565,13 +658,20 @@ class SecondOrder:
     (sinc_prob) or of one of the six families of family_prob (iso / aniso Gaussian, generalised Gaussian, plateau) with standard
     deviations uniform in blur_sigma at a uniform angle, on a window `support` that is odd and uniform in 7..ksize; then
     sinc_bank_size final-sinc kernels.  draw(n, generator) -> int32 [4, n, 8] on the host: the rows of A, B, J (word 6: the quality,
-    as sst_jpeg reads it) and C.  SecondOrder.fixed(...) draws the same bank and rows every time (validation, tests)."""
+    as sst_jpeg reads it) and C.  SecondOrder.fixed(...) draws the same bank and rows every time (validation, tests).
+    resize_prob = (up, down, keep), three probabilities that sum to 1 (Real-ESRGAN's second stage: (0.3, 0.4, 0.3); None: no resize,
+    and every draw is the one made without these arguments): between A's blur and B the sample makes a resize round trip R
+    (sst_rescale) - to an intermediate size at a scale uniform in [1, resize_range[1]] (up) or [resize_range[0], 1] (down), the same
+    on both axes, with a mode uniform in resize_modes, then noise 2 THERE, then back to the LR size with a mode drawn independently.
+    draw() then leaves A's noise words zero (keep_noise=True: as drawn), and draw_resize(n, h, w, generator, noise=A's rows as drawn)
+    -> int32 [n, 8] makes the rows of R with that noise in them: the noise parameters of a sample are the ones drawn without resize."""
 
     def __init__(self, blur_prob: float = 0.8, blur_sigma=(0.2, 1.5), family_prob=(0.45, 0.25, 0.12, 0.03, 0.12, 0.03),
                  beta_gaussian=(0.5, 4.0), beta_plateau=(1.0, 2.0), sinc_prob: float = 0.1, noise_prob: float = 1.0,
                  noise_sigma=(1.0, 25.0), shot=(1e-5, 0.025), shot_prob: float = 0.5, gray_prob: float = 0.4,
                  final_sinc_prob: float = 0.8, omega=(np.pi / 3, np.pi), sinc_first_prob: float = 0.5, jpeg_quality=(30, 95),
-                 jpeg_prob: float = 1.0, ksize: int = 21, bank_size: int = 1024, sinc_bank_size: int = 256, jpeg_chroma: str = "420"):
+                 jpeg_prob: float = 1.0, ksize: int = 21, bank_size: int = 1024, sinc_bank_size: int = 256, jpeg_chroma: str = "420",
+                 resize_prob=None, resize_range=(0.3, 1.2), resize_modes=("area", "bilinear", "bicubic")):
         self.blur_sigma = _range(blur_sigma, "blur_sigma", strict=True)
         self.beta_gaussian = _range(beta_gaussian, "beta_gaussian", strict=True)
         self.beta_plateau = _range(beta_plateau, "beta_plateau", strict=True)
@@ -597,6 +697,16 @@ class SecondOrder:
             raise ValueError(f"SecondOrder: ksize {ksize} must be odd and in 3..21")
         if self.bank_size < 1 or self.sinc_bank_size < 1:
             raise ValueError(f"SecondOrder: bank_size {bank_size} and sinc_bank_size {sinc_bank_size} must be positive")
+        self.resize_prob = None if resize_prob is None else tuple(float(v) for v in resize_prob)
+        if self.resize_prob is not None and (len(self.resize_prob) != 3 or min(self.resize_prob) < 0
+                                             or abs(sum(self.resize_prob) - 1) > 1e-9):
+            raise ValueError(f"SecondOrder: resize_prob {tuple(resize_prob)} must be three probabilities (up, down, keep) that sum to 1")
+        self.resize_range = (float(resize_range[0]), float(resize_range[1]))
+        if not 0 < self.resize_range[0] <= 1 <= self.resize_range[1] <= RESIZE_MAX_RATIO:
+            raise ValueError(f"SecondOrder: resize_range {tuple(resize_range)} must be 0 < lo <= 1 <= hi <= {RESIZE_MAX_RATIO}")
+        self.resize_modes = tuple(resize_modes)
+        if not self.resize_modes or any(m not in RESIZE_MODES for m in self.resize_modes):
+            raise ValueError(f"SecondOrder: resize_modes {tuple(resize_modes)} must be names of {tuple(RESIZE_MODES)}")
         self._fixed = None
 
     @property
@@ -604,15 +714,27 @@ class SecondOrder:
         """True when a row this draws can hold a JPEG quality: the loader then issues the stage's sst_jpeg launch."""
         return self._fixed["jpeg"] > 0 if self._fixed else self.jpeg_prob > 0
 
+    @property
+    def has_resize(self) -> bool:
+        """True when the stage has the resize round trip R: the loader then issues the sst_rescale launch after A."""
+        return self._fixed.get("resize") is not None if self._fixed else self.resize_prob is not None
+
     @classmethod
     def fixed(cls, kernel=None, noise: float = 0.0, shot: float = 0.0, gray: bool = False, key=0, sinc_omega: float | None = None,
-              sinc_first: bool = True, jpeg: int = 0, ksize: int = 21, jpeg_chroma: str = "420") -> "SecondOrder":
+              sinc_first: bool = True, jpeg: int = 0, ksize: int = 21, jpeg_chroma: str = "420", resize=None) -> "SecondOrder":
         """Every sample gets these: the blur kernel (a [ksize, ksize] table; None: no blur), the noise's standard deviation in 0..255
         units and shot coefficient, the gray flag, the key (an int: the low and high 32 bits; or a pair of words), the final sinc
-        filter's cutoff (None: none) before (sinc_first) or after the JPEG pass, and the JPEG quality (0: none)."""
+        filter's cutoff (None: none) before (sinc_first) or after the JPEG pass, the JPEG quality (0: none), and the resize round
+        trip (None: none; (s, m1, m2): to the scale s in [0.25, 2] with the mode m1, the noise there, back with m2)."""
         from . import kernels
         if int(jpeg) != jpeg or not 0 <= jpeg <= 100:
             raise ValueError(f"SecondOrder.fixed: the JPEG quality {jpeg!r} must be an integer in 0..100 (0: none)")
+        if resize is not None:
+            if len(resize) != 3 or not 1 / RESIZE_MIN_DIV <= float(resize[0]) <= RESIZE_MAX_RATIO or resize[1] not in RESIZE_MODES \
+                    or resize[2] not in RESIZE_MODES:
+                raise ValueError(f"SecondOrder.fixed: resize {resize!r} must be (s, m1, m2), s in [{1 / RESIZE_MIN_DIV}, "
+                                 f"{RESIZE_MAX_RATIO}], the modes of {tuple(RESIZE_MODES)}")
+            resize = (float(resize[0]), resize[1], resize[2])
         d = cls(ksize=ksize, jpeg_chroma=jpeg_chroma)
         tables = []
         if kernel is not None:
@@ -627,7 +749,7 @@ class SecondOrder:
         d._fixed = dict(bank=kernels.bank(tables) if tables else np.zeros((0, d.ksize, d.ksize), np.float32),
                         blur=0 if kernel is not None else -1, sinc=-1 if sinc_omega is None else len(tables) - 1,
                         noise=float(noise), shot=float(shot), gray=int(bool(gray)), key=k, sinc_first=bool(sinc_first), jpeg=int(jpeg),
-                        omega=sinc_omega)
+                        omega=sinc_omega, resize=resize)
         return d
 
     def __repr__(self) -> str:
@@ -635,13 +757,15 @@ class SecondOrder:
             f = self._fixed
             return (f"SecondOrder.fixed(kernel={'a table' if f['blur'] >= 0 else None}, noise={f['noise']:g}, shot={f['shot']:g}, "
                     f"gray={bool(f['gray'])}, key={f['key']}, sinc_omega={f['omega']}, sinc_first={f['sinc_first']}, jpeg={f['jpeg']}, "
-                    f"ksize={self.ksize})")
+                    f"ksize={self.ksize}" + (f", resize={f['resize']}" if f.get("resize") else "") + ")")
+        rs = (f", resize_prob={self.resize_prob}, resize_range={self.resize_range}, resize_modes={self.resize_modes}"
+              if self.resize_prob is not None else "")
         return (f"SecondOrder(blur_prob={self.blur_prob:g}, blur_sigma={self.blur_sigma}, family_prob={self.family_prob}, "
                 f"beta_gaussian={self.beta_gaussian}, beta_plateau={self.beta_plateau}, sinc_prob={self.sinc_prob:g}, "
                 f"noise_prob={self.noise_prob:g}, noise_sigma={self.noise_sigma}, shot={self.shot}, shot_prob={self.shot_prob:g}, "
                 f"gray_prob={self.gray_prob:g}, final_sinc_prob={self.final_sinc_prob:g}, omega=({self.omega[0]:.4g}, {self.omega[1]:.4g}), "
                 f"sinc_first_prob={self.sinc_first_prob:g}, jpeg_quality={self.jpeg_quality}, jpeg_prob={self.jpeg_prob:g}, "
-                f"jpeg_chroma={self.jpeg_chroma!r}, ksize={self.ksize}, bank_size={self.bank_size}+{self.sinc_bank_size})")
+                f"jpeg_chroma={self.jpeg_chroma!r}, ksize={self.ksize}, bank_size={self.bank_size}+{self.sinc_bank_size}{rs})")
 
     def _support(self, u: float) -> int:
         lo = min(7, self.ksize)
@@ -677,7 +801,45 @@ class SecondOrder:
             tables.append(kernels.sinc(K, w0 + (w1 - w0) * u[m, 2], self._support(u[m, 1])))
         return kernels.bank(tables)
 
-    def draw(self, n: int, generator: torch.Generator | None = None) -> Tensor:
+    def draw_resize(self, n: int, h: int, w: int, generator: torch.Generator | None = None, noise=None) -> Tensor:
+        """The rows of R for n samples of an [h, w] LR batch, int32 [n, 8] (rescale_rows' layout).  Per sample the kind (up, down,
+        keep), then s uniform in [1, resize_range[1]] (up) or [resize_range[0], 1] (down), hi = max(int(h s), ceil(h / 4)) and wi
+        likewise from the same s, then m1 and m2 uniform in resize_modes, independently; keep writes 0, 0.  noise: A's rows as drawn
+        (draw(..., keep_noise=True)[0], filter_rows' layout) - their sigma, shot coefficient, gray flag and key go into the rows; a
+        sample that keeps its size, has no noise but a blur in A then gets the size (h, w), the exact identity, so that R still puts
+        it on the 1/255 grid, which A (launched unquantised beside R) no longer does."""
+        if not self.has_resize:
+            raise ValueError("SecondOrder.draw_resize: this stage has no resize (resize_prob is None)")
+        rows = np.zeros((n, 8), np.int32)
+        if self._fixed:
+            s, m1, m2 = self._fixed["resize"]
+            rows[:, 0], rows[:, 1], rows[:, 6] = resize_size(h, s), resize_size(w, s), RESIZE_MODES[m1] | RESIZE_MODES[m2] << 2
+        else:
+            u = torch.rand(n, 2, generator=generator, dtype=torch.float64).numpy()
+            pick = torch.randint(0, 1 << 62, (n, 2), generator=generator, dtype=torch.int64).numpy()
+            up, down, _ = self.resize_prob
+            lo, hi = self.resize_range
+            s = np.where(u[:, 0] < up, 1.0 + (hi - 1.0) * u[:, 1], lo + (1.0 - lo) * u[:, 1])
+            keep = u[:, 0] >= up + down
+            rows[:, 0] = np.where(keep, 0, [resize_size(h, v) for v in s])
+            rows[:, 1] = np.where(keep, 0, [resize_size(w, v) for v in s])
+            codes = np.array([RESIZE_MODES[m] for m in self.resize_modes], np.int32)
+            rows[:, 6] = np.where(keep, 0, codes[pick[:, 0] % len(codes)] | codes[pick[:, 1] % len(codes)] << 2)
+        if noise is not None:
+            a = np.asarray(noise, np.int32).reshape(n, 8)
+            rows[:, 2:4], rows[:, 4:6] = a[:, 1:3], a[:, 4:6]
+            rows[:, 6] |= (a[:, 3] & 1) << 4
+            bare = (rows[:, 0] == 0) & (a[:, 0] >= 0) & (a[:, 1] == 0) & (a[:, 2] == 0)
+            rows[bare, 0], rows[bare, 1] = h, w
+        return torch.from_numpy(rows)
+
+    def draw(self, n: int, generator: torch.Generator | None = None, keep_noise: bool = False) -> Tensor:
+        rows = self._draw(n, generator)
+        if self.has_resize and not keep_noise:
+            rows[0, :, 1:4] = 0                              # sigma, shot and gray: R adds this noise at its intermediate size
+        return torch.from_numpy(rows)
+
+    def _draw(self, n: int, generator) -> np.ndarray:
         rows = np.zeros((4, n, 8), np.int32)
         if self._fixed:
             f = self._fixed
@@ -686,7 +848,7 @@ class SecondOrder:
             rows[1, :, 0] = f["sinc"] if first else -1
             rows[2, :, 6] = f["jpeg"]
             rows[3, :, 0] = -1 if first else f["sinc"]
-            return torch.from_numpy(rows)
+            return rows
         u = torch.rand(n, 8, generator=generator, dtype=torch.float64).numpy()
         keys = torch.randint(0, 1 << 32, (n, 2), generator=generator, dtype=torch.int64).numpy()
         pick = torch.randint(0, 1 << 62, (n, 3), generator=generator, dtype=torch.int64).numpy()
@@ -702,7 +864,7 @@ class SecondOrder:
         q0, q1 = self.jpeg_quality
         rows[2, :, 6] = np.where(u[:, 7] < self.jpeg_prob, q0 + pick[:, 2] % (q1 - q0 + 1), 0)
         rows[3, :, 0] = np.where(first, -1, sinc)
-        return torch.from_numpy(rows)
+        return rows
 
     @classmethod
     def from_config(cls, config) -> "SecondOrder | None":
@@ -714,17 +876,30 @@ class SecondOrder:
                    d.DEGRADE2_SINC_PROB, d.DEGRADE2_NOISE_PROB, d.DEGRADE2_NOISE_SIGMA, d.DEGRADE2_SHOT, d.DEGRADE2_SHOT_PROB,
                    d.DEGRADE2_GRAY_PROB, d.DEGRADE2_FINAL_SINC_PROB, d.DEGRADE2_OMEGA, d.DEGRADE2_SINC_FIRST_PROB,
                    tuple(d.DEGRADE2_JPEG_QUALITY), d.DEGRADE2_JPEG_PROB, d.DEGRADE2_KSIZE, d.DEGRADE2_BANK_SIZE,
-                   d.DEGRADE2_SINC_BANK_SIZE, d.get("DEGRADE_JPEG_CHROMA", "420"))
+                   d.DEGRADE2_SINC_BANK_SIZE, d.get("DEGRADE_JPEG_CHROMA", "420"),
+                   tuple(d.get("DEGRADE2_RESIZE_PROB", (0.3, 0.4, 0.3))) if d.get("DEGRADE2_RESIZE", False) else None,
+                   tuple(d.get("DEGRADE2_RESIZE_RANGE", (0.3, 1.2))),
+                   tuple(d.get("DEGRADE2_RESIZE_MODES", ("area", "bilinear", "bicubic"))))
 
 
 def second_order(lr: Tensor, rows: Tensor, bank: Tensor | None, jpeg_chroma: str | None = "420", out: Tensor | None = None,
-                 scratch=None) -> Tensor:
+                 scratch=None, resize_rows: Tensor | None = None) -> Tensor:
     """The second stage on an LR batch on the 1/255 grid, as the loader issues it: filter2d with rows[0] (blur 2, noise 2), filter2d
     with rows[1] (the final sinc before JPEG), jpeg with rows[2] (jpeg_chroma None: no such launch), filter2d with rows[3] (the final
     sinc after it).  rows: int32 [4, B, 8] on lr's device (SecondOrder.draw).  The last launch writes `out`; scratch: two buffers of
     lr's shape for the passes between (allocated when None: lr is then left as it is; the second may be lr itself, as the loader has
-    it, and lr is then overwritten)."""
+    it, and lr is then overwritten).
+    resize_rows: int32 [B, 8] on lr's device (SecondOrder.draw_resize): five launches - filter2d with rows[0] UNQUANTISED (blur 2
+    alone: its noise words are zero), rescale with resize_rows (the resize round trip with noise 2 inside; its clamp and rounding are
+    the ones the first launch leaves out), then the three last launches as above, over the same two scratch buffers."""
     a, b = scratch if scratch is not None else (torch.empty_like(lr, memory_format=torch.contiguous_format) for _ in range(2))
+    if resize_rows is not None:
+        filter2d(lr, rows[0], bank, quantise=False, out=a)
+        rescale(a, resize_rows, out=b)
+        filter2d(b, rows[1], bank, out=a)
+        if jpeg_chroma is not None:
+            jpeg(a, rows[2], jpeg_chroma, out=a)
+        return filter2d(a, rows[3], bank, out=out)
     filter2d(lr, rows[0], bank, out=a)
     filter2d(a, rows[1], bank, out=b)
     if jpeg_chroma is not None:
@@ -934,7 +1109,11 @@ class DeviceCropLoader:
     last two (second_order()); the gather then writes a scratch buffer of the loader and the last launch the bound lr buffer.  The
     epoch's kernel bank is a function of (seed, epoch); the epoch's rows are drawn for ALL tiles from a THIRD private generator (seed,
     epoch and a constant of its own), so a tile's second stage depends on neither world size nor rank nor batch size, the window,
-    transform and first-stage draws are the ones made without it, and resuming at an epoch reproduces it."""
+    transform and first-stage draws are the ones made without it, and resuming at an epoch reproduces it.
+    A second stage that resizes (SecondOrder(resize_prob=...)) adds one sst_rescale launch per batch behind the first sst_filter2d;
+    the epoch's resize rows are drawn for ALL tiles from a FOURTH private generator (seed, epoch and a constant of its own), so a
+    tile's resize depends on neither world size nor rank nor batch size, the window, transform, first-stage, second-stage and bank
+    draws are the ones made without it, and resuming at an epoch reproduces it: nothing new goes into a checkpoint."""
 
     def __init__(self, arena: DeviceImageArena, batch_size: int, sampler=None, random_crop: bool = False, augment: bool = False,
                  seed: int = 0, degradation: Degradation | None = None, second: SecondOrder | None = None):
@@ -1000,14 +1179,31 @@ class DeviceCropLoader:
         rows = self.second.draw(len(self.dset), torch.Generator().manual_seed((base + _SECOND_STREAM) % (1 << 63))).numpy()
         return rows, self.second.draw_bank(torch.Generator().manual_seed((base + _SECOND_BANK_STREAM) % (1 << 63)))
 
+    def resize_draws(self, epoch: int) -> np.ndarray | None:
+        """The epoch's resize row of EVERY tile of the set, int32 [len(arena), 8] (SecondOrder.draw_resize); None without a second stage
+        that resizes.  The sizes and modes come from a FOURTH private generator (seed, epoch and a constant of its own); the noise
+        words are the ones the third generator draws for pass A, which second_draws() then hands out zeroed."""
+        if self.second is None or not self.second.has_resize:
+            return None
+        base, n, o = self.seed * 1000003 + epoch, len(self.dset), self.dset.out
+        full = self.second.draw(n, torch.Generator().manual_seed((base + _SECOND_STREAM) % (1 << 63)), keep_noise=True).numpy()
+        return self.second.draw_resize(n, o, o, torch.Generator().manual_seed((base + _RESIZE_STREAM) % (1 << 63)), noise=full[0]).numpy()
+
     def plan_all(self):
         """plan_both() and, in the same order, the second stage's rows int32 [4, len(self) * batch_size, 8] and bank (or None, None)."""
+        return self.plan_resize()[:4]
+
+    def plan_resize(self):
+        """plan_all() and, in the same order (ONE walk of the sampler for all five), the resize rows int32 [len(self) * batch_size, 8],
+        or None without a second stage that resizes."""
         order = np.fromiter(iter(self.sampler), dtype=np.int64)[: len(self) * self.batch_size]
         desc, deg = self._plan(order)
         if self.second is None:
-            return desc, deg, None, None
+            return desc, deg, None, None, None
         rows, bank = self.second_draws(self.epoch)
-        return desc, deg, torch.from_numpy(np.ascontiguousarray(rows[:, order])), torch.from_numpy(bank)
+        resize = self.resize_draws(self.epoch)
+        return (desc, deg, torch.from_numpy(np.ascontiguousarray(rows[:, order])), torch.from_numpy(bank),
+                None if resize is None else torch.from_numpy(np.ascontiguousarray(resize[order])))
 
     def plan_both(self):
         """The current epoch on the host, in the sampler's order (ONE walk of the sampler): the descriptors int32
@@ -1030,7 +1226,8 @@ class DeviceCropLoader:
 
     def __iter__(self):
         B = self.batch_size
-        host, host_deg, host_rows, host_bank = self.plan_all() if self.second is not None else (*self.plan_both(), None, None)
+        host, host_deg, host_rows, host_bank, host_resize = (self.plan_resize() if self.second is not None
+                                                             else (*self.plan_both(), None, None, None))
         self.epoch += 1
         dev = self.dset.device
         up = (lambda t: t.pin_memory().to(dev, non_blocking=True)) if dev.type == "cuda" else (lambda t: t)
@@ -1042,15 +1239,16 @@ class DeviceCropLoader:
         deg = up(host_deg)                                               # once per epoch, next to desc
         jpeg_chroma = self.degradation.jpeg_chroma if self.degradation.has_jpeg else None
         if self.second is not None:
-            yield from self._iter_second(desc, deg, jpeg_chroma, up(host_rows), up(host_bank) if host_bank.numel() else None)
+            yield from self._iter_second(desc, deg, jpeg_chroma, up(host_rows), up(host_bank) if host_bank.numel() else None,
+                                         None if host_resize is None else up(host_resize))
             return
         for k in range(len(self)):
             yield self.dset.crops(desc[k * B:(k + 1) * B], self._gt, self._lr, deg=deg[k * B:(k + 1) * B],
                                   ksize=self.degradation.ksize, jpeg_chroma=jpeg_chroma)
 
-    def _iter_second(self, desc, deg, jpeg_chroma, rows, bank):
+    def _iter_second(self, desc, deg, jpeg_chroma, rows, bank, resize=None):
         """The batches with the second stage: the gather (and its sst_jpeg) into a scratch buffer, then second_order() from it, the last
-        launch into the bound lr buffer - no copy."""
+        launch into the bound lr buffer - no copy.  resize: the epoch's resize rows (one more launch, sst_rescale, per batch)."""
         B, o, dev = self.batch_size, self.dset.out, self.dset.device
         if self._scratch is None or self._scratch[0].shape[0] != B:
             self._scratch = (torch.empty(B, 3, o, o, device=dev), torch.empty(B, 3, o, o, device=dev))
@@ -1061,12 +1259,13 @@ class DeviceCropLoader:
             gt, _ = self.dset.crops(desc[sl], self._gt, s0, deg=deg[sl], ksize=self.degradation.ksize, jpeg_chroma=jpeg_chroma)
             lr = self._lr if self._lr is not None else torch.empty(B, 3, o, o, device=dev)
             _expect(lr, (B, 3, o, o), "lr_out")
-            yield gt, second_order(s0, rows[:, sl], bank, chroma2, out=lr, scratch=(s1, s0))
+            yield gt, second_order(s0, rows[:, sl], bank, chroma2, out=lr, scratch=(s1, s0),
+                                   resize_rows=None if resize is None else resize[sl])
 
 
 def check_switches(config) -> None:
     """DATA.RANDOM_CROP, DATA.AUGMENT and DATA.DEGRADE are made by the whole-image gather only; DATA.DEGRADE_JPEG_PROB and
-    DATA.DEGRADE_SECOND follow DATA.DEGRADE."""
+    DATA.DEGRADE_SECOND follow DATA.DEGRADE; DATA.DEGRADE2_RESIZE follows DATA.DEGRADE_SECOND."""
     data = config.DATA
     if data.get("DEGRADE", False) and not data.get("ON_DEVICE_WHOLE_IMAGES", False):
         raise ValueError("DATA.DEGRADE needs DATA.ON_DEVICE_WHOLE_IMAGES = True: the per-sample blur and noise are made by the "
@@ -1079,13 +1278,16 @@ def check_switches(config) -> None:
         raise ValueError("DATA.DEGRADE_SECOND needs DATA.DEGRADE = True: the second-order stage (sst_filter2d, DESIGN.md section 23) works "
                          "on the first stage's quantised LR batch (set DEGRADE_BLUR_PROB = DEGRADE_NOISE_PROB = 0 for the second "
                          "stage alone)")
+    if data.get("DEGRADE2_RESIZE", False) and not data.get("DEGRADE_SECOND", False):
+        raise ValueError("DATA.DEGRADE2_RESIZE needs DATA.DEGRADE_SECOND = True: the random resize round trip (sst_rescale, DESIGN.md "
+                         "section 24) is a pass of the second-order stage, between its blur and its final sinc / JPEG")
     if (data.get("RANDOM_CROP", False) or data.get("AUGMENT", False)) and not data.get("ON_DEVICE_WHOLE_IMAGES", False):
         raise ValueError("DATA.RANDOM_CROP / DATA.AUGMENT need DATA.ON_DEVICE_WHOLE_IMAGES = True: the random window and the flips / "
                          "transposition are made by the whole-image gather (device_data.DeviceCropLoader), no other data path has them")
 
 
 def announce_degradation(config, degradation: Degradation, second: SecondOrder | None = None) -> None:
-    """The drivers' one log line for DATA.DEGRADE (one more with a JPEG stage, one more with the second-order stage), and a warning
+    """The drivers' one log line for DATA.DEGRADE (one more with a JPEG stage, one more with the second-order stage, one more with its resize), and a warning
     for every configured BackProjectionLoss(target="gt"): its target is the bicubic of gt, which is then not the LR image the generator
     saw (target="lr" takes the loader's)."""
     import warnings
@@ -1097,6 +1299,11 @@ def announce_degradation(config, degradation: Degradation, second: SecondOrder |
     if second is not None:
         print("[Data] DATA.DEGRADE_SECOND: then lr = sinc(jpeg(sinc(quantise(clamp(lr * k2 + n2))))) per sample (sst_filter2d x 3 around "
               f"sst_jpeg, kernels from a table drawn per epoch), {second!r}")
+        if second.has_resize:
+            print("[Data] DATA.DEGRADE2_RESIZE: with lr * k2 unquantised, then resize to a size per sample, n2 there, resize back, clamp, "
+                  "quantise (sst_rescale, one more launch between the first two sst_filter2d)"
+                  + ("" if second._fixed else f": (up, down, keep) = {second.resize_prob}, scale in {second.resize_range}, "
+                                              f"modes {second.resize_modes}"))
     loss = config.MODEL.G_LOSS
     for where in ("CRITERIONS", "WARMUP_CRITERIONS"):
         for name, crit in loss.get(where, {}).items():

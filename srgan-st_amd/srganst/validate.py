@@ -18,7 +18,10 @@ stage (device_data.jpeg, chroma DATA.DEGRADE_JPEG_CHROMA) at quality Q; without 
 of the plain bicubic LR made from gt.  The printed line and _metrics.txt name the quality.
 With config.DATA.VALIDATE_DEGRADE_SINC = omega (or degrade_sinc=omega, or --degrade-sinc OMEGA; 0 < omega <= pi) that input also goes
 through the sinc low-pass filter of the second-order degradation (device_data.filter2d with kernels.sinc at this cutoff, window
-DATA.DEGRADE2_KSIZE): after degrade(gt), or the plain bicubic LR made from gt, and before the JPEG stage.  The head line names it."""
+DATA.DEGRADE2_KSIZE): after degrade(gt), or the plain bicubic LR made from gt, and before the JPEG stage.  The head line names it.
+With config.DATA.VALIDATE_DEGRADE_RESIZE = s (or degrade_resize=s, or --degrade-resize S; 0.25 <= s <= 2) that input also goes through
+the resize round trip of the second-order degradation (device_data.rescale: bicubic to the scale s and bicubic back, no noise): after
+degrade(gt), or the plain bicubic LR made from gt, and before the sinc stage.  The head line names it."""
 from __future__ import annotations
 
 import argparse
@@ -106,18 +109,39 @@ def _sinc_param(config, degrade_sinc):
     return float(degrade_sinc)
 
 
+def _resize_param(config, degrade_resize):
+    """None, or the resize round trip's scale as a float in [0.25, 2]: the argument, else config.DATA.VALIDATE_DEGRADE_RESIZE."""
+    if degrade_resize is None:
+        degrade_resize = config.DATA.get("VALIDATE_DEGRADE_RESIZE", None)
+    if degrade_resize is None:
+        return None
+    if not 0.25 <= float(degrade_resize) <= 2:
+        raise ValueError(f"VALIDATE_DEGRADE_RESIZE: expected a scale in [0.25, 2], got {degrade_resize!r}")
+    return float(degrade_resize)
+
+
 _sinc_banks = {}
 
 
-def _degraded_input(hr_img, idx, config, degrade, jpeg=None, sinc=None):
-    """The generator's input under VALIDATE_DEGRADE / VALIDATE_DEGRADE_SINC / VALIDATE_DEGRADE_JPEG: degrade(hr) with the fixed
-    parameters and key = the image's index (without VALIDATE_DEGRADE: neither blur nor noise, the plain bicubic's bits), then the sinc
-    filter at cutoff sinc, then the JPEG stage at quality jpeg."""
+def _round_trip(lr, s):
+    """lr [1,3,h,w] through device_data.rescale at the scale s: bicubic to (max(int(h s), ceil(h / 4)), the same for w), bicubic
+    back, no noise; clamped and on the 1/255 grid."""
+    from .device_data import rescale, rescale_rows, resize_size
+    h, w = lr.shape[2:]
+    rows = rescale_rows([(resize_size(h, s), resize_size(w, s))], ("bicubic", "bicubic"), 0.0, 0.0, 0, [(0, 0)])
+    return rescale(lr, torch.from_numpy(rows))
+
+
+def _degraded_input(hr_img, idx, config, degrade, jpeg=None, sinc=None, resize=None):
+    """The generator's input under VALIDATE_DEGRADE / VALIDATE_DEGRADE_RESIZE / VALIDATE_DEGRADE_SINC / VALIDATE_DEGRADE_JPEG:
+    degrade(hr) with the fixed parameters and key = the image's index (without VALIDATE_DEGRADE: neither blur nor noise, the plain
+    bicubic's bits), then the resize round trip at scale resize (bicubic both ways, no noise), then the sinc filter at cutoff sinc,
+    then the JPEG stage at quality jpeg."""
     from .device_data import Degradation
     from .device_data import degrade as degrade_op
     ksize = int(config.DATA.get("DEGRADE_BLUR_KSIZE", 21))
     chroma = config.DATA.get("DEGRADE_JPEG_CHROMA", "420")
-    if sinc:
+    if sinc or resize:
         from . import kernels
         from .device_data import filter2d, filter_rows
         from .device_data import jpeg as jpeg_op
@@ -125,12 +149,15 @@ def _degraded_input(hr_img, idx, config, degrade, jpeg=None, sinc=None):
         deg = Degradation.fixed(*(degrade or (0.0, 0.0, 0.0, 0.0)), key=idx, ksize=ksize, jpeg=jpeg or 0, jpeg_chroma=chroma)
         rows = deg.draw(1).to(hr_img.device)
         lr = degrade_op(hr_img.to(torch.float32), rows, int(config.DATA.UPSCALE_FACTOR), ksize)
-        key = (str(hr_img.device), k2, sinc)
-        if key not in _sinc_banks:                           # the table and its one row: made once per (device, window, cutoff)
-            _sinc_banks[key] = (torch.from_numpy(kernels.bank([kernels.sinc(k2, sinc)])).to(hr_img.device),
-                                torch.from_numpy(filter_rows([0], 0.0, 0.0, 0, [(0, 0)])).to(hr_img.device))
-        bank, flt = _sinc_banks[key]
-        lr = filter2d(lr, flt, bank)
+        if resize:
+            lr = _round_trip(lr, resize)
+        if sinc:
+            key = (str(hr_img.device), k2, sinc)
+            if key not in _sinc_banks:                       # the table and its one row: made once per (device, window, cutoff)
+                _sinc_banks[key] = (torch.from_numpy(kernels.bank([kernels.sinc(k2, sinc)])).to(hr_img.device),
+                                    torch.from_numpy(filter_rows([0], 0.0, 0.0, 0, [(0, 0)])).to(hr_img.device))
+            bank, flt = _sinc_banks[key]
+            lr = filter2d(lr, flt, bank)
         return jpeg_op(lr, rows, chroma, out=lr) if jpeg else lr
     deg = Degradation.fixed(*(degrade or (0.0, 0.0, 0.0, 0.0)), key=idx, ksize=ksize, jpeg=jpeg or 0, jpeg_chroma=chroma)
     return degrade_op(hr_img.to(torch.float32), deg.draw(1).to(hr_img.device), int(config.DATA.UPSCALE_FACTOR), ksize,
@@ -138,7 +165,7 @@ def _degraded_input(hr_img, idx, config, degrade, jpeg=None, sinc=None):
 
 
 def _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params=None, with_lr=False, degrade=None,
-                       jpeg=None, sinc=None):
+                       jpeg=None, sinc=None, resize=None):
     """The per-image loop of _validate with everything on the device: generator forward -> sst_image_metrics into row idx of one
     [N,2] result buffer, ONE device-to-host copy after the loop.  Nothing syncs per image unless save_images is set (the uint8
     images tensor2img would make then cross per image and are written by _save_png).  st_params: also st_distance(output, hr) per
@@ -152,8 +179,8 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
         for idx, (hr_img, lr_img) in enumerate(val_loader):
             lr_img = lr_img.to(config.DEVICE, non_blocking=True)
             hr_img = hr_img.to(config.DEVICE, non_blocking=True)
-            if degrade or jpeg or sinc:
-                lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg, sinc)
+            if degrade or jpeg or sinc or resize:
+                lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg, sinc, resize)
             output = generator(lr_img)
             row = results[idx:idx + 1]
             if save_images:
@@ -174,13 +201,15 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
 
 
 def _validate(generator, val_loader, config, save_images=False, concat_with_gt=False, save_metrics=False, on_device=None,
-              with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None, degrade_sinc=None):
+              with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None, degrade_sinc=None, degrade_resize=None):
     """degrade: None = config.DATA.VALIDATE_DEGRADE; (sigma1, sigma2, theta_deg, noise) = the generator's input is degrade(hr)
     (_degraded_input) instead of the loader's LR image, and the printed line and _metrics.txt start by saying so.
     degrade_jpeg: None = config.DATA.VALIDATE_DEGRADE_JPEG; Q in 1..100 = that input, or without `degrade` the plain bicubic LR made
     from hr, goes through the JPEG stage at quality Q, and the head line names it.
     degrade_sinc: None = config.DATA.VALIDATE_DEGRADE_SINC; omega in (0, pi] = that input goes through the sinc filter at this cutoff
     before the JPEG stage, and the head line names it.
+    degrade_resize: None = config.DATA.VALIDATE_DEGRADE_RESIZE; s in [0.25, 2] = that input goes through the resize round trip at
+    this scale (bicubic both ways, no noise) before the sinc filter, and the head line names it.
     on_device: None = config.DATA.VALIDATE_ON_DEVICE; True = metrics by the HIP kernel, one host copy per pass
     (_metrics_on_device); False = the host loop below.  Same averages, same printed line, same _metrics.txt either way.
     with_st: None = config.DATA.VALIDATE_ST; True = every image also gets st.st_distance(output, hr) with the configured ``ST``
@@ -205,16 +234,17 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
     degrade = _degrade_params(config, degrade)
     jpeg = _jpeg_param(config, degrade_jpeg)
     sinc = _sinc_param(config, degrade_sinc)
-    deg_head = ""
+    resize = _resize_param(config, degrade_resize)
+    parts, made = [], "degrade(GT)" if degrade else "bicubic(GT)"               # the head line: what made the input, then its parameters
     if degrade:
-        deg_head = "LR = degrade(GT): sigma {:g} / {:g}, theta {:g} deg, noise {:g} | ".format(*degrade)
-    if sinc:
-        deg_head = (deg_head[:-3] + f", sinc cutoff {sinc:g} | " if degrade
-                    else f"LR = {'jpeg(sinc(bicubic(GT)))' if jpeg else 'sinc(bicubic(GT))'}: sinc cutoff {sinc:g} | ")
-    if jpeg:
-        chroma = config.DATA.get("DEGRADE_JPEG_CHROMA", "420")
-        deg_head = (deg_head[:-3] + f", JPEG quality {jpeg} ({chroma}) | " if degrade or sinc
-                    else f"LR = jpeg(bicubic(GT)): JPEG quality {jpeg} ({chroma}) | ")
+        parts.append("sigma {:g} / {:g}, theta {:g} deg, noise {:g}".format(*degrade))
+    for on, name, part in ((resize, "resize", f"resize round trip at scale {resize:g} (bicubic)" if resize else ""),
+                           (sinc, "sinc", f"sinc cutoff {sinc:g}" if sinc else ""),
+                           (jpeg, "jpeg", f"JPEG quality {jpeg} ({config.DATA.get('DEGRADE_JPEG_CHROMA', '420')})" if jpeg else "")):
+        if on:
+            parts.append(part)
+            made = made if degrade else f"{name}({made})"
+    deg_head = f"LR = {made}: {', '.join(parts)} | " if parts else ""
     file = None
     if save_metrics:
         path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
@@ -225,7 +255,7 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
     all_psnr, all_ssim, all_st, all_lr = [], [], [], []
     if on_device:
         all_psnr, all_ssim, all_st, all_lr = _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params,
-                                                                with_lr, degrade, jpeg, sinc)
+                                                                with_lr, degrade, jpeg, sinc, resize)
         if file:
             for idx, (psnr, ssim) in enumerate(zip(all_psnr, all_ssim)):
                 st_col = f" | ST: {all_st[idx]:.4f}" if with_st else ""
@@ -236,8 +266,8 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
             for idx, (hr_img, lr_img) in enumerate(val_loader):
                 lr_img = lr_img.to(config.DEVICE)
                 hr_img = hr_img.to(config.DEVICE)
-                if degrade or jpeg or sinc:
-                    lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg, sinc)
+                if degrade or jpeg or sinc or resize:
+                    lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg, sinc, resize)
                 output = generator(lr_img)
                 if save_images:
                     path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
@@ -277,7 +307,7 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
 
 
 def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_gt: bool = False, dataset=None, on_device=None,
-         with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None, degrade_sinc=None):
+         with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None, degrade_sinc=None, degrade_resize=None):
     if not g_path:                # the averaged generator's best when the run kept one (SOLVER.G_EMA_DECAY), else the last iterate's
         g_path = f"results/{config.EXP.NAME}/g_ema_best.pth"
         if not os.path.exists(g_path):
@@ -294,7 +324,7 @@ def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_
         generator.eval()
     return _validate(generator, loader, config, save_images=save_images, concat_with_gt=concat_w_gt, save_metrics=True,
                      on_device=on_device, with_st=with_st, tile=tile, with_lr=with_lr, degrade=degrade, degrade_jpeg=degrade_jpeg,
-                     degrade_sinc=degrade_sinc)
+                     degrade_sinc=degrade_sinc, degrade_resize=degrade_resize)
 
 
 if __name__ == "__main__":
@@ -315,6 +345,9 @@ if __name__ == "__main__":
     parser.add_argument("--degrade-sinc", type=float, default=None, metavar="OMEGA",
                         help="also take that input through the sinc low-pass filter at cutoff OMEGA in (0, pi], before the JPEG stage "
                              "(DATA.VALIDATE_DEGRADE_SINC)")
+    parser.add_argument("--degrade-resize", type=float, default=None, metavar="S",
+                        help="also take that input through the resize round trip at scale S in [0.25, 2] (bicubic both ways, no noise), "
+                             "before the sinc stage (DATA.VALIDATE_DEGRADE_RESIZE)")
     a = parser.parse_args()
     cfg = Config()
     if a.name:
@@ -326,4 +359,4 @@ if __name__ == "__main__":
     test(cfg, save_images=not a.no_images, g_path=a.g_path, on_device=True if a.on_device else None,
          with_st=True if a.st else None, tile=a.tile, with_lr=True if a.lr_consistency else None,
          degrade=tuple(float(v) for v in a.degrade.split(",")) if a.degrade else None, degrade_jpeg=a.degrade_jpeg,
-         degrade_sinc=a.degrade_sinc)
+         degrade_sinc=a.degrade_sinc, degrade_resize=a.degrade_resize)

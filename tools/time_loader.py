@@ -42,6 +42,13 @@ difference between two legs).  Prints one JSON line.
         # added launch alone on the LR buffers (pass A, pass B, the second sst_jpeg, pass C); the whole second-order batch as the
         # loader issues it; and the same pipeline behind the same first stage as torch ops (F.pad(reflect), grouped conv2d with the
         # per-sample weights, randn, clamp, round, torch_jpeg) - the yardstick
+    python tools/time_loader.py resize [--launches L] [--replays R] [--repeat N] [--parent-lib PATH [--parent-first]]
+        # the resize round trip inside the second-order stage (DATA.DEGRADE2_RESIZE), same sizes and method, every sample with all
+        # stages on.  Legs: the off path = the degraded gather and the second-order batch without resize (and, with --parent-lib,
+        # the same six launches through another build of the library in the same process); sst_rescale alone on the LR buffers with
+        # every sample at the scale 0.3, 1.0 and 1.2 and with the drawn rows (up, down, keep = 0.3, 0.4, 0.3); pass A unquantised;
+        # the whole batch with resize on; and the drawn round trips as torch ops - one F.interpolate pair PER SAMPLE, since the
+        # intermediate sizes differ per sample, with randn noise between them - the yardstick for sst_rescale alone
 """
 import argparse
 import json
@@ -590,8 +597,146 @@ def second_mode(launches, replays, repeat, parent_lib, parent_first=False):
     print(json.dumps(out))
 
 
+def resize_mode(launches, replays, repeat, parent_lib, parent_first=False):
+    import ctypes
+    from srganst import _abi
+    from srganst.device_data import (RESIZE_MODES, Degradation, DeviceImageArena, SecondOrder, filter2d, rescale, resize_size,
+                                     second_order)
+    g = torch.Generator().manual_seed(0)
+    imgs = [torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8) for h, w in WHOLE_SIZES * 2]
+    arena = DeviceImageArena.from_arrays(imgs, HR, HR, UP, "cuda")
+    n, K, o = launches * B, 21, HR // UP
+    tiles = torch.from_numpy(arena.tiles)[torch.randperm(len(arena), generator=g)[:n]]
+    room = torch.from_numpy(arena.table_host[tiles[:, 0].numpy(), 1:3] - HR + 1)
+    desc = torch.zeros(n, 4, dtype=torch.int32)
+    desc[:, 0] = tiles[:, 0]
+    desc[:, 1:3] = (torch.randint(0, 1 << 30, (n, 2), generator=g) % room).to(torch.int32)
+    desc[:, 3] = torch.randint(0, 8, (n,), generator=g).to(torch.int32)
+    arena.check_desc(desc.numpy())
+    desc = desc.cuda()
+    deg = Degradation(jpeg_prob=1.0).draw(n, torch.Generator().manual_seed(1)).cuda()
+    kw = dict(blur_prob=1.0, noise_prob=1.0, final_sinc_prob=1.0, jpeg_prob=1.0, ksize=K)
+    so, so_r = SecondOrder(**kw), SecondOrder(**kw, resize_prob=(0.3, 0.4, 0.3))
+    full = so.draw(n, torch.Generator().manual_seed(2))
+    rows_off, rows_on = full.cuda(), so_r.draw(n, torch.Generator().manual_seed(2)).cuda()
+    bank = torch.from_numpy(so.draw_bank(torch.Generator().manual_seed(3))).cuda()
+    drawn_host = so_r.draw_resize(n, o, o, torch.Generator().manual_seed(4), noise=full[0].numpy())
+    drawn = drawn_host.cuda()
+
+    def at_scale(s):                                     # every sample at the scale s, the drawn modes (keep: bicubic both ways) and noise
+        r = drawn_host.clone()
+        r[:, 0] = r[:, 1] = resize_size(o, s)
+        keep = drawn_host[:, 0] == 0
+        r[keep, 6] |= RESIZE_MODES["bicubic"] | RESIZE_MODES["bicubic"] << 2
+        return r.cuda()
+    gt, lr = torch.empty(B, 3, HR, HR, device="cuda"), torch.empty(B, 3, o, o, device="cuda")
+    s0, s1 = torch.empty_like(lr), torch.empty_like(lr)
+    sl = lambda k: slice(k * B, (k + 1) * B)
+
+    def off(k):
+        arena.crops(desc[sl(k)], gt, s0, deg=deg[sl(k)], ksize=K, jpeg_chroma="420")
+        second_order(s0, rows_off[:, sl(k)], bank, "420", out=lr, scratch=(s1, s0))
+
+    def whole(k):
+        arena.crops(desc[sl(k)], gt, s0, deg=deg[sl(k)], ksize=K, jpeg_chroma="420")
+        second_order(s0, rows_on[:, sl(k)], bank, "420", out=lr, scratch=(s1, s0), resize_rows=drawn[sl(k)])
+
+    # ---- the comparator for R alone: the drawn round trips as torch ops, one F.interpolate pair per sample (the sizes differ per
+    # sample, so the batch cannot be one call), noise at the intermediate size, clamp, round
+    interp = torch.nn.functional.interpolate
+    names = {v: k for k, v in RESIZE_MODES.items()}
+    sn, sp = (drawn[:, j].contiguous().view(torch.float32) for j in (2, 3))
+    plan = [(int(r[0]), int(r[1]), names[int(r[6]) & 3], names[(int(r[6]) >> 2) & 3], bool(int(r[6]) >> 4 & 1)) for r in drawn_host.tolist()]
+
+    def torch_leg(k):
+        for b in range(B):
+            i = k * B + b
+            hi, wi, m1, m2, gray = plan[i]
+            v = s0[b:b + 1]
+            if hi:
+                v = interp(v, size=(hi, wi), mode=m1, **({} if m1 == "area" else {"align_corners": False}))
+            z = torch.randn(1, 1 if gray else 3, v.shape[2], v.shape[3], device="cuda")
+            v = v + torch.sqrt(sp[i] * v.clamp(min=0) + sn[i] ** 2) * z
+            if hi:
+                v = interp(v, size=(o, o), mode=m2, **({} if m2 == "area" else {"align_corners": False}))
+            s1[b:b + 1] = torch.round(v.clamp(0, 1) * 255) / 255
+
+    # the comparator is the kernel's model: without noise the two agree but for pixels whose rounding the summation order decides
+    off(0)
+    s0.copy_(lr)
+    quiet = drawn[sl(0)].clone()
+    quiet[:, 2:4] = 0
+    want = rescale(s0, quiet)
+    sn_keep, sp_keep = sn.clone(), sp.clone()
+    sn.zero_(), sp.zero_()
+    torch_leg(0)
+    sn.copy_(sn_keep), sp.copy_(sp_keep)
+    differ = float((((s1 - want).abs() * 255) > 0.5).float().mean())
+    assert differ < 0.05, f"the torch round trip and sst_rescale differ on {differ:.3f} of the pixels"
+
+    legs = {"off_second_order_batch": off}
+    if parent_lib:
+        other = ctypes.CDLL(parent_lib)
+        for name in ("sst_gather_crops_degraded", "sst_jpeg", "sst_filter2d"):
+            getattr(other, name).restype, getattr(other, name).argtypes = _abi.SIGNATURES[name]
+        wy, iy, wx, ix = arena._bicubic.tables_i32(HR, HR, 1.0 / UP, arena.device)
+        M = bank.shape[0]
+
+        def parent(k):
+            d, st = deg[sl(k)], _abi.stream_ptr()
+            rcs = [other.sst_gather_crops_degraded(arena.arena.data_ptr(), arena.arena.numel(), arena.table.data_ptr(), arena.n_images,
+                                                   desc[sl(k)].data_ptr(), B, HR, arena.lut.data_ptr(), gt.data_ptr(), s0.data_ptr(),
+                                                   wy.data_ptr(), iy.data_ptr(), wx.data_ptr(), ix.data_ptr(), o, o, wy.shape[1],
+                                                   wx.shape[1], arena.span(True, True), d.data_ptr(), K, 1, st),
+                   other.sst_jpeg(s0.data_ptr(), d.data_ptr(), B, o, o, 1, st)]
+            r = rows_off[:, sl(k)]
+            rcs.append(other.sst_filter2d(s0.data_ptr(), s1.data_ptr(), r[0].data_ptr(), bank.data_ptr(), M, B, o, o, K, 1, st))
+            rcs.append(other.sst_filter2d(s1.data_ptr(), s0.data_ptr(), r[1].data_ptr(), bank.data_ptr(), M, B, o, o, K, 1, st))
+            rcs.append(other.sst_jpeg(s0.data_ptr(), r[2].data_ptr(), B, o, o, 1, st))
+            rcs.append(other.sst_filter2d(s0.data_ptr(), lr.data_ptr(), r[3].data_ptr(), bank.data_ptr(), M, B, o, o, K, 1, st))
+            assert not any(rcs), rcs
+        legs["off_second_order_batch_parent_lib"] = parent
+        if parent_first:                                 # the same two legs in the other order: what the order alone is worth
+            legs = {"off_second_order_batch_parent_lib": parent, "off_second_order_batch": off}
+    off(0)
+    s0.copy_(lr)
+    for s in (0.3, 1.0, 1.2):
+        legs[f"rescale_alone_s{s:g}"] = lambda k, r=at_scale(s): rescale(s0, r[sl(k)], out=s1)
+    legs["rescale_alone_drawn"] = lambda k: rescale(s0, drawn[sl(k)], out=s1)
+    legs["pass_a_blur_unquantised"] = lambda k: filter2d(s0, rows_on[0, sl(k)], bank, quantise=False, out=s1)
+    legs["torch_ops_rescale_alone_drawn"] = torch_leg
+    legs["second_order_batch_with_resize"] = whole
+
+    graphs = {}
+    for name, run in legs.items():
+        for k in range(min(3, launches)):               # warm up: tables, code objects, the allocator's pool
+            run(k)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for k in range(launches):
+                run(k)
+        gr.replay()
+        graphs[name] = gr
+    torch.cuda.synchronize()
+    out = {"mode": "resize", "batch": B, "hr": HR, "scale": UP, "launches_per_graph": launches, "replays": replays, "repeat": repeat,
+           "torch_ops_pixels_off_by_a_level": round(differ, 5),
+           "us_per_batch": {name: [] for name in legs}}
+    for _ in range(repeat):
+        for name, gr in graphs.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(replays):
+                gr.replay()
+            t1.record()
+            torch.cuda.synchronize()
+            out["us_per_batch"][name].append(round(t0.elapsed_time(t1) * 1e3 / (replays * launches), 2))
+    out["median_us_per_batch"] = {name: sorted(v)[len(v) // 2] for name, v in out["us_per_batch"].items()}
+    print(json.dumps(out))
+
+
 def main():
-    if len(sys.argv) > 1 and sys.argv[1] == "second":
+    if len(sys.argv) > 1 and sys.argv[1] in ("second", "resize"):
         ap = argparse.ArgumentParser()
         ap.add_argument("mode")
         ap.add_argument("--launches", type=int, default=32)
@@ -600,7 +745,8 @@ def main():
         ap.add_argument("--parent-lib", default="", help="another build of libsrganst.so whose off path is timed beside this one's")
         ap.add_argument("--parent-first", action="store_true", help="time the parent library's leg before this library's")
         a = ap.parse_args()
-        return second_mode(a.launches, a.replays, a.repeat, a.parent_lib, a.parent_first)
+        mode = second_mode if a.mode == "second" else resize_mode
+        return mode(a.launches, a.replays, a.repeat, a.parent_lib, a.parent_first)
     if len(sys.argv) > 1 and sys.argv[1] == "jpeg":
         ap = argparse.ArgumentParser()
         ap.add_argument("mode")
