@@ -566,6 +566,23 @@ int sst_filter2d(const float* x, float* y, const int* flt, const float* bank, in
  * !(sigma_n >= 0) or !(s_p >= 0) makes that sample NaN and touches no other.  No atomics: a result is a function of its sample's
  * inputs alone, whatever the batch position, batch size and tile geometry.  One launch, no allocation, no sync (capturable). */
 int sst_rescale(const float* x, float* y, const int* rows, int B, int h, int w, int quantise, void* stream);
+/* ---- the random resize of the FIRST degradation stage (device_data.py: blur / rescale_to / Degradation(resize_prob=...);
+ * csrc/resize.hip, csrc/degrade.hip).
+ * sst_rescale_to: sst_rescale's chain with an output geometry of its own, out of place: x fp32 [B,3,H,W] -> y fp32 [B,3,h,w], H, W,
+ * h, w in 1..8192, h <= H <= 16 h and w <= W <= 16 w (y == x is refused).  rows int32 [B,8] in sst_rescale's format.  Per sample:
+ * resample (H, W) -> (hi, wi) with m1 by the one-axis rule above, the noise there (e = c hi wi + Y wi + X), neither clamp nor
+ * rounding, resample (hi, wi) -> (h, w) with m2, then clamp and quantise (quantise = 0: the raw value).  hi == wi == 0 ("keep"): the
+ * intermediate is the input itself, hi, wi = H, W, the noise at (H, W), then m2.  There is no pass-through when (H, W) != (h, w); at
+ * (H, W) == (h, w) every row that sst_rescale accepts gives sst_rescale's bits.  Exactly one of hi, wi zero, a negative one, 8 hi < H,
+ * hi > 2 H (the same for wi against W), a mode 3, a bit above bit 4 of word 6, !(sigma_n >= 0) or !(s_p >= 0) makes that sample NaN
+ * and touches no other.  An area entry keeps its full tap count (H -> hi up to 9, hi -> h up to 2 H / h + 1).  No atomics: the same
+ * bits whatever the batch position, batch size and tile geometry (SST_RESIZE1_TILE=RxC, a dev switch, fixes the output tile).  One
+ * launch, no allocation, no sync (capturable).
+ * sst_blur: the first stage's blur alone, out of place: y fp32 [B,3,H,W] = x (*) k per sample, unquantised, by sst_degrade's rule and
+ * device code (deg rows as above; the noise word is not read): a sample's y is the image sst_degrade makes before its bicubic.  qa < 0
+ * keeps the sample's bits.  K odd, 3..21, K / 2 < min(H, W).  One launch, no allocation, no sync (capturable). */
+int sst_rescale_to(const float* x, float* y, const int* rows, int B, int H, int W, int h, int w, int quantise, void* stream);
+int sst_blur(const float* x, const int* deg, float* y, int B, int H, int W, int K, void* stream);
 /* Validation metrics of validate.image_metrics on the device (metrics.py), rounding for rounding: sr, hr fp32 NCHW [B,3,H,W] RGB;
  * out fp64 [B,2] = (MSE of the Y channel on the 0..255 scale over all H*W pixels, mean of the SSIM map over its (H-10) x (W-10)
  * valid region); sr_u8 / hr_u8: uint8 [B,H,W,3] BGR = tensor2img of each image (either may be null).  workspace:

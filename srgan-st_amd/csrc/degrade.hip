@@ -90,3 +90,75 @@ SST_API int sst_degrade(const float* x, const int* dg, int B, int H, int W, int 
   SST_LAUNCH_CHECK("degrade_kernel");
   return SST_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// sst_blur: step (1) of degrade.h alone, at the input's size: y = x (*) k per sample, unquantised, through the
+// device functions above - the weights, the fp64 sum, `reflect` at the image border and blur_tile's row-major fmaf chain - so a
+// sample's blurred image is the one degrade_kernel makes in LDS before its bicubic.  A row with qa < 0 keeps the sample's bits.  One
+// workgroup per (sample, channel, tile of BLUR_ROWS x BLUR_COLS pixels): 256 threads x 4 adjacent pixels, blur_tile's own shape.
+namespace {
+
+constexpr int BLUR_ROWS = 32, BLUR_COLS = 32;
+
+__global__ __launch_bounds__(deg::NT) void blur_kernel(const float* __restrict__ x, const int* __restrict__ dg, float* __restrict__ y,
+                                                       int H, int W, int K, int nct) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int tid = threadIdx.x, c = blockIdx.y, b = blockIdx.z;
+  const int r0 = (blockIdx.x / nct) * BLUR_ROWS, c0 = (blockIdx.x % nct) * BLUR_COLS;
+  const int nr = min(BLUR_ROWS, H - r0), nc = min(BLUR_COLS, W - c0);
+  const float* __restrict__ img = x + ((int64_t)b * 3 + c) * H * W;
+  float* __restrict__ out = y + ((int64_t)b * 3 + c) * H * W;
+  const deg::Params q = deg::load_params(dg, b);
+  if (!q.blur()) {                                               // the bits, whatever they are
+    const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(img);
+    uint32_t* __restrict__ dst = reinterpret_cast<uint32_t*>(out);
+    for (int i = tid; i < nr * nc; i += deg::NT) {
+      const int64_t o = (int64_t)(r0 + i / nc) * W + c0 + i % nc;
+      dst[o] = src[o];
+    }
+    return;
+  }
+  const deg::Layout L(K, 0, BLUR_ROWS, BLUR_COLS, 0, 0);
+  const int p = L.p;
+  float* s_k = reinterpret_cast<float*>(smem + L.o_k);
+  deg::weights_raw(s_k, q, K);
+  __syncthreads();
+  if (tid == deg::NT - 1) deg::weights_sum(s_k, reinterpret_cast<double*>(smem), K);
+  float* plane = reinterpret_cast<float*>(smem + L.o_plane);     // reflected at the image border (p < min(H, W))
+  const int wp = nc + 2 * p;
+  for (int i = tid; i < (nr + 2 * p) * wp; i += deg::NT) {
+    const int r = i / wp, j = i - r * wp;
+    plane[r * L.pitch + j] = img[(int64_t)deg::refl(r0 - p + r, H) * W + deg::refl(c0 - p + j, W)];
+  }
+  __syncthreads();
+  deg::weights_norm(s_k, reinterpret_cast<const double*>(smem), K);
+  __syncthreads();
+  float* s_blur = reinterpret_cast<float*>(smem + L.o_a);
+  deg::blur_tile(plane, L.pitch, s_k, K, s_blur, L.bpitch, nr, nc);
+  __syncthreads();
+  for (int i = tid; i < nr * nc; i += deg::NT) {
+    const int r = i / nc, j = i - r * nc;
+    out[(int64_t)(r0 + r) * W + c0 + j] = s_blur[r * L.bpitch + j];
+  }
+}
+
+}  // namespace
+
+SST_API int sst_blur(const float* x, const int* dg, float* y, int B, int H, int W, int K, void* stream) {
+  SST_REQUIRE(x && dg && y, "sst_blur: null pointer");
+  SST_REQUIRE(x != y, "sst_blur: y == x (a tile reads its neighbours' pixels: out of place only)");
+  SST_REQUIRE(B > 0 && B <= 65535, "sst_blur: batch %d outside [1, 65535]", B);
+  SST_REQUIRE(K >= deg::K_MIN && K <= deg::K_MAX && (K & 1), "sst_blur: the blur window K = %d must be odd and in %d..%d", K, deg::K_MIN,
+              deg::K_MAX);
+  SST_REQUIRE(H > 0 && W > 0 && H <= 32768 && W <= 32768, "sst_blur: image %dx%d outside 1..32768", W, H);
+  SST_REQUIRE(K / 2 < (H < W ? H : W), "sst_blur: the half window %d (K = %d) must be smaller than the image's shorter side (%dx%d)",
+              K / 2, K, W, H);
+  SST_REQUIRE((reinterpret_cast<uintptr_t>(dg) & 31) == 0, "sst_blur: deg must be 32-byte aligned (rows of 8 int32)");
+  const int nct = (W + BLUR_COLS - 1) / BLUR_COLS;
+  const int64_t ntile = (int64_t)nct * ((H + BLUR_ROWS - 1) / BLUR_ROWS);
+  const int64_t lds = deg::Layout(K, 0, BLUR_ROWS, BLUR_COLS, 0, 0).bytes;
+  SST_REQUIRE(lds <= deg::LDS_BUDGET, "sst_blur: %lld B of LDS needed > 64 KiB", (long long)lds);
+  blur_kernel<<<dim3((unsigned)ntile, 3, B), deg::NT, (size_t)lds, sst_stream(stream)>>>(x, dg, y, H, W, K, nct);
+  SST_LAUNCH_CHECK("blur_kernel");
+  return SST_OK;
+}

@@ -139,6 +139,8 @@ SIGNATURES = {
     "sst_jpeg_tables": (c_int, [c_int, P]),
     "sst_filter2d": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "sst_rescale": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
+    "sst_rescale_to": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "sst_blur": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
     "sst_image_metrics_workspace": (c_int, [c_int, c_int, c_int, POINTER(c_int64)]),
     "sst_image_metrics": (c_int, [P, P, c_int, c_int, c_int, P, P, P, P, P]),
     "sst_tile_gather": (c_int, [P, P, c_int64, c_int, c_int, P, c_int, c_int, c_int, c_int, P, P, P]),

@@ -166,6 +166,19 @@ class Config:
         # degrade(gt) (or the plain bicubic LR made from gt) and before the VALIDATE_DEGRADE_SINC stage; the printed line says so.
         # None: off
         self.DATA.VALIDATE_DEGRADE_RESIZE = None
+        # with DEGRADE: the random resize of Real-ESRGAN's FIRST stage (sst_blur, sst_rescale_to).  Between the
+        # blur and the noise a sample is, with the probabilities RESIZE_PROB = (up, down, keep), resized from the HR size to a scale
+        # uniform in [1, RESIZE_RANGE[1]] or [RESIZE_RANGE[0], 1] with a mode uniform in RESIZE_MODES (no antialias), gets its noise at
+        # THAT size, and is resized to the LR size with a mode drawn independently - in place of the antialiased bicubic.  Three
+        # launches per batch for the one.  The draws come from a fifth private generator: all others stay as they are
+        self.DATA.DEGRADE_RESIZE = False
+        self.DATA.DEGRADE_RESIZE_PROB = (0.2, 0.7, 0.1)
+        self.DATA.DEGRADE_RESIZE_RANGE = (0.15, 1.5)
+        self.DATA.DEGRADE_RESIZE_MODES = ("area", "bilinear", "bicubic")
+        # (s, m1, m2), s in [0.125, 2]: validation's input is made through the first stage's resize at this scale - blur (with
+        # VALIDATE_DEGRADE), resize of gt to the scale s with the mode m1, the noise there, resize to the LR size with m2 - before the
+        # other VALIDATE_DEGRADE_* stages in their order; the printed line says so.  None: off
+        self.DATA.VALIDATE_DEGRADE_RESIZE1 = None
 
         self.MODEL = dotdict()
         self.MODEL.G_CONTINUE_FROM_WARMUP = False

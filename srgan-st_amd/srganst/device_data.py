@@ -306,6 +306,24 @@ _DEGRADE_STREAM = 0x6A09E667F3BCC908      # keeps the loader's degradation gener
 
 
 JPEG_CHROMA = {"444": 0, "420": 1}         # sst_jpeg's chroma argument
+RESIZE_MODES = {"area": 0, "bilinear": 1, "bicubic": 2}       # the modes of sst_rescale and sst_rescale_to
+# the first stage's random resize (DATA.DEGRADE_RESIZE; sst_rescale_to)
+_RESIZE1_STREAM = 0x5BE0CD19137E2179      # keeps the loader's first-stage resize generator apart from its four others
+RESIZE1_MAX_RATIO, RESIZE1_MIN_DIV, RESIZE1_MAX_DOWN = 2, 8, 16   # sst_rescale_to: H <= 8 hi, hi <= 2 H; h <= H <= 16 h
+
+
+def resize1_size(n: int, s: float) -> int:
+    """The intermediate length of an HR axis of n pixels at scale s: int(n s), at least ceil(n / 8)."""
+    return max(int(n * s), -(-n // RESIZE1_MIN_DIV))
+
+
+def rescale_to_size_ok(hi: int, wi: int, H: int, W: int) -> bool:
+    """True when sst_rescale_to takes the intermediate size (hi, wi) on an [H, W] input: 0, 0 (keep), or both within
+    [ceil(n / 8), 2 n] of their axis."""
+    if hi == 0 and wi == 0:
+        return True
+    return (hi > 0 and wi > 0 and RESIZE1_MIN_DIV * hi >= H and hi <= RESIZE1_MAX_RATIO * H and RESIZE1_MIN_DIV * wi >= W
+            and wi <= RESIZE1_MAX_RATIO * W)
 
 
 def _chroma(mode, who: str) -> int:
@@ -344,10 +362,17 @@ class Degradation:
     1 - noise_prob; two random key words.  With jpeg_prob > 0 a sample also gets, with that probability, a JPEG quality that is a
     uniform integer in the closed range jpeg_quality (word 6 of its row; sst_jpeg, chroma mode jpeg_chroma): these draws are made
     after all the others, so the other words are the ones drawn without them.  Degradation.fixed(...) draws the same row every time
-    (validation, tests)."""
+    (validation, tests).
+    resize_prob = (up, down, keep), three probabilities that sum to 1 (Real-ESRGAN's first stage: (0.2, 0.7, 0.1); None: no resize,
+    and every draw, repr and behaviour is the one of an instance built without these arguments): the stage becomes blur at the HR
+    size (sst_blur), a resize to an intermediate size at a scale uniform in [1, resize_range[1]] (up) or [resize_range[0], 1]
+    (down), the same on both axes, with a mode uniform in resize_modes, the noise THERE, and a resize to the LR size with a mode
+    drawn independently (sst_rescale_to; no antialias).  draw() is unchanged; draw_resize(n, H, W, generator, deg_rows) -> int32
+    [n, 8] makes the rows of the resize, with the deg rows' noise word and key in them."""
 
     def __init__(self, blur_sigma=(0.2, 4.0), aniso: bool = True, blur_prob: float = 1.0, noise_sigma=(0.0, 25.0),
-                 noise_prob: float = 1.0, ksize: int = 21, jpeg_quality=(30, 95), jpeg_prob: float = 0.0, jpeg_chroma: str = "420"):
+                 noise_prob: float = 1.0, ksize: int = 21, jpeg_quality=(30, 95), jpeg_prob: float = 0.0, jpeg_chroma: str = "420",
+                 resize_prob=None, resize_range=(0.15, 1.5), resize_modes=("area", "bilinear", "bicubic")):
         self.blur_sigma, self.noise_sigma = (float(blur_sigma[0]), float(blur_sigma[1])), (float(noise_sigma[0]), float(noise_sigma[1]))
         self.aniso, self.blur_prob, self.noise_prob, self.ksize = bool(aniso), float(blur_prob), float(noise_prob), int(ksize)
         self._fixed = None
@@ -366,17 +391,42 @@ class Degradation:
         if not 0 <= self.jpeg_prob <= 1:
             raise ValueError(f"Degradation: jpeg_prob {jpeg_prob} must be in [0, 1]")
         _chroma(jpeg_chroma, "Degradation")
+        self.resize_prob = None if resize_prob is None else tuple(float(v) for v in resize_prob)
+        if self.resize_prob is not None and (len(self.resize_prob) != 3 or min(self.resize_prob) < 0
+                                             or abs(sum(self.resize_prob) - 1) > 1e-9):
+            raise ValueError(f"Degradation: resize_prob {tuple(resize_prob)} must be three probabilities (up, down, keep) that sum to 1")
+        self.resize_range = (float(resize_range[0]), float(resize_range[1]))
+        if not 0 < self.resize_range[0] <= 1 <= self.resize_range[1] <= RESIZE1_MAX_RATIO:
+            raise ValueError(f"Degradation: resize_range {tuple(resize_range)} must be 0 < lo <= 1 <= hi <= {RESIZE1_MAX_RATIO}")
+        self.resize_modes = tuple(resize_modes)
+        if not self.resize_modes or any(m not in RESIZE_MODES for m in self.resize_modes):
+            raise ValueError(f"Degradation: resize_modes {tuple(resize_modes)} must be names of {tuple(RESIZE_MODES)}")
+        self._fixed_resize = None
 
     @property
     def has_jpeg(self) -> bool:
         """True when a row this draws can hold a JPEG quality: the loader then issues the sst_jpeg launch after the gather."""
         return self._fixed_jpeg > 0 if self._fixed else self.jpeg_prob > 0
 
+    @property
+    def has_resize(self) -> bool:
+        """True when the stage resizes at random on the way to LR: the loader then issues the plain gather, sst_blur and sst_rescale_to
+        instead of the fused degraded gather."""
+        return self._fixed_resize is not None if self._fixed else self.resize_prob is not None
+
     @classmethod
     def fixed(cls, sigma1: float, sigma2: float, theta_deg: float, noise: float, key=0, ksize: int = 21, jpeg: int = 0,
-              jpeg_chroma: str = "420") -> "Degradation":
+              jpeg_chroma: str = "420", resize=None) -> "Degradation":
         """Every sample gets these parameters: the two standard deviations (0: no blur), the angle in degrees, the noise's standard
-        deviation in 0..255 units, the key (an int: the low and high 32 bits; or a pair of words) and the JPEG quality (0: none)."""
+        deviation in 0..255 units, the key (an int: the low and high 32 bits; or a pair of words), the JPEG quality (0: none) and the
+        random resize's stand-in (None: none, the fused stage; (s, m1, m2): to the scale s in [0.125, 2] of the HR size with the mode
+        m1, the noise there, to the LR size with m2)."""
+        if resize is not None:
+            if len(resize) != 3 or not 1 / RESIZE1_MIN_DIV <= float(resize[0]) <= RESIZE1_MAX_RATIO or resize[1] not in RESIZE_MODES \
+                    or resize[2] not in RESIZE_MODES:
+                raise ValueError(f"Degradation.fixed: resize {resize!r} must be (s, m1, m2), s in [{1 / RESIZE1_MIN_DIV}, "
+                                 f"{RESIZE1_MAX_RATIO}], the modes of {tuple(RESIZE_MODES)}")
+            resize = (float(resize[0]), resize[1], resize[2])
         if sigma1 < 0 or sigma2 < 0 or noise < 0 or (sigma1 > 0) != (sigma2 > 0):
             raise ValueError(f"Degradation.fixed: sigma ({sigma1}, {sigma2}) must be both positive or both 0, noise {noise} >= 0")
         if int(jpeg) != jpeg or not 0 <= jpeg <= 100:
@@ -385,16 +435,20 @@ class Degradation:
         d._fixed_jpeg = int(jpeg)
         k = (int(key) & 0xFFFFFFFF, (int(key) >> 32) & 0xFFFFFFFF) if isinstance(key, (int, np.integer)) else (int(key[0]), int(key[1]))
         d._fixed = (float(sigma1), float(sigma2), float(theta_deg), float(noise), k)
+        d._fixed_resize = resize
         return d
 
     def __repr__(self) -> str:
         if self._fixed:
             s1, s2, th, nz, k = self._fixed
             jp = f", jpeg={self._fixed_jpeg}, jpeg_chroma={self.jpeg_chroma!r}" if self._fixed_jpeg else ""
-            return f"Degradation.fixed(sigma1={s1:g}, sigma2={s2:g}, theta_deg={th:g}, noise={nz:g}, key={k}, ksize={self.ksize}{jp})"
+            rs = f", resize={self._fixed_resize}" if self._fixed_resize else ""
+            return f"Degradation.fixed(sigma1={s1:g}, sigma2={s2:g}, theta_deg={th:g}, noise={nz:g}, key={k}, ksize={self.ksize}{jp}{rs})"
         jp = f", jpeg_quality={self.jpeg_quality}, jpeg_prob={self.jpeg_prob:g}, jpeg_chroma={self.jpeg_chroma!r}" if self.jpeg_prob > 0 else ""
+        rs = (f", resize_prob={self.resize_prob}, resize_range={self.resize_range}, resize_modes={self.resize_modes}"
+              if self.resize_prob is not None else "")
         return (f"Degradation(blur_sigma={self.blur_sigma}, aniso={self.aniso}, blur_prob={self.blur_prob:g}, "
-                f"noise_sigma={self.noise_sigma}, noise_prob={self.noise_prob:g}, ksize={self.ksize}{jp})")
+                f"noise_sigma={self.noise_sigma}, noise_prob={self.noise_prob:g}, ksize={self.ksize}{jp}{rs})")
 
     def draw(self, n: int, generator: torch.Generator | None = None) -> Tensor:
         if self._fixed:
@@ -414,6 +468,35 @@ class Degradation:
             jpeg = np.where(on, q, 0)
         return torch.from_numpy(degrade_rows(np.where(blur, s1, 0.0), np.where(blur, s2, 0.0), np.pi * u[:, 2], nz, keys, jpeg))
 
+    def draw_resize(self, n: int, H: int, W: int, generator: torch.Generator | None = None, deg_rows=None) -> Tensor:
+        """The rows of the stage's random resize for n samples of an [H, W] HR batch, int32 [n, 8] (rescale_rows' layout, for
+        rescale_to).  Per sample the kind (up, down, keep), then s uniform in [1, resize_range[1]] (up) or [resize_range[0], 1]
+        (down), hi = max(int(H s), ceil(H / 8)) and wi likewise from the same s, then m1 and m2 uniform in resize_modes,
+        independently; keep writes 0, 0 (the intermediate is the blurred HR image itself) and still draws m2, the mode of the resize
+        to the LR size.  deg_rows: the stage's deg rows as draw() makes them - their sigma_n (word 3) and key (words 4, 5) go into
+        the rows, shot and gray stay zero: the noise parameters of a sample are the ones drawn without resize."""
+        if not self.has_resize:
+            raise ValueError("Degradation.draw_resize: this stage has no resize (resize_prob is None)")
+        rows = np.zeros((n, 8), np.int32)
+        if self._fixed:
+            s, m1, m2 = self._fixed_resize
+            rows[:, 0], rows[:, 1], rows[:, 6] = resize1_size(H, s), resize1_size(W, s), RESIZE_MODES[m1] | RESIZE_MODES[m2] << 2
+        else:
+            u = torch.rand(n, 2, generator=generator, dtype=torch.float64).numpy()
+            pick = torch.randint(0, 1 << 62, (n, 2), generator=generator, dtype=torch.int64).numpy()
+            up, down, _ = self.resize_prob
+            lo, hi = self.resize_range
+            s = np.where(u[:, 0] < up, 1.0 + (hi - 1.0) * u[:, 1], lo + (1.0 - lo) * u[:, 1])
+            keep = u[:, 0] >= up + down
+            rows[:, 0] = np.where(keep, 0, [resize1_size(H, v) for v in s])
+            rows[:, 1] = np.where(keep, 0, [resize1_size(W, v) for v in s])
+            codes = np.array([RESIZE_MODES[m] for m in self.resize_modes], np.int32)
+            rows[:, 6] = np.where(keep, 0, codes[pick[:, 0] % len(codes)]) | codes[pick[:, 1] % len(codes)] << 2
+        if deg_rows is not None:
+            a = np.asarray(deg_rows, np.int32).reshape(n, 8)
+            rows[:, 2], rows[:, 4:6] = a[:, 3], a[:, 4:6]
+        return torch.from_numpy(rows)
+
     @classmethod
     def from_config(cls, config) -> "Degradation | None":
         """DATA.DEGRADE_* -> a Degradation, or None with DATA.DEGRADE off."""
@@ -422,7 +505,10 @@ class Degradation:
             return None
         return cls(data.DEGRADE_BLUR_SIGMA, data.DEGRADE_BLUR_ANISO, data.DEGRADE_BLUR_PROB, data.DEGRADE_NOISE_SIGMA,
                    data.DEGRADE_NOISE_PROB, data.DEGRADE_BLUR_KSIZE, tuple(data.get("DEGRADE_JPEG_QUALITY", (30, 95))),
-                   data.get("DEGRADE_JPEG_PROB", 0.0), data.get("DEGRADE_JPEG_CHROMA", "420"))
+                   data.get("DEGRADE_JPEG_PROB", 0.0), data.get("DEGRADE_JPEG_CHROMA", "420"),
+                   tuple(data.get("DEGRADE_RESIZE_PROB", (0.2, 0.7, 0.1))) if data.get("DEGRADE_RESIZE", False) else None,
+                   tuple(data.get("DEGRADE_RESIZE_RANGE", (0.15, 1.5))),
+                   tuple(data.get("DEGRADE_RESIZE_MODES", ("area", "bilinear", "bicubic"))))
 
 
 def _check_deg(deg: Tensor, B: int, device, who: str) -> None:
@@ -453,12 +539,47 @@ def jpeg(lr: Tensor, deg: Tensor, chroma: str = "420", out: Tensor | None = None
     return out
 
 
-def degrade(x: Tensor, deg: Tensor, scale: int, ksize: int = 21, quantise: bool = True, jpeg_chroma: str | None = None) -> Tensor:
+def blur(x: Tensor, deg: Tensor, ksize: int = 21, out: Tensor | None = None) -> Tensor:
+    """ONE sst_blur launch on the current stream: the degradation stage's blur alone on an fp32 batch x [B,3,H,W] (ksize // 2 <
+    min(H, W)) with the rows deg int32 [B,8] (Degradation.draw / degrade_rows; the noise word is not read) -> unquantised fp32
+    [B,3,H,W], a new tensor, or `out` (contiguous fp32 of x's shape; never x itself).  A sample's result is the image sst_degrade
+    makes before its bicubic, bit for bit; a row without blur keeps the sample's bits."""
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_cuda:
+        raise ValueError(f"blur: x must be fp32 [B, 3, H, W] on a ROCm device, got {x.dtype} {tuple(x.shape)} on {x.device}")
+    B, _, H, W = x.shape
+    _check_deg(deg, B, x.device, "blur")
+    if out is None:
+        out = torch.empty(B, 3, H, W, device=x.device)
+    else:
+        if out is x or out.data_ptr() == x.data_ptr():
+            raise ValueError("blur: out must not be x (a tile reads its neighbours' pixels: out of place only)")
+        if out.dtype != torch.float32 or tuple(out.shape) != tuple(x.shape) or not out.is_contiguous() or out.device != x.device:
+            raise ValueError(f"blur: out must be contiguous fp32 {tuple(x.shape)} on {x.device}, got {out.dtype} {tuple(out.shape)}")
+    x = x.contiguous()
+    _abi.check(_abi.lib().sst_blur(_abi.ptr(x), _abi.ptr(deg), _abi.ptr(out), B, H, W, int(ksize), _abi.stream_ptr()), "sst_blur")
+    return out
+
+
+def degrade(x: Tensor, deg: Tensor, scale: int, ksize: int = 21, quantise: bool = True, jpeg_chroma: str | None = None,
+            resize_rows: Tensor | None = None) -> Tensor:
     """ONE sst_degrade launch on the current stream: the degradation stage on an fp32 batch x [B,3,H,W] of any size (H, W >= scale,
     ksize // 2 < min(H, W)) with per-sample rows deg int32 [B,8] (Degradation.draw / degrade_rows) -> lr [B,3,H//scale,W//scale].
     The stand-alone form of DeviceImageArena.crops(desc, deg=...), whose lr it reproduces from its gt bit for bit.  quantise=False
     (tests and tools) returns the unclamped, unrounded values.  jpeg_chroma ('444' / '420'): a second launch (sst_jpeg) takes lr
-    through the JPEG stage in place, at the qualities in word 6 of the rows; it needs the quantised values."""
+    through the JPEG stage in place, at the qualities in word 6 of the rows; it needs the quantised values.
+    resize_rows: int32 [B,8] (Degradation.draw_resize) - the stage with its random resize, as the loader issues it: TWO launches
+    instead of the one, blur(x, deg) and rescale_to(.., resize_rows, (H//scale, W//scale)), whose rows carry the noise."""
+    if resize_rows is not None:
+        if jpeg_chroma is not None:
+            _chroma(jpeg_chroma, "degrade")
+            if not quantise:
+                raise ValueError("degrade: the JPEG stage works on the 1/255 grid; jpeg_chroma needs quantise=True")
+        if scale not in (2, 4, 8):
+            raise ValueError(f"degrade: scale must be 2, 4 or 8, got {scale!r}")
+        lr = rescale_to(blur(x, deg, ksize), resize_rows, (int(x.shape[2] * (1.0 / scale)), int(x.shape[3] * (1.0 / scale))), quantise)
+        if jpeg_chroma is not None:
+            jpeg(lr, deg, jpeg_chroma, out=lr)
+        return lr
     if jpeg_chroma is not None:
         _chroma(jpeg_chroma, "degrade")
         if not quantise:
@@ -547,7 +668,6 @@ def filter2d(x: Tensor, flt: Tensor, bank: Tensor | None, quantise: bool = True,
 
 # ---- the random resize round trip inside the second stage (DATA.DEGRADE2_RESIZE; csrc/resize.hip)
 _RESIZE_STREAM = 0x1F83D9ABFB41BD6B       # keeps the loader's resize generator apart from its three others
-RESIZE_MODES = {"area": 0, "bilinear": 1, "bicubic": 2}
 RESIZE_MAX_RATIO, RESIZE_MIN_DIV = 2, 4   # sst_rescale's limits on an intermediate size: h <= 4 hi and hi <= 2 h
 
 
@@ -635,6 +755,43 @@ def rescale(x: Tensor, rows: Tensor, quantise: bool = True, out: Tensor | None =
     x = x.contiguous()
     _abi.check(_abi.lib().sst_rescale(_abi.ptr(x), _abi.ptr(out), _abi.ptr(rows), B, h, w, int(bool(quantise)), _abi.stream_ptr()),
                "sst_rescale")
+    return out
+
+
+def rescale_to(x: Tensor, rows: Tensor, size, quantise: bool = True, out: Tensor | None = None) -> Tensor:
+    """ONE sst_rescale_to launch on the current stream: rescale's chain with an output size of its own, on an fp32 batch x [B,3,H,W]
+    (H, W <= 8192) with the rows int32 [B,8] (rescale_rows) -> [B,3,h,w], size = (h, w) with h <= H <= 16 h and w <= W <= 16 w: a
+    new tensor, or `out` (contiguous fp32 of that shape; never x itself).  Per sample: resample to its intermediate size with its
+    first mode (0, 0: the intermediate is x itself), noise there, resample to (h, w) with its second mode, clamp to [0, 1] and the
+    1/255 grid; at (h, w) = (H, W) the bits are rescale's.  quantise=False (tests and tools) returns the unclamped, unrounded values.
+    rows on x's device are taken as they are (a size outside the kernel's limits makes that sample NaN); rows on the host are
+    checked first - a size outside [ceil(n / 8), 2 n] of its axis raises - and then uploaded."""
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_cuda:
+        raise ValueError(f"rescale_to: x must be fp32 [B, 3, H, W] on a ROCm device, got {x.dtype} {tuple(x.shape)} on {x.device}")
+    B, _, H, W = x.shape
+    if np.ndim(size) != 1 or len(size) != 2 or any(int(v) != v for v in size):
+        raise ValueError(f"rescale_to: size must be a pair of integers (h, w), got {size!r}")
+    h, w = int(size[0]), int(size[1])
+    if not (1 <= h <= H <= RESIZE1_MAX_DOWN * h and 1 <= w <= W <= RESIZE1_MAX_DOWN * w):
+        raise ValueError(f"rescale_to: the output size {h}x{w} (rows x columns) must be within [n / {RESIZE1_MAX_DOWN}, n] of each axis "
+                         f"of the {H}x{W} input")
+    if rows.device.type == "cpu" and rows.dtype == torch.int32 and tuple(rows.shape) == (B, 8):
+        for b, (hi, wi) in enumerate(rows[:, :2].tolist()):
+            if not rescale_to_size_ok(hi, wi, H, W):
+                raise ValueError(f"rescale_to: row {b}: the intermediate size {hi}x{wi} (rows x columns) must be 0, 0 or within "
+                                 f"[ceil(n / {RESIZE1_MIN_DIV}), {RESIZE1_MAX_RATIO} n] of each axis of the {H}x{W} image")
+        rows = rows.contiguous().to(x.device)
+    _check_deg(rows, B, x.device, "rescale_to")
+    if out is None:
+        out = torch.empty(B, 3, h, w, device=x.device)
+    else:
+        if out is x or out.data_ptr() == x.data_ptr():
+            raise ValueError("rescale_to: out must not be x (a tile reads its neighbours' pixels: out of place only)")
+        if out.dtype != torch.float32 or tuple(out.shape) != (B, 3, h, w) or not out.is_contiguous() or out.device != x.device:
+            raise ValueError(f"rescale_to: out must be contiguous fp32 {(B, 3, h, w)} on {x.device}, got {out.dtype} {tuple(out.shape)}")
+    x = x.contiguous()
+    _abi.check(_abi.lib().sst_rescale_to(_abi.ptr(x), _abi.ptr(out), _abi.ptr(rows), B, H, W, h, w, int(bool(quantise)),
+                                         _abi.stream_ptr()), "sst_rescale_to")
     return out
 
 
@@ -1113,7 +1270,12 @@ class DeviceCropLoader:
     A second stage that resizes (SecondOrder(resize_prob=...)) adds one sst_rescale launch per batch behind the first sst_filter2d;
     the epoch's resize rows are drawn for ALL tiles from a FOURTH private generator (seed, epoch and a constant of its own), so a
     tile's resize depends on neither world size nor rank nor batch size, the window, transform, first-stage, second-stage and bank
-    draws are the ones made without it, and resuming at an epoch reproduces it: nothing new goes into a checkpoint."""
+    draws are the ones made without it, and resuming at an epoch reproduces it: nothing new goes into a checkpoint.
+    A degradation that resizes (Degradation(resize_prob=...)) makes the first stage three launches per batch instead of the one: the
+    plain gather (gt alone), sst_blur on gt into a scratch buffer of the loader, and sst_rescale_to from it into the buffer the fused
+    gather would have written; the epoch's rows for it are drawn for ALL tiles from a FIFTH private generator (seed, epoch and a
+    constant of its own) and carry the noise words and keys of the tile's deg row, so every other draw is the one made without it, a
+    tile's resize depends on neither world size nor rank nor batch size, and resuming at an epoch reproduces it."""
 
     def __init__(self, arena: DeviceImageArena, batch_size: int, sampler=None, random_crop: bool = False, augment: bool = False,
                  seed: int = 0, degradation: Degradation | None = None, second: SecondOrder | None = None):
@@ -1138,6 +1300,7 @@ class DeviceCropLoader:
         self.epoch = 0
         self._gt = self._lr = None
         self._scratch = None
+        self._hr = None
 
     def __len__(self) -> int:
         return len(self.sampler) // self.batch_size
@@ -1189,6 +1352,16 @@ class DeviceCropLoader:
         full = self.second.draw(n, torch.Generator().manual_seed((base + _SECOND_STREAM) % (1 << 63)), keep_noise=True).numpy()
         return self.second.draw_resize(n, o, o, torch.Generator().manual_seed((base + _RESIZE_STREAM) % (1 << 63)), noise=full[0]).numpy()
 
+    def resize1_draws(self, epoch: int) -> np.ndarray | None:
+        """The epoch's first-stage resize row of EVERY tile of the set, int32 [len(arena), 8] (Degradation.draw_resize); None without
+        a degradation that resizes.  The sizes and modes come from a FIFTH private generator (seed, epoch and a constant of its
+        own); the noise word and the key are the ones of the tile's deg row (deg_draws)."""
+        if self.degradation is None or not self.degradation.has_resize:
+            return None
+        n, S = len(self.dset), self.dset.crop
+        g = torch.Generator().manual_seed((self.seed * 1000003 + epoch + _RESIZE1_STREAM) % (1 << 63))
+        return self.degradation.draw_resize(n, S, S, g, deg_rows=self.deg_draws(epoch)).numpy()
+
     def plan_all(self):
         """plan_both() and, in the same order, the second stage's rows int32 [4, len(self) * batch_size, 8] and bank (or None, None)."""
         return self.plan_resize()[:4]
@@ -1196,14 +1369,21 @@ class DeviceCropLoader:
     def plan_resize(self):
         """plan_all() and, in the same order (ONE walk of the sampler for all five), the resize rows int32 [len(self) * batch_size, 8],
         or None without a second stage that resizes."""
+        return self.plan_first_resize()[:5]
+
+    def plan_first_resize(self):
+        """plan_resize() and, in the same order (ONE walk of the sampler for all six), the first-stage resize rows int32
+        [len(self) * batch_size, 8], or None without a degradation that resizes."""
         order = np.fromiter(iter(self.sampler), dtype=np.int64)[: len(self) * self.batch_size]
         desc, deg = self._plan(order)
+        first = self.resize1_draws(self.epoch)
+        first = None if first is None else torch.from_numpy(np.ascontiguousarray(first[order]))
         if self.second is None:
-            return desc, deg, None, None, None
+            return desc, deg, None, None, None, first
         rows, bank = self.second_draws(self.epoch)
         resize = self.resize_draws(self.epoch)
         return (desc, deg, torch.from_numpy(np.ascontiguousarray(rows[:, order])), torch.from_numpy(bank),
-                None if resize is None else torch.from_numpy(np.ascontiguousarray(resize[order])))
+                None if resize is None else torch.from_numpy(np.ascontiguousarray(resize[order])), first)
 
     def plan_both(self):
         """The current epoch on the host, in the sampler's order (ONE walk of the sampler): the descriptors int32
@@ -1226,8 +1406,12 @@ class DeviceCropLoader:
 
     def __iter__(self):
         B = self.batch_size
-        host, host_deg, host_rows, host_bank, host_resize = (self.plan_resize() if self.second is not None
-                                                             else (*self.plan_both(), None, None, None))
+        host_first = None
+        if self.degradation is not None and self.degradation.has_resize:
+            host, host_deg, host_rows, host_bank, host_resize, host_first = self.plan_first_resize()
+        else:
+            host, host_deg, host_rows, host_bank, host_resize = (self.plan_resize() if self.second is not None
+                                                                 else (*self.plan_both(), None, None, None))
         self.epoch += 1
         dev = self.dset.device
         up = (lambda t: t.pin_memory().to(dev, non_blocking=True)) if dev.type == "cuda" else (lambda t: t)
@@ -1238,17 +1422,36 @@ class DeviceCropLoader:
             return
         deg = up(host_deg)                                               # once per epoch, next to desc
         jpeg_chroma = self.degradation.jpeg_chroma if self.degradation.has_jpeg else None
+        first = None if host_first is None else up(host_first)
         if self.second is not None:
             yield from self._iter_second(desc, deg, jpeg_chroma, up(host_rows), up(host_bank) if host_bank.numel() else None,
-                                         None if host_resize is None else up(host_resize))
+                                         None if host_resize is None else up(host_resize), first)
             return
         for k in range(len(self)):
-            yield self.dset.crops(desc[k * B:(k + 1) * B], self._gt, self._lr, deg=deg[k * B:(k + 1) * B],
-                                  ksize=self.degradation.ksize, jpeg_chroma=jpeg_chroma)
+            sl = slice(k * B, (k + 1) * B)
+            yield self._first(desc[sl], deg[sl], None if first is None else first[sl], self._lr, jpeg_chroma)
 
-    def _iter_second(self, desc, deg, jpeg_chroma, rows, bank, resize=None):
+    def _first(self, desc, deg, first, lr_out, jpeg_chroma):
+        """The first stage of one batch into lr_out (None: a new tensor) -> gt, lr.  first None: the fused degraded gather (and its
+        sst_jpeg).  first (the batch's first-stage resize rows): the plain gather, gt alone; sst_blur on gt into the loader's HR
+        scratch; sst_rescale_to from it to the LR size, with the noise in its rows; then the same sst_jpeg."""
+        if first is None:
+            return self.dset.crops(desc, self._gt, lr_out, deg=deg, ksize=self.degradation.ksize, jpeg_chroma=jpeg_chroma)
+        B, S, o, dev = desc.shape[0], self.dset.crop, self.dset.out, self.dset.device
+        gt, _ = self.dset.crops(desc, self._gt, with_lr=False)
+        if self._hr is None or self._hr.shape[0] != B:
+            self._hr = torch.empty(B, 3, S, S, device=dev)
+        if lr_out is not None:
+            _expect(lr_out, (B, 3, o, o), "lr_out")
+        lr = rescale_to(blur(gt, deg, self.degradation.ksize, out=self._hr), first, (o, o), out=lr_out)
+        if jpeg_chroma is not None:
+            jpeg(lr, deg, jpeg_chroma, out=lr)
+        return gt, lr
+
+    def _iter_second(self, desc, deg, jpeg_chroma, rows, bank, resize=None, first=None):
         """The batches with the second stage: the gather (and its sst_jpeg) into a scratch buffer, then second_order() from it, the last
-        launch into the bound lr buffer - no copy.  resize: the epoch's resize rows (one more launch, sst_rescale, per batch)."""
+        launch into the bound lr buffer - no copy.  resize: the epoch's resize rows (one more launch, sst_rescale, per batch).  first:
+        the epoch's first-stage resize rows (_first: three launches in the gather's place, into the same scratch buffer)."""
         B, o, dev = self.batch_size, self.dset.out, self.dset.device
         if self._scratch is None or self._scratch[0].shape[0] != B:
             self._scratch = (torch.empty(B, 3, o, o, device=dev), torch.empty(B, 3, o, o, device=dev))
@@ -1256,7 +1459,7 @@ class DeviceCropLoader:
         chroma2 = self.second.jpeg_chroma if self.second.has_jpeg else None
         for k in range(len(self)):
             sl = slice(k * B, (k + 1) * B)
-            gt, _ = self.dset.crops(desc[sl], self._gt, s0, deg=deg[sl], ksize=self.degradation.ksize, jpeg_chroma=jpeg_chroma)
+            gt, _ = self._first(desc[sl], deg[sl], None if first is None else first[sl], s0, jpeg_chroma)
             lr = self._lr if self._lr is not None else torch.empty(B, 3, o, o, device=dev)
             _expect(lr, (B, 3, o, o), "lr_out")
             yield gt, second_order(s0, rows[:, sl], bank, chroma2, out=lr, scratch=(s1, s0),
@@ -1265,7 +1468,7 @@ class DeviceCropLoader:
 
 def check_switches(config) -> None:
     """DATA.RANDOM_CROP, DATA.AUGMENT and DATA.DEGRADE are made by the whole-image gather only; DATA.DEGRADE_JPEG_PROB and
-    DATA.DEGRADE_SECOND follow DATA.DEGRADE; DATA.DEGRADE2_RESIZE follows DATA.DEGRADE_SECOND."""
+    DATA.DEGRADE_SECOND and DATA.DEGRADE_RESIZE follow DATA.DEGRADE; DATA.DEGRADE2_RESIZE follows DATA.DEGRADE_SECOND."""
     data = config.DATA
     if data.get("DEGRADE", False) and not data.get("ON_DEVICE_WHOLE_IMAGES", False):
         raise ValueError("DATA.DEGRADE needs DATA.ON_DEVICE_WHOLE_IMAGES = True: the per-sample blur and noise are made by the "
@@ -1278,6 +1481,10 @@ def check_switches(config) -> None:
         raise ValueError("DATA.DEGRADE_SECOND needs DATA.DEGRADE = True: the second-order stage (sst_filter2d, DESIGN.md section 23) works "
                          "on the first stage's quantised LR batch (set DEGRADE_BLUR_PROB = DEGRADE_NOISE_PROB = 0 for the second "
                          "stage alone)")
+    if data.get("DEGRADE_RESIZE", False) and not data.get("DEGRADE", False):
+        raise ValueError("DATA.DEGRADE_RESIZE needs DATA.DEGRADE = True: the first stage's random resize (sst_blur, sst_rescale_to, "
+                         "DESIGN.md section 25) sits between that stage's blur and its noise and takes both from the same per-sample "
+                         "rows (set DEGRADE_BLUR_PROB = DEGRADE_NOISE_PROB = 0 for the resize alone)")
     if data.get("DEGRADE2_RESIZE", False) and not data.get("DEGRADE_SECOND", False):
         raise ValueError("DATA.DEGRADE2_RESIZE needs DATA.DEGRADE_SECOND = True: the random resize round trip (sst_rescale, DESIGN.md "
                          "section 24) is a pass of the second-order stage, between its blur and its final sinc / JPEG")
@@ -1293,6 +1500,11 @@ def announce_degradation(config, degradation: Degradation, second: SecondOrder |
     import warnings
     from .loss import BackProjectionLoss
     print(f"[Data] DATA.DEGRADE: lr = quantise(clamp(bicubic(gt * k) + n)) per sample in the gather launch, {degradation!r}")
+    if degradation.has_resize:
+        print("[Data] DATA.DEGRADE_RESIZE: instead lr = quantise(clamp(resize(resize(gt * k) + n))) per sample, to a size of its own, n "
+              "there, then to the LR size, no antialias (plain gather, sst_blur, sst_rescale_to: three launches for the one)"
+              + ("" if degradation._fixed else f": (up, down, keep) = {degradation.resize_prob}, scale in {degradation.resize_range}, "
+                                               f"modes {degradation.resize_modes}"))
     if degradation.has_jpeg:
         print(f"[Data] DATA.DEGRADE: then lr = jpeg(lr) in a second launch (sst_jpeg, integer codec, chroma {degradation.jpeg_chroma})"
               + ("" if degradation._fixed else f": quality uniform in {degradation.jpeg_quality} with probability {degradation.jpeg_prob:g}"))

@@ -21,7 +21,11 @@ through the sinc low-pass filter of the second-order degradation (device_data.fi
 DATA.DEGRADE2_KSIZE): after degrade(gt), or the plain bicubic LR made from gt, and before the JPEG stage.  The head line names it.
 With config.DATA.VALIDATE_DEGRADE_RESIZE = s (or degrade_resize=s, or --degrade-resize S; 0.25 <= s <= 2) that input also goes through
 the resize round trip of the second-order degradation (device_data.rescale: bicubic to the scale s and bicubic back, no noise): after
-degrade(gt), or the plain bicubic LR made from gt, and before the sinc stage.  The head line names it."""
+degrade(gt), or the plain bicubic LR made from gt, and before the sinc stage.  The head line names it.
+With config.DATA.VALIDATE_DEGRADE_RESIZE1 = (s, m1, m2) (or degrade_resize1=(...), or --degrade-resize1 S[,M1,M2]; 0.125 <= s <= 2) that
+input is made through the first stage's random resize (device_data.blur, then device_data.rescale_to): the blur of VALIDATE_DEGRADE,
+gt to the scale s with the mode m1, the noise there, to the LR size with m2 - in the antialiased bicubic's place, before every other
+stage.  The head line names it."""
 from __future__ import annotations
 
 import argparse
@@ -120,6 +124,26 @@ def _resize_param(config, degrade_resize):
     return float(degrade_resize)
 
 
+def _resize1_param(config, degrade_resize1):
+    """None, or the first stage's resize as (s, m1, m2), s a float in [0.125, 2] and the modes names of device_data.RESIZE_MODES
+    (a bare s, or (s,): bicubic both ways): the argument, else config.DATA.VALIDATE_DEGRADE_RESIZE1."""
+    from .device_data import RESIZE_MODES
+    if degrade_resize1 is None:
+        degrade_resize1 = config.DATA.get("VALIDATE_DEGRADE_RESIZE1", None)
+    if degrade_resize1 is None:
+        return None
+    v = tuple(degrade_resize1) if isinstance(degrade_resize1, (tuple, list)) else (degrade_resize1,)
+    v = v + ("bicubic", "bicubic") if len(v) == 1 else v
+    try:
+        ok = len(v) == 3 and 0.125 <= float(v[0]) <= 2 and v[1] in RESIZE_MODES and v[2] in RESIZE_MODES
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"VALIDATE_DEGRADE_RESIZE1: expected (s, m1, m2), s in [0.125, 2], the modes of {tuple(RESIZE_MODES)}, got "
+                         f"{degrade_resize1!r}")
+    return float(v[0]), v[1], v[2]
+
+
 _sinc_banks = {}
 
 
@@ -132,23 +156,34 @@ def _round_trip(lr, s):
     return rescale(lr, torch.from_numpy(rows))
 
 
-def _degraded_input(hr_img, idx, config, degrade, jpeg=None, sinc=None, resize=None):
-    """The generator's input under VALIDATE_DEGRADE / VALIDATE_DEGRADE_RESIZE / VALIDATE_DEGRADE_SINC / VALIDATE_DEGRADE_JPEG:
-    degrade(hr) with the fixed parameters and key = the image's index (without VALIDATE_DEGRADE: neither blur nor noise, the plain
-    bicubic's bits), then the resize round trip at scale resize (bicubic both ways, no noise), then the sinc filter at cutoff sinc,
-    then the JPEG stage at quality jpeg."""
+def _degraded_input(hr_img, idx, config, degrade, jpeg=None, sinc=None, resize=None, resize1=None):
+    """The generator's input under VALIDATE_DEGRADE / VALIDATE_DEGRADE_RESIZE1 / VALIDATE_DEGRADE_RESIZE / VALIDATE_DEGRADE_SINC /
+    VALIDATE_DEGRADE_JPEG: degrade(hr) with the fixed parameters and key = the image's index (without VALIDATE_DEGRADE: neither blur
+    nor noise, the plain bicubic's bits) - with resize1 = (s, m1, m2) the stage with its resize instead (degrade(resize_rows=): the
+    blur, hr to the scale s with m1, the noise there, to the LR size with m2) - then the resize round trip at scale resize (bicubic
+    both ways, no noise), then the sinc filter at cutoff sinc, then the JPEG stage at quality jpeg."""
     from .device_data import Degradation
     from .device_data import degrade as degrade_op
     ksize = int(config.DATA.get("DEGRADE_BLUR_KSIZE", 21))
     chroma = config.DATA.get("DEGRADE_JPEG_CHROMA", "420")
+    if resize1:
+        deg = Degradation.fixed(*(degrade or (0.0, 0.0, 0.0, 0.0)), key=idx, ksize=ksize, jpeg=jpeg or 0, jpeg_chroma=chroma,
+                                resize=resize1)
+        rows = deg.draw(1)
+        first = deg.draw_resize(1, hr_img.shape[2], hr_img.shape[3], deg_rows=rows).to(hr_img.device)
+        rows = rows.to(hr_img.device)
+        if not (sinc or resize):
+            return degrade_op(hr_img.to(torch.float32), rows, int(config.DATA.UPSCALE_FACTOR), ksize,
+                              jpeg_chroma=chroma if jpeg else None, resize_rows=first)
     if sinc or resize:
         from . import kernels
         from .device_data import filter2d, filter_rows
         from .device_data import jpeg as jpeg_op
         k2 = int(config.DATA.get("DEGRADE2_KSIZE", 21))
-        deg = Degradation.fixed(*(degrade or (0.0, 0.0, 0.0, 0.0)), key=idx, ksize=ksize, jpeg=jpeg or 0, jpeg_chroma=chroma)
-        rows = deg.draw(1).to(hr_img.device)
-        lr = degrade_op(hr_img.to(torch.float32), rows, int(config.DATA.UPSCALE_FACTOR), ksize)
+        if not resize1:
+            deg = Degradation.fixed(*(degrade or (0.0, 0.0, 0.0, 0.0)), key=idx, ksize=ksize, jpeg=jpeg or 0, jpeg_chroma=chroma)
+            rows, first = deg.draw(1).to(hr_img.device), None
+        lr = degrade_op(hr_img.to(torch.float32), rows, int(config.DATA.UPSCALE_FACTOR), ksize, resize_rows=first)
         if resize:
             lr = _round_trip(lr, resize)
         if sinc:
@@ -165,7 +200,7 @@ def _degraded_input(hr_img, idx, config, degrade, jpeg=None, sinc=None, resize=N
 
 
 def _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params=None, with_lr=False, degrade=None,
-                       jpeg=None, sinc=None, resize=None):
+                       jpeg=None, sinc=None, resize=None, resize1=None):
     """The per-image loop of _validate with everything on the device: generator forward -> sst_image_metrics into row idx of one
     [N,2] result buffer, ONE device-to-host copy after the loop.  Nothing syncs per image unless save_images is set (the uint8
     images tensor2img would make then cross per image and are written by _save_png).  st_params: also st_distance(output, hr) per
@@ -179,8 +214,8 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
         for idx, (hr_img, lr_img) in enumerate(val_loader):
             lr_img = lr_img.to(config.DEVICE, non_blocking=True)
             hr_img = hr_img.to(config.DEVICE, non_blocking=True)
-            if degrade or jpeg or sinc or resize:
-                lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg, sinc, resize)
+            if degrade or jpeg or sinc or resize or resize1:
+                lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg, sinc, resize, resize1)
             output = generator(lr_img)
             row = results[idx:idx + 1]
             if save_images:
@@ -201,7 +236,8 @@ def _metrics_on_device(generator, val_loader, config, save_images, concat_with_g
 
 
 def _validate(generator, val_loader, config, save_images=False, concat_with_gt=False, save_metrics=False, on_device=None,
-              with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None, degrade_sinc=None, degrade_resize=None):
+              with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None, degrade_sinc=None, degrade_resize=None,
+              degrade_resize1=None):
     """degrade: None = config.DATA.VALIDATE_DEGRADE; (sigma1, sigma2, theta_deg, noise) = the generator's input is degrade(hr)
     (_degraded_input) instead of the loader's LR image, and the printed line and _metrics.txt start by saying so.
     degrade_jpeg: None = config.DATA.VALIDATE_DEGRADE_JPEG; Q in 1..100 = that input, or without `degrade` the plain bicubic LR made
@@ -210,6 +246,9 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
     before the JPEG stage, and the head line names it.
     degrade_resize: None = config.DATA.VALIDATE_DEGRADE_RESIZE; s in [0.25, 2] = that input goes through the resize round trip at
     this scale (bicubic both ways, no noise) before the sinc filter, and the head line names it.
+    degrade_resize1: None = config.DATA.VALIDATE_DEGRADE_RESIZE1; (s, m1, m2), s in [0.125, 2] = that input is made through the first
+    stage's resize (the blur, hr to the scale s with m1, the noise there, to the LR size with m2) instead of the antialiased bicubic,
+    before every other stage, and the head line names it.
     on_device: None = config.DATA.VALIDATE_ON_DEVICE; True = metrics by the HIP kernel, one host copy per pass
     (_metrics_on_device); False = the host loop below.  Same averages, same printed line, same _metrics.txt either way.
     with_st: None = config.DATA.VALIDATE_ST; True = every image also gets st.st_distance(output, hr) with the configured ``ST``
@@ -235,10 +274,13 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
     jpeg = _jpeg_param(config, degrade_jpeg)
     sinc = _sinc_param(config, degrade_sinc)
     resize = _resize_param(config, degrade_resize)
-    parts, made = [], "degrade(GT)" if degrade else "bicubic(GT)"               # the head line: what made the input, then its parameters
+    resize1 = _resize1_param(config, degrade_resize1)
+    parts, made = [], "degrade(GT)" if degrade else ("GT" if resize1 else "bicubic(GT)")              # the head line: what made the input, then its parameters
     if degrade:
         parts.append("sigma {:g} / {:g}, theta {:g} deg, noise {:g}".format(*degrade))
-    for on, name, part in ((resize, "resize", f"resize round trip at scale {resize:g} (bicubic)" if resize else ""),
+    for on, name, part in ((resize1, "resize1", "first-stage resize at scale {:g} ({}, then {} to the LR size)".format(*resize1)
+                            if resize1 else ""),
+                           (resize, "resize", f"resize round trip at scale {resize:g} (bicubic)" if resize else ""),
                            (sinc, "sinc", f"sinc cutoff {sinc:g}" if sinc else ""),
                            (jpeg, "jpeg", f"JPEG quality {jpeg} ({config.DATA.get('DEGRADE_JPEG_CHROMA', '420')})" if jpeg else "")):
         if on:
@@ -255,7 +297,7 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
     all_psnr, all_ssim, all_st, all_lr = [], [], [], []
     if on_device:
         all_psnr, all_ssim, all_st, all_lr = _metrics_on_device(generator, val_loader, config, save_images, concat_with_gt, st_params,
-                                                                with_lr, degrade, jpeg, sinc, resize)
+                                                                with_lr, degrade, jpeg, sinc, resize, resize1)
         if file:
             for idx, (psnr, ssim) in enumerate(zip(all_psnr, all_ssim)):
                 st_col = f" | ST: {all_st[idx]:.4f}" if with_st else ""
@@ -266,8 +308,8 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
             for idx, (hr_img, lr_img) in enumerate(val_loader):
                 lr_img = lr_img.to(config.DEVICE)
                 hr_img = hr_img.to(config.DEVICE)
-                if degrade or jpeg or sinc or resize:
-                    lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg, sinc, resize)
+                if degrade or jpeg or sinc or resize or resize1:
+                    lr_img = _degraded_input(hr_img, idx, config, degrade, jpeg, sinc, resize, resize1)
                 output = generator(lr_img)
                 if save_images:
                     path = os.path.join(config.DATA.TEST_SR_IMAGES_DIR, config.EXP.NAME)
@@ -307,7 +349,8 @@ def _validate(generator, val_loader, config, save_images=False, concat_with_gt=F
 
 
 def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_gt: bool = False, dataset=None, on_device=None,
-         with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None, degrade_sinc=None, degrade_resize=None):
+         with_st=None, tile=None, with_lr=None, degrade=None, degrade_jpeg=None, degrade_sinc=None, degrade_resize=None,
+         degrade_resize1=None):
     if not g_path:                # the averaged generator's best when the run kept one (SOLVER.G_EMA_DECAY), else the last iterate's
         g_path = f"results/{config.EXP.NAME}/g_ema_best.pth"
         if not os.path.exists(g_path):
@@ -324,7 +367,7 @@ def test(config: Config, save_images: bool = True, g_path: str = None, concat_w_
         generator.eval()
     return _validate(generator, loader, config, save_images=save_images, concat_with_gt=concat_w_gt, save_metrics=True,
                      on_device=on_device, with_st=with_st, tile=tile, with_lr=with_lr, degrade=degrade, degrade_jpeg=degrade_jpeg,
-                     degrade_sinc=degrade_sinc, degrade_resize=degrade_resize)
+                     degrade_sinc=degrade_sinc, degrade_resize=degrade_resize, degrade_resize1=degrade_resize1)
 
 
 if __name__ == "__main__":
@@ -348,6 +391,10 @@ if __name__ == "__main__":
     parser.add_argument("--degrade-resize", type=float, default=None, metavar="S",
                         help="also take that input through the resize round trip at scale S in [0.25, 2] (bicubic both ways, no noise), "
                              "before the sinc stage (DATA.VALIDATE_DEGRADE_RESIZE)")
+    parser.add_argument("--degrade-resize1", type=str, default=None, metavar="S[,M1,M2]",
+                        help="make that input through the first stage's random resize at scale S in [0.125, 2] of the HR size: mode M1 "
+                             "there, M2 to the LR size (area | bilinear | bicubic; default bicubic), before every other stage "
+                             "(DATA.VALIDATE_DEGRADE_RESIZE1)")
     a = parser.parse_args()
     cfg = Config()
     if a.name:
@@ -359,4 +406,5 @@ if __name__ == "__main__":
     test(cfg, save_images=not a.no_images, g_path=a.g_path, on_device=True if a.on_device else None,
          with_st=True if a.st else None, tile=a.tile, with_lr=True if a.lr_consistency else None,
          degrade=tuple(float(v) for v in a.degrade.split(",")) if a.degrade else None, degrade_jpeg=a.degrade_jpeg,
-         degrade_sinc=a.degrade_sinc, degrade_resize=a.degrade_resize)
+         degrade_sinc=a.degrade_sinc, degrade_resize=a.degrade_resize,
+         degrade_resize1=(lambda v: (float(v[0]),) + tuple(v[1:]))(a.degrade_resize1.split(",")) if a.degrade_resize1 else None)

@@ -49,6 +49,13 @@ difference between two legs).  Prints one JSON line.
         # every sample at the scale 0.3, 1.0 and 1.2 and with the drawn rows (up, down, keep = 0.3, 0.4, 0.3); pass A unquantised;
         # the whole batch with resize on; and the drawn round trips as torch ops - one F.interpolate pair PER SAMPLE, since the
         # intermediate sizes differ per sample, with randn noise between them - the yardstick for sst_rescale alone
+    python tools/time_loader.py resize1 [--launches L] [--replays R] [--repeat N] [--parent-lib PATH [--parent-first]]
+        # the first stage's random resize (DATA.DEGRADE_RESIZE), same sizes and method, every sample with blur (K = 21) and noise.
+        # Legs: the off path = the fused sst_gather_crops_degraded (and, with --parent-lib, the same launch through another build of
+        # the library in the same process); the plain gather writing gt alone; sst_blur alone; sst_rescale_to alone on the blurred
+        # batch with every sample at the scale 0.15, 1.0 and 1.5 and with the drawn rows (up, down, keep = 0.2, 0.7, 0.1); the whole
+        # three-launch first stage; and the same stage as torch ops behind the plain gather (reflect pad, grouped conv2d, one
+        # F.interpolate pair PER SAMPLE with randn noise between them, clamp, round) - the yardstick
 """
 import argparse
 import json
@@ -735,8 +742,144 @@ def resize_mode(launches, replays, repeat, parent_lib, parent_first=False):
     print(json.dumps(out))
 
 
+def resize1_mode(launches, replays, repeat, parent_lib, parent_first=False):
+    import ctypes
+    from srganst import _abi
+    from srganst.device_data import RESIZE_MODES, Degradation, DeviceImageArena, blur, rescale_to, resize1_size
+    g = torch.Generator().manual_seed(0)
+    imgs = [torch.randint(0, 256, (h, w, 3), generator=g, dtype=torch.uint8) for h, w in WHOLE_SIZES * 2]
+    arena = DeviceImageArena.from_arrays(imgs, HR, HR, UP, "cuda")
+    n, K, o = launches * B, 21, HR // UP
+    tiles = torch.from_numpy(arena.tiles)[torch.randperm(len(arena), generator=g)[:n]]
+    room = torch.from_numpy(arena.table_host[tiles[:, 0].numpy(), 1:3] - HR + 1)
+    desc = torch.zeros(n, 4, dtype=torch.int32)
+    desc[:, 0] = tiles[:, 0]
+    desc[:, 1:3] = (torch.randint(0, 1 << 30, (n, 2), generator=g) % room).to(torch.int32)
+    desc[:, 3] = torch.randint(0, 8, (n,), generator=g).to(torch.int32)
+    arena.check_desc(desc.numpy())
+    desc = desc.cuda()
+    first = Degradation(resize_prob=(0.2, 0.7, 0.1))
+    deg_host = first.draw(n, torch.Generator().manual_seed(1))
+    drawn_host = first.draw_resize(n, HR, HR, torch.Generator().manual_seed(5), deg_rows=deg_host.numpy())
+    deg, drawn = deg_host.cuda(), drawn_host.cuda()
+
+    def at_scale(s):                                     # every sample at the scale s, the drawn modes (keep: bicubic there) and noise
+        r = drawn_host.clone()
+        r[:, 0] = r[:, 1] = resize1_size(HR, s)
+        r[drawn_host[:, 0] == 0, 6] |= RESIZE_MODES["bicubic"]
+        return r.cuda()
+    gt, lr = torch.empty(B, 3, HR, HR, device="cuda"), torch.empty(B, 3, o, o, device="cuda")
+    hr = torch.empty_like(gt)
+    sl = lambda k: slice(k * B, (k + 1) * B)
+
+    def off(k):
+        arena.crops(desc[sl(k)], gt, lr, deg=deg[sl(k)], ksize=K)
+
+    def whole(k):
+        arena.crops(desc[sl(k)], gt, with_lr=False)
+        rescale_to(blur(gt, deg[sl(k)], K, out=hr), drawn[sl(k)], (o, o), out=lr)
+
+    # ---- the comparator: the same first stage as torch ops behind the plain gather - reflect pad and a grouped conv2d with the
+    # per-sample weights (made beforehand), then one F.interpolate pair PER SAMPLE (the intermediate sizes differ per sample), randn
+    # noise between them, clamp, round
+    interp, pad, conv2d = torch.nn.functional.interpolate, torch.nn.functional.pad, torch.nn.functional.conv2d
+    names = {v: k for k, v in RESIZE_MODES.items()}
+    sn = drawn[:, 2].contiguous().view(torch.float32)
+    plan = [(int(r[0]), int(r[1]), names[int(r[6]) & 3], names[(int(r[6]) >> 2) & 3]) for r in drawn_host.tolist()]
+    q = deg[:, :3].contiguous().view(torch.float32).double()
+    d = torch.arange(-(K // 2), K // 2 + 1, device="cuda", dtype=torch.float64)
+    dy, dx = d[None, :, None], d[None, None, :]
+    wts = torch.exp(-(q[:, 0, None, None] * dx * dx + q[:, 1, None, None] * dx * dy + q[:, 2, None, None] * dy * dy))
+    wts = (wts / wts.sum((1, 2), keepdim=True)).float()
+    ident = torch.zeros(K, K, device="cuda")
+    ident[K // 2, K // 2] = 1.0
+    wts[q[:, 0] < 0] = ident                             # the no-blur sentinel: the identity kernel, the same ops for every sample
+    wts = wts.repeat_interleave(3, 0)[:, None].contiguous()
+    p = K // 2
+    mode_kw = lambda m: {} if m == "area" else {"align_corners": False}
+
+    def torch_resize(k, src):
+        for b in range(B):
+            i = k * B + b
+            hi, wi, m1, m2 = plan[i]
+            v = src[b:b + 1]
+            if hi:
+                v = interp(v, size=(hi, wi), mode=m1, **mode_kw(m1))
+            v = v + sn[i] * torch.randn(1, 3, v.shape[2], v.shape[3], device="cuda")
+            v = interp(v, size=(o, o), mode=m2, **mode_kw(m2))
+            lr[b:b + 1] = torch.round(v.clamp(0, 1) * 255) / 255
+
+    def torch_leg(k):
+        arena.crops(desc[sl(k)], gt, with_lr=False)
+        x = pad(gt, (p, p, p, p), mode="reflect").reshape(1, B * 3, HR + 2 * p, HR + 2 * p)
+        torch_resize(k, conv2d(x, wts[k * B * 3:(k + 1) * B * 3], groups=B * 3).reshape(B, 3, HR, HR))
+
+    # the comparator is the kernel's model: without noise the two agree but for pixels whose rounding the summation order decides
+    arena.crops(desc[sl(0)], gt, with_lr=False)
+    blur(gt, deg[sl(0)], K, out=hr)
+    quiet = drawn[sl(0)].clone()
+    quiet[:, 2] = 0
+    want = rescale_to(hr, quiet, (o, o))
+    sn_keep = sn.clone()
+    sn.zero_()
+    torch_resize(0, hr)
+    sn.copy_(sn_keep)
+    differ = float((((lr - want).abs() * 255) > 0.5).float().mean())
+    assert differ < 0.05, f"the torch resize pair and sst_rescale_to differ on {differ:.3f} of the pixels"
+
+    legs = {"off_degraded_gather_k21": off}
+    if parent_lib:
+        other = ctypes.CDLL(parent_lib)
+        other.sst_gather_crops_degraded.restype, other.sst_gather_crops_degraded.argtypes = _abi.SIGNATURES["sst_gather_crops_degraded"]
+        wy, iy, wx, ix = arena._bicubic.tables_i32(HR, HR, 1.0 / UP, arena.device)
+
+        def parent(k):
+            rc = other.sst_gather_crops_degraded(arena.arena.data_ptr(), arena.arena.numel(), arena.table.data_ptr(), arena.n_images,
+                                                 desc[sl(k)].data_ptr(), B, HR, arena.lut.data_ptr(), gt.data_ptr(), lr.data_ptr(),
+                                                 wy.data_ptr(), iy.data_ptr(), wx.data_ptr(), ix.data_ptr(), o, o, wy.shape[1], wx.shape[1],
+                                                 arena.span(True, True), deg[sl(k)].data_ptr(), K, 1, _abi.stream_ptr())
+            assert rc == 0, rc
+        legs["off_degraded_gather_k21_parent_lib"] = parent
+        if parent_first:                                 # the same two legs in the other order: what the order alone is worth
+            legs = {"off_degraded_gather_k21_parent_lib": parent, "off_degraded_gather_k21": off}
+    legs["plain_gather_gt_alone"] = lambda k: arena.crops(desc[sl(k)], gt, with_lr=False)
+    legs["blur_alone"] = lambda k: blur(gt, deg[sl(k)], K, out=hr)
+    for s in (0.15, 1.0, 1.5):
+        legs[f"rescale_to_alone_s{s:g}"] = lambda k, r=at_scale(s): rescale_to(hr, r[sl(k)], (o, o), out=lr)
+    legs["rescale_to_alone_drawn"] = lambda k: rescale_to(hr, drawn[sl(k)], (o, o), out=lr)
+    legs["first_stage_three_launches"] = whole
+    legs["torch_ops_first_stage"] = torch_leg
+
+    graphs = {}
+    for name, run in legs.items():
+        for k in range(min(3, launches)):               # warm up: tables, code objects, the allocator's pool
+            run(k)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            for k in range(launches):
+                run(k)
+        gr.replay()
+        graphs[name] = gr
+    torch.cuda.synchronize()
+    out = {"mode": "resize1", "batch": B, "hr": HR, "scale": UP, "launches_per_graph": launches, "replays": replays, "repeat": repeat,
+           "torch_ops_pixels_off_by_a_level": round(differ, 5),
+           "us_per_batch": {name: [] for name in legs}}
+    for _ in range(repeat):
+        for name, gr in graphs.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(replays):
+                gr.replay()
+            t1.record()
+            torch.cuda.synchronize()
+            out["us_per_batch"][name].append(round(t0.elapsed_time(t1) * 1e3 / (replays * launches), 2))
+    out["median_us_per_batch"] = {name: sorted(v)[len(v) // 2] for name, v in out["us_per_batch"].items()}
+    print(json.dumps(out))
+
+
 def main():
-    if len(sys.argv) > 1 and sys.argv[1] in ("second", "resize"):
+    if len(sys.argv) > 1 and sys.argv[1] in ("second", "resize", "resize1"):
         ap = argparse.ArgumentParser()
         ap.add_argument("mode")
         ap.add_argument("--launches", type=int, default=32)
@@ -745,7 +888,7 @@ def main():
         ap.add_argument("--parent-lib", default="", help="another build of libsrganst.so whose off path is timed beside this one's")
         ap.add_argument("--parent-first", action="store_true", help="time the parent library's leg before this library's")
         a = ap.parse_args()
-        mode = second_mode if a.mode == "second" else resize_mode
+        mode = {"second": second_mode, "resize": resize_mode, "resize1": resize1_mode}[a.mode]
         return mode(a.launches, a.replays, a.repeat, a.parent_lib, a.parent_first)
     if len(sys.argv) > 1 and sys.argv[1] == "jpeg":
         ap = argparse.ArgumentParser()
